@@ -19,7 +19,9 @@ Beside the headline (never part of `value`), at N = 1:
   cpu_baseline    the reference's LZ4 path on the host cores (bounded sample)
 Corpus: S-mix (tools/corpus.c) unless SILESIA_DIR names a directory with the silesia files.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]   (N>1 via torch.distributed.run)
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]   (N>1 via torch.distributed.run)
+--dump-outputs DIR: after the timed steps, what the last one computed (rank 0's) is written as DIR/<name>.npy (float64 per-block
+arrays, float32 seeded byte samples of the .4mc image and of the decoded output; 34 MB at most), for comparing two builds.
 """
 import argparse
 import ctypes as C
@@ -133,7 +135,10 @@ def main():
     ap.add_argument("--config", choices=["fast", "ultra_logs"], default="fast",
                     help="fast: BASELINE configs[1], 4mc Fast on the S-mix (the headline).  ultra_logs: configs[4]'s codec and corpus - 4mz Ultra (zstd 12) on the "
                          "synthetic log corpus, block ranges per rank, the footer index gathered over RCCL, then decoded rank by rank (no collective)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -225,6 +230,29 @@ def main():
         if record:
             torch.cuda.synchronize()
             phase["compress"].append(e[0].elapsed_time(e[4])); phase["decompress"].append(e[5].elapsed_time(e[7]))
+
+    DUMP_SAMPLE = 4 << 20                          # bytes sampled from the image and from the output (float32: 16 MB each)
+
+    def dump_outputs(dirname):
+        """What a caller of the timed path receives from its last step: per block the stored payload size, the XXH32 of the payload,
+        the block's offset in the .4mc file and the decoded size (float64, exact), and bytes of the packed image (block headers +
+        payloads; the 12-byte file header is not part of the step) and of the decoded output at fixed positions drawn with a fixed
+        seed (float32, exact)."""
+        os.makedirs(dirname, exist_ok=True)
+        csz, dec, img_off = state["csz"], state["dec"], state["img_off"]
+        img_end = int((state["loc_off"][-1] + 12 + csz[-1]).item())
+        rng = np.random.default_rng(0x4D43)
+        def sample(t, lo, hi):
+            pos = np.arange(lo, hi) if hi - lo <= DUMP_SAMPLE else np.sort(rng.integers(lo, hi, DUMP_SAMPLE))
+            return t[torch.from_numpy(pos.astype(np.int64)).to(dev)].cpu().numpy().astype(np.float32)
+        out = {"compressed_sizes": csz.cpu().numpy().astype(np.float64),
+               "checksums": (enc.d.view(torch.int32).view(nb, 8)[:, 7].to(torch.int64) & 0xFFFFFFFF).cpu().numpy().astype(np.float64),
+               "image_offsets": img_off.cpu().numpy().astype(np.float64),
+               "decoded_sizes": dec[:, 6].cpu().numpy().astype(np.float64),
+               "image_sample": sample(d_image, 12, img_end),
+               "output_sample": sample(d_out, 0, nb * B)}
+        for name, a in out.items():
+            np.save(os.path.join(dirname, name + ".npy"), a)
 
     def kernel_times():
         """Per-kernel launch durations with events on the launch stream, in an extra pass after the timed steps (the fused
@@ -515,6 +543,8 @@ def main():
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     own_wall = wall
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs)
     per_rank = None; rccl_ranks = None
     if world > 1:
         w = torch.tensor([wall], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")

@@ -2,6 +2,7 @@
 """Generates tests/golden/*.json from the REFERENCE ITSELF, run in the build container:
   - oracle/_ref/4mc_ref     (reference CLI built from /root/reference/native by oracle/Makefile)
   - oracle/_ref/libref4mc.so (reference codecs)
+  - the reference's shipped libhadoop-4mc.so, driven through tests/jni_mock/mock_jni.c (jni_reference_artifact.json)
 The fixtures are DATA only: inputs (or their generator parameters) and expected outputs.
 Re-run:  make -C oracle ref && python tests/golden/make_golden.py
 """
@@ -9,6 +10,7 @@ import ctypes as C
 import hashlib
 import json
 import os
+import pathlib
 import subprocess
 import sys
 import tempfile
@@ -88,6 +90,16 @@ for name, d in zin.items():
         assert not ref.ZSTD_isError(r)
         zf[name]["frames"][str(lvl)] = out[:r].tobytes().hex()
 json.dump(zf, open(os.path.join(HERE, "zstd_frames.json"), "w"))
+
+# the reference's shipped JNI library through the mock JNIEnv driver: stdout, size + SHA-256 of every payload, stream sizes
+from test_jni_reference_artifact import REF_SO, RUNS, run_driver  # noqa: E402
+assert os.path.exists(REF_SO), REF_SO
+jni = {}
+for name, cfg in RUNS.items():
+    with tempfile.TemporaryDirectory() as d:
+        _, rec = run_driver(REF_SO, pathlib.Path(d), **cfg)
+    jni[name] = dict(cfg, **rec)
+json.dump(jni, open(os.path.join(HERE, "jni_reference_artifact.json"), "w"), indent=1)
 
 json.dump(files, open(os.path.join(HERE, "small_files.json"), "w"), indent=0)
 json.dump(manifest, open(os.path.join(HERE, "corpus_manifest.json"), "w"))

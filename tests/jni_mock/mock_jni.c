@@ -57,6 +57,7 @@ static void dump(const char* dir, const char* name, const void* p, long n)
     char path[1024];
     snprintf(path, sizeof path, "%s/%s.bin", dir, name);
     FILE* f = fopen(path, "wb");
+    if (!f) { fprintf(stderr, "mock: cannot write %s\n", path); exit(2); }
     if (n > 0) fwrite(p, 1, (size_t)n, f);
     fclose(f);
 }
@@ -179,7 +180,7 @@ int main(int argc, char** argv)
          * their sizes so that the test can compare every one with the oracle, then each is decompressed again. */
         const int chunk = atoi(argv[5]);
         for (int c = 0; c < 2; c++) {
-            char ccls[32], dcls[32], name[96];
+            char ccls[32], dcls[32], name[1024];
             snprintf(ccls, sizeof ccls, "%sCompressor", codecs[c]);
             snprintf(dcls, sizeof dcls, "%sDecompressor", codecs[c]);
             ((init_fn)sym(lib, ccls, "initIDs"))(&env, (jclass)ccls);
@@ -189,6 +190,7 @@ int main(int argc, char** argv)
             FILE* fo = fopen(name, "wb");
             snprintf(name, sizeof name, "%s/%s_stream.sizes", dir, codecs[c]);
             FILE* fs = fopen(name, "w");
+            if (!fo || !fs) { fprintf(stderr, "mock: cannot write %s\n", name); return 2; }
             int calls = 0, bad = 0, thrown = 0;
             for (int at = 0; at < n; at += chunk, calls++) {
                 const int len = n - at < chunk ? n - at : chunk;

@@ -1,6 +1,7 @@
 """GPU: the 35 JNI entry points of libhadoop-4mc.so driven through a mock JNIEnv (tests/jni_mock/mock_jni.c,
 no JVM): field protocol, return values, InternalError text, and bytes equal to the oracle's for every codec call
 (native/jniCompressor.c:72-168, jniDecompressor.c:67-100, jniZstdCompressor.c:74-173, jniZstdDecompressor.c:69-102)."""
+import hashlib
 import os
 import subprocess
 
@@ -57,9 +58,31 @@ def test_jni_lz4_compressor_under_the_tolerance_switch(gpu, tmp_path):
     assert np.array_equal(np.fromfile(os.path.join(str(tmp_path), "Lz4_compressBytesDirectHC.bin"), dtype=np.uint8), wbytes)
 
 
+def record_of_run(stdout, out_dir):
+    """What one run of the mock driver left, as data: its stdout, the size and SHA-256 of every .bin it wrote and the stream sizes
+    (tests/golden/jni_reference_artifact.json holds such records of the reference's shipped library)."""
+    files, sizes = {}, {}
+    for f in sorted(os.listdir(str(out_dir))):
+        path = os.path.join(str(out_dir), f)
+        if f.endswith(".bin") and f != "in.bin":
+            b = open(path, "rb").read()
+            files[f] = {"bytes": len(b), "sha256": hashlib.sha256(b).hexdigest()}
+        elif f.endswith("_stream.sizes"):
+            sizes[f[: -len("_stream.sizes")]] = [int(x) for x in open(path).read().split()]
+    return {"stdout": stdout, "files": files, "sizes": sizes}
+
+
+def same_bytes(out, name, want):
+    """`name` as the driver wrote it equals `want`; `out` is the driver's output directory or a record_of_run of one"""
+    if isinstance(out, dict):
+        return out["files"].get(name) == {"bytes": int(len(want)), "sha256": hashlib.sha256(want.tobytes()).hexdigest()}
+    return np.array_equal(np.fromfile(os.path.join(str(out), name), dtype=np.uint8), want)
+
+
 def check_jni_protocol(stdout, data, out_dir, level15_on_device):
     """What the mock driver's output has to show, whichever library it drove: this repository's (on the GPU) or the reference's
-    shipped artefact (tests/test_jni_reference_artifact.py, on the CPU) - the same expectations for both."""
+    shipped artefact (tests/test_jni_reference_artifact.py, on the CPU, from its stored record) - the same expectations for both
+    (SURVEY.md Appendix C.3)."""
     n = len(data)
     out = {}
     for line in stdout.splitlines():
@@ -79,7 +102,7 @@ def check_jni_protocol(stdout, data, out_dir, level15_on_device):
     for name, (wr, wbytes) in want.items():
         got_r, rest = out[name]
         assert got_r == wr and rest.startswith("- ") and "ulen_after=0" in rest, (name, got_r, wr, rest)
-        assert np.array_equal(np.fromfile(os.path.join(str(out_dir), name + ".bin"), dtype=np.uint8), wbytes), name
+        assert same_bytes(out_dir, name + ".bin", wbytes), name
         d, rest = out[name + "_roundtrip"]
         assert d == n and "same=1" in rest and "clen_after=0" in rest, (name, d, rest)
     # level 9: a level the shipped Java classes never pass - the reference serves every level, the device levels 1..12: a frame, no
@@ -106,14 +129,17 @@ def check_block_stream(stdout, data, out_dir, chunk):
                        ("Zstd", lambda s: helpers.orc_zstd_compress(s, 1))):
         line = [l for l in stdout.splitlines() if l.startswith(codec + "_stream ")][0]
         assert line.split()[1] == str(calls) and "bad=0 thrown=0" in line, line
-        sizes = [int(x) for x in open(os.path.join(str(out_dir), codec + "_stream.sizes")).read().split()]
-        blob = np.fromfile(os.path.join(str(out_dir), codec + "_stream.bin"), dtype=np.uint8)
-        assert len(sizes) == calls and sum(sizes) == len(blob)
-        at = 0
+        if isinstance(out_dir, dict):
+            sizes = out_dir["sizes"][codec]
+        else:
+            sizes = [int(x) for x in open(os.path.join(str(out_dir), codec + "_stream.sizes")).read().split()]
+        assert len(sizes) == calls
+        wants = []
         for k, sz in enumerate(sizes):
             r, want = orc(data[k * chunk: min(n, (k + 1) * chunk)])
-            assert sz == r and np.array_equal(blob[at: at + sz], want), (codec, k, sz, r)
-            at += sz
+            assert sz == r, (codec, k, sz, r)
+            wants.append(want)
+        assert same_bytes(out_dir, codec + "_stream.bin", np.concatenate(wants)), codec      # every chunk's bytes, back to back
 
 
 def test_raw_codecs_in_block_compressor_stream_shape(gpu, tmp_path):

@@ -51,7 +51,7 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert "debug" not in dyn and "fourmc_launch" not in dyn, "the product library exports debug symbols or internal launchers"
 
 
-def test_no_gpu_calls_fail_loudly_not_silently():
+def test_no_gpu_calls_fail_loudly_not_silently(tmp_path):
     """In this container there is no device: the engine must refuse, never fall back."""
     import torch
     if torch.cuda.is_available():
@@ -62,7 +62,7 @@ def test_no_gpu_calls_fail_loudly_not_silently():
     src = np.zeros(100, np.uint8); dst = np.zeros(200, np.uint8)
     assert L.fourmc_LZ4_compress_default(src.ctypes.data, dst.ctypes.data, 100, 200) == 0
     assert L.fourmc_LZ4_decompress_safe(src.ctypes.data, dst.ctypes.data, 100, 200) < 0
-    r = subprocess.run([p.cli_path(), "-f", __file__, "/tmp/_x.4mc"], capture_output=True)
+    r = subprocess.run([p.cli_path(), "-f", __file__, str(tmp_path / "_x.4mc")], capture_output=True)
     assert r.returncode == 1 and b"GPU engine error" in r.stderr
 
 
@@ -130,7 +130,7 @@ def test_block_index_queries_like_reference_unit_test():
     assert L.fourmc_index_align_end(a, 4, 450, 1000) == 1000
 
 
-def test_cli_flags_without_gpu():
+def test_cli_flags_without_gpu(tmp_path):
     p = helpers.pkg()
     r = subprocess.run([p.cli_path(), "-V"], capture_output=True)
     assert r.returncode == 0 and b"4mc CLI 64-bits" in r.stderr
@@ -138,5 +138,5 @@ def test_cli_flags_without_gpu():
     assert r.returncode == 0 and b"-z     : zstd compression" in r.stderr
     r = subprocess.run([p.cli_path(), "-Q", "x"], capture_output=True)
     assert r.returncode == 1 and b"Incorrect command line arguments" in r.stderr
-    r = subprocess.run([p.cli_path(), "-f", "/nonexistent/file", "/tmp/_y.4mc"], capture_output=True)
+    r = subprocess.run([p.cli_path(), "-f", "/nonexistent/file", str(tmp_path / "_y.4mc")], capture_output=True)
     assert r.returncode == 2 and b"Cannot open input file" in r.stderr

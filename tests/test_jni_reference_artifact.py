@@ -3,43 +3,56 @@ expectations the GPU test applies to this repository's library (tests/test_gpu_j
 field names and types read, buffer lengths reset, InternalError texts, return values - is thereby checked against the artefact,
 not against a reading of native/jniCompressor.c:72-168.  The compressed bytes the
 artefact returns are compared with the oracle's as well: one more pin of the oracle, on the prebuilt binary.
-Skipped where the reference tree is absent (the GPU box)."""
+The artefact's runs are stored as data in tests/golden/jni_reference_artifact.json (stdout, size and SHA-256 of every payload,
+stream sizes; written by tests/golden/make_golden.py), so the expectations are checked on every machine; where the artefact itself
+is present, a live run of it must reproduce that record as well."""
+import json
 import os
 import subprocess
 
-import pytest
-
 import helpers
-from test_gpu_jni import check_jni_protocol, check_block_stream
+from test_gpu_jni import check_jni_protocol, check_block_stream, record_of_run
 
 REF_SO = "/root/reference/java/hadoop-4mc/src/main/resources/com/fing/compression/fourmc/linux/amd64/libhadoop-4mc.so"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jni_reference_artifact.json")
+# the two driver runs recorded: the 35 entry points on one 1.5 MB buffer, and BlockCompressorStream-sized chunks of a 1 MB one
+RUNS = {"protocol": {"n": 1_500_000, "first_block": 6, "chunk": None},
+        "block_stream": {"n": 1_000_000, "first_block": 9, "chunk": 65536 - 65536 // 255 - 16}}
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="the reference's shipped library is not on this machine")
-def test_mock_jni_driver_against_the_reference_artifact(tmp_path):
+def run_driver(lib, tmp_path, n, first_block, chunk):
+    """the mock driver on `lib` over corpus(n, first_block) -> (input, record_of_run)"""
     exe = tmp_path / "mock_jni"
     subprocess.run(["gcc", "-O1", "-I" + os.path.join(helpers.ROOT, "include"), os.path.join(helpers.ROOT, "tests", "jni_mock", "mock_jni.c"),
                     "-ldl", "-o", str(exe)], check=True)
-    n = 1_500_000
-    data = helpers.corpus(n, first_block=6)
+    data = helpers.corpus(n, first_block=first_block)
     src = tmp_path / "in.bin"; src.write_bytes(data.tobytes())
-    r = subprocess.run([str(exe), REF_SO, str(src), str(n), str(tmp_path)], capture_output=True, text=True)
+    r = subprocess.run([str(exe), lib, str(src), str(n), str(tmp_path)] + ([str(chunk)] if chunk else []), capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    check_jni_protocol(r.stdout, data, tmp_path, level15_on_device=True)
+    return data, record_of_run(r.stdout, tmp_path)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="the reference's shipped library is not on this machine")
+def _artifact_run(name, tmp_path):
+    """the stored record of the artefact's run `name` (checked against a live run where the artefact is present) and its input"""
+    cfg = RUNS[name]
+    rec = json.load(open(GOLDEN))[name]
+    assert {k: rec[k] for k in cfg} == cfg, "fixture written for other inputs"
+    data = helpers.corpus(cfg["n"], first_block=cfg["first_block"])
+    if os.path.exists(REF_SO):
+        _, live = run_driver(REF_SO, tmp_path, **cfg)
+        assert live == {k: rec[k] for k in live}, "the reference's shipped library no longer gives the stored record"
+    return data, rec
+
+
+def test_mock_jni_driver_against_the_reference_artifact(tmp_path):
+    data, rec = _artifact_run("protocol", tmp_path)
+    check_jni_protocol(rec["stdout"], data, rec, level15_on_device=True)
+
+
 def test_block_stream_shape_against_the_reference_artifact(tmp_path):
     """the BlockCompressorStream call pattern (64 KiB-class buffers) on the artefact: the expectations of the GPU test hold there"""
-    exe = tmp_path / "mock_jni"
-    subprocess.run(["gcc", "-O1", "-I" + os.path.join(helpers.ROOT, "include"), os.path.join(helpers.ROOT, "tests", "jni_mock", "mock_jni.c"),
-                    "-ldl", "-o", str(exe)], check=True)
-    n, chunk = 1_000_000, 65536 - 65536 // 255 - 16
-    data = helpers.corpus(n, first_block=9)
-    src = tmp_path / "in.bin"; src.write_bytes(data.tobytes())
-    r = subprocess.run([str(exe), REF_SO, str(src), str(n), str(tmp_path), str(chunk)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    check_block_stream(r.stdout, data, tmp_path, chunk)
+    data, rec = _artifact_run("block_stream", tmp_path)
+    check_block_stream(rec["stdout"], data, rec, RUNS["block_stream"]["chunk"])
 
 
 def _zstream(exe, lib, src, n, outdir, chunk, decode=None):

@@ -1,5 +1,5 @@
 import subprocess, time, os, sys
-R=os.environ.get("GRAFT_REPO_ROOT","/root/repo")
+R=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))   # the repository this tool sits in
 os.chdir("/dev/shm"); open("empty","wb").close(); open("one","wb").write(os.urandom(4<<20))
 def t(cmd):
     s=time.perf_counter(); subprocess.run(cmd, capture_output=True); return time.perf_counter()-s
