@@ -276,13 +276,23 @@ int fourmc_gpu_lz4_compress_fast(const void* d_src, void* d_dst, fourmc_block* d
     return lz4_fast_encode(d_src, d_dst, d_blocks, n, 0, static_cast<hipStream_t>(stream));
 }
 
+// LZ4 HC at any level, as LZ4_compress_HC takes it: <= 0 is the default 9 and above 12 is 12 (lz4hc.c:840-841); 1..8 run the
+// hash-chain kernel (lz4hc_encode.hip), 9..12 the one with pattern analysis, chain swap and the optimal parser (lz4hc_opt_encode.hip)
+static int lz4hc_encode(const void* d_src, void* d_dst, fourmc_block* d_blocks, uint32_t n, int level, int container_mode, hipStream_t s)
+{
+    if (level < 1) level = 9;
+    if (level > 12) level = 12;
+    if (level <= 8)
+        return in_pieces(s, n, 0, fourmc_lz4hc_work_bytes, [&](uint32_t b0, uint32_t m, void* work) -> int {
+            HIP_TRY(fourmc_launch_lz4hc_encode(d_src, d_dst, d_blocks + b0, m, work, level, container_mode, s)); return FOURMC_OK; });
+    return in_pieces(s, n, 0, fourmc_lz4hc_opt_work_bytes, [&](uint32_t b0, uint32_t m, void* work) -> int {
+        HIP_TRY(fourmc_launch_lz4hc_opt_encode(d_src, d_dst, d_blocks + b0, m, work, level, container_mode, s)); return FOURMC_OK; });
+}
+
 int fourmc_gpu_lz4_compress_hc(const void* d_src, void* d_dst, fourmc_block* d_blocks, uint32_t n, int level, void* stream)
 {
     if (int r = ensure_device()) return r;
-    if (level < 1 || level > 8) { snprintf(g_err, sizeof g_err, "LZ4 HC level %d not on the device (hash-chain levels 1..8 are)", level); return FOURMC_EUNSUP; }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    return in_pieces(s, n, 0, fourmc_lz4hc_work_bytes, [&](uint32_t b0, uint32_t m, void* work) -> int {
-        HIP_TRY(fourmc_launch_lz4hc_encode(d_src, d_dst, d_blocks + b0, m, work, level, 0, s)); return FOURMC_OK; });
+    return lz4hc_encode(d_src, d_dst, d_blocks, n, level, 0, static_cast<hipStream_t>(stream));
 }
 
 int fourmc_gpu_lz4_compress_mc(const void* d_src, void* d_dst, fourmc_block* d_blocks, uint32_t n, void* stream)
@@ -367,9 +377,7 @@ int fourmc_gpu_4mc_encode_blocks(const void* d_src, void* d_dst, fourmc_block* d
     if (int r = ensure_device()) return r;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (codec == FOURMC_CODEC_LZ4_HC) {
-        if (level < 1 || level > 8) { snprintf(g_err, sizeof g_err, "LZ4 HC level %d not on the device", level); return FOURMC_EUNSUP; }
-        if (int r = in_pieces(s, n, 0, fourmc_lz4hc_work_bytes, [&](uint32_t b0, uint32_t m, void* work) -> int {
-                HIP_TRY(fourmc_launch_lz4hc_encode(d_src, d_dst, d_blocks + b0, m, work, level, 1, s)); return FOURMC_OK; })) return r;
+        if (int r = lz4hc_encode(d_src, d_dst, d_blocks, n, level, 1, s)) return r;
         HIP_TRY(fourmc_launch_xxh32(d_dst, d_blocks, n, 0, FOURMC_HASH_DST_RESULT, s));
         return FOURMC_OK;
     }

@@ -64,6 +64,10 @@ hipError_t fourmc_launch_pack_image(const void* d_staging, void* d_image, const 
 size_t     fourmc_lz4hc_work_bytes(uint32_t n);
 hipError_t fourmc_launch_lz4hc_encode(const void* d_src, void* d_dst, fourmc_block* d_blocks, uint32_t n,
                                       void* d_work, int level, int container_mode, hipStream_t stream);
+/* LZ4 HC levels 9..12 (lz4hc_opt_encode.hip): one wavefront per block, the chain ring in LDS */
+size_t     fourmc_lz4hc_opt_work_bytes(uint32_t n);
+hipError_t fourmc_launch_lz4hc_opt_encode(const void* d_src, void* d_dst, fourmc_block* d_blocks, uint32_t n,
+                                          void* d_work, int level, int container_mode, hipStream_t stream);
 hipError_t fourmc_launch_lz4mc_encode(const void* d_src, void* d_dst, fourmc_block* d_blocks, uint32_t n,
                                       void* d_work, int container_mode, hipStream_t stream);
 #ifdef FOURMC_RESEARCH      /* the research side build exports these two: tools/zstd_timing.py and tools/k7x_prof.py size their read-backs with them */

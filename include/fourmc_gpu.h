@@ -32,14 +32,14 @@ enum {
     FOURMC_EHIP     = -2,   /* a HIP runtime call failed (fourmc_gpu_last_error() has the text) */
     FOURMC_EINVAL   = -3,
     FOURMC_ENOMEM   = -4,
-    FOURMC_EUNSUP   = -5    /* codec/level not implemented on the device yet                   */
+    FOURMC_EUNSUP   = -5    /* codec/level not implemented on the device (zstd outside 1..12)  */
 };
 
 /* Codec selectors: the (function, level) pairs 4mc can reach (native/4mc.c:243-253,:411-419). */
 enum {
     FOURMC_CODEC_LZ4_FAST = 0,   /* LZ4_compress_default            4mc -1  (Lz4Compressor)    */
     FOURMC_CODEC_LZ4_MC   = 1,   /* LZ4_compressMC                  4mc -2                     */
-    FOURMC_CODEC_LZ4_HC   = 2,   /* LZ4_compress_HC(level 4 / 8)    4mc -3 / -4                */
+    FOURMC_CODEC_LZ4_HC   = 2,   /* LZ4_compress_HC(any level)      4mc -3 / -4 = 4 / 8        */
     FOURMC_CODEC_ZSTD     = 3    /* ZSTD_compress(level 1..12)      4mz -1..-4 = 1/3/6/12      */
 };
 
@@ -68,8 +68,9 @@ int fourmc_gpu_lz4_decompress(const void* d_src, void* d_dst, fourmc_block* d_bl
  * (0 = does not fit dst_cap).  Payload bytes identical to the reference 64-bit LE build.      */
 int fourmc_gpu_lz4_compress_fast(const void* d_src, void* d_dst, fourmc_block* d_blocks,
                                  uint32_t n, void* stream);
-/* result = LZ4_compress_HC(src, dst, src_len, dst_cap, level), hash-chain levels 1..8 (4mc High = 4,
- * Ultra = 8); byte-identical payloads                            native/lz4/lz4hc.c:958-973       */
+/* result = LZ4_compress_HC(src, dst, src_len, dst_cap, level) for any int level, byte-identical payloads
+ * (native/lz4/lz4hc.c:958-973): level <= 0 is the default 9 and level > 12 is 12 (:840-841); 1..8 hash chain
+ * (4mc High = 4, Ultra = 8), 9 hash chain with pattern analysis, 10..12 the optimal parser.              */
 int fourmc_gpu_lz4_compress_hc(const void* d_src, void* d_dst, fourmc_block* d_blocks,
                                uint32_t n, int level, void* stream);
 /* result = LZ4_compressMC_limitedOutput(src, dst, src_len, dst_cap), or LZ4_compressMC (no limit)
