@@ -18,6 +18,15 @@ BLOCK_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("src_len", "<u4
 assert BLOCK_DTYPE.itemsize == 32
 
 
+# struct fourmc_image_status (include/fourmc_gpu.h)
+class ImageStatus(C.Structure):
+    _fields_ = [("decoded_bytes", C.c_uint64), ("total_bytes", C.c_uint64), ("fail_offset", C.c_uint64),
+                ("streams", C.c_uint32), ("blocks", C.c_uint32), ("exit_code", C.c_int32), ("reason", C.c_int32)]
+
+
+assert C.sizeof(ImageStatus) == 40
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -69,6 +78,11 @@ _GPU_API = {
     "fourmc_gpu_4mc_encode_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "fourmc_gpu_4mc_decode_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
     "fourmc_gpu_4mc_pack_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "fourmc_gpu_image_bound": (C.c_uint64, [C.c_uint64]),
+    "fourmc_gpu_image_compress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
+    "fourmc_gpu_image_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_image_reason_text": (C.c_char_p, [C.c_int]),
+    "fourmc_gpu_image_parse_stats": (None, [C.c_void_p, C.c_void_p]),
     "fourmc_LZ4_compressBound": (C.c_int, [C.c_int]),
     "fourmc_LZ4_compress_default": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "fourmc_LZ4_compressMC": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

@@ -15,6 +15,7 @@
 #include <string.h>
 #include "fourmc_gpu.h"
 #include "kernels.h"
+#include "codec_level.h"
 
 namespace {
 
@@ -76,10 +77,16 @@ std::mutex g_wsmu;
 std::map<hipStream_t, StreamWs*> g_ws;
 StreamWs* g_ws_last = nullptr;          // for fourmc_gpu_debug_read_workspace
 
+// The image calls (image.hip) keep their descriptors, offsets and staging slots in a second registry of the same kind: they hold
+// that lease while the codec launches they make lease the stream's workspace.
+std::map<hipStream_t, StreamWs*> g_img_ws;
+
 class WsLease {
     StreamWs* w_ = nullptr;
+    std::map<hipStream_t, StreamWs*>* reg_ = &g_ws;
 public:
     WsLease() {}
+    explicit WsLease(std::map<hipStream_t, StreamWs*>* reg) : reg_(reg) {}
     WsLease(const WsLease&) = delete;
     ~WsLease() { if (w_) w_->mu.unlock(); }
     int get(hipStream_t s, size_t need, void** out)
@@ -87,9 +94,10 @@ public:
         if (!w_) {
             {
                 std::lock_guard<std::mutex> lk(g_wsmu);
-                auto it = g_ws.find(s);
-                if (it == g_ws.end()) it = g_ws.emplace(s, new StreamWs()).first;
-                w_ = it->second; g_ws_last = w_;
+                auto it = reg_->find(s);
+                if (it == reg_->end()) it = reg_->emplace(s, new StreamWs()).first;
+                w_ = it->second;
+                if (reg_ == &g_ws) g_ws_last = w_;
             }
             w_->mu.lock();          // entries are never removed; the registry lock is not held while waiting here
         }
@@ -117,7 +125,7 @@ public:
 extern "C" int fourmc_gpu_release_workspaces(void)
 {
     std::vector<std::pair<hipStream_t, StreamWs*>> all;
-    { std::lock_guard<std::mutex> lk(g_wsmu); for (auto& kv : g_ws) all.push_back(kv); }
+    { std::lock_guard<std::mutex> lk(g_wsmu); for (auto& kv : g_ws) all.push_back(kv); for (auto& kv : g_img_ws) all.push_back(kv); }
     for (auto& kv : all) {
         std::lock_guard<std::mutex> lk(kv.second->mu);
         if (kv.second->p) {
@@ -430,6 +438,142 @@ int fourmc_gpu_4mc_pack_image(const void* d_staging, void* d_image, const fourmc
 {
     if (int r = ensure_device()) return r;
     HIP_TRY(fourmc_launch_pack_image(d_staging, d_image, d_blocks, d_image_off, n, static_cast<hipStream_t>(stream)));
+    return FOURMC_OK;
+}
+
+// ------------------------------------------------------------------------ whole file images (image.hip)
+uint64_t fourmc_gpu_image_bound(uint64_t src_bytes)
+{
+    const uint64_t n = (src_bytes + FOURMC_BLOCKSIZE - 1) / FOURMC_BLOCKSIZE;
+    return 12 + 12 * n + src_bytes + 12 + 20 + 4 * n;
+}
+
+static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+// Descriptors from the size, the container encode (codec + XXH32, fourmc_gpu_4mc_encode_blocks) into 4 MiB staging slots, the
+// scan into image offsets, the pack, the header / end mark / footer; one read-back of the image size.
+int fourmc_gpu_image_compress(const void* d_src, uint64_t src_bytes, void* d_image, uint64_t image_cap,
+                              uint64_t* image_bytes, uint32_t magic, int level, void* stream)
+{
+    if (int r = ensure_device()) return r;
+    if (magic != FOURMC_MAGIC_4MC && magic != FOURMC_MAGIC_4MZ) { snprintf(g_err, sizeof g_err, "magic 0x%08x is neither 4mc nor 4mz", magic); return FOURMC_EINVAL; }
+    if (!image_bytes || !d_image || (src_bytes && !d_src)) { snprintf(g_err, sizeof g_err, "image_compress: null pointer"); return FOURMC_EINVAL; }
+    const uint64_t n64 = (src_bytes + FOURMC_BLOCKSIZE - 1) / FOURMC_BLOCKSIZE;
+    if (n64 > 0x3FFFFFFFull) { snprintf(g_err, sizeof g_err, "image_compress: %llu blocks", (unsigned long long)n64); return FOURMC_EINVAL; }
+    const uint32_t n = uint32_t(n64);
+    if (image_cap < fourmc_gpu_image_bound(src_bytes)) {
+        snprintf(g_err, sizeof g_err, "image capacity %llu below the bound %llu", (unsigned long long)image_cap,
+                 (unsigned long long)fourmc_gpu_image_bound(src_bytes));
+        return FOURMC_EINVAL;
+    }
+    int codec_level = 0;
+    const int codec = fourmc_level_codec(magic, level, &codec_level);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t o_off = align256(sizeof(fourmc_image_enc_summary)), o_blk = o_off + align256((size_t(n) + 1) * 8);
+    const size_t o_stage = o_blk + align256(size_t(n) * sizeof(fourmc_block));
+    WsLease ws(&g_img_ws); void* w = nullptr;
+    if (int r = ws.get(s, o_stage + size_t(n) * FOURMC_BLOCKSIZE, &w)) return r;
+    char* base = static_cast<char*>(w);
+    auto* d_sum = reinterpret_cast<fourmc_image_enc_summary*>(base);
+    auto* d_off = reinterpret_cast<uint64_t*>(base + o_off);
+    auto* d_blk = reinterpret_cast<fourmc_block*>(base + o_blk);
+    void* d_stage = base + o_stage;
+    HIP_TRY(fourmc_launch_image_enc_desc(d_blk, src_bytes, n, s));
+    if (n) { if (int r = fourmc_gpu_4mc_encode_blocks(d_src, d_stage, d_blk, n, codec, codec_level, s)) return r; }
+    HIP_TRY(fourmc_launch_image_enc_frame(d_image, d_blk, d_off, n, magic, d_stage, d_sum, s));
+    fourmc_image_enc_summary h;
+    HIP_TRY(hipMemcpyAsync(&h, d_sum, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h.bad_blocks) { snprintf(g_err, sizeof g_err, "image_compress: %u blocks with an encoder result outside [1, src_len]", h.bad_blocks); return FOURMC_EINVAL; }
+    *image_bytes = h.image_bytes;
+    return FOURMC_OK;
+}
+
+const char* fourmc_gpu_image_reason_text(int reason)
+{
+    switch (reason) {                       // fourmc_file.c: decode_stream, the writer thread (wjob_main)
+        case FOURMC_IMG_OK:                    return "";
+        case FOURMC_IMG_MAGIC_UNREADABLE:      return "Unrecognized header : Magic Number unreadable";
+        case FOURMC_IMG_NOT_4MC:               return "Unrecognized header : not a 4mc file";
+        case FOURMC_IMG_HEADER_UNREADABLE:     return "Unreadable header";
+        case FOURMC_IMG_VERSION:               return "Wrong version number";
+        case FOURMC_IMG_HEADER_CHECKSUM:       return "Wrong header checksum";
+        case FOURMC_IMG_BLOCK_SIZE_UNREADABLE: return "Read error : cannot read next block size";
+        case FOURMC_IMG_CSIZE_BEYOND:          return "Read error: block size beyond 4MB limit";
+        case FOURMC_IMG_DATA_UNREADABLE:       return "Read error : cannot read data block";
+        case FOURMC_IMG_USIZE_BEYOND:          return "Read error: uncompressed block size beyond 4MB limit";
+        case FOURMC_IMG_BLOCK_CHECKSUM:        return "Error : invalid block checksum detected";
+        case FOURMC_IMG_CORRUPT:               return "Decoding Failed ! Corrupted input detected !";
+        case FOURMC_IMG_FOOTER_UNREADABLE:     return "Unreadable footer";
+        case FOURMC_IMG_FOOTER_SHORT:          return "Read error : cannot read footer";
+        case FOURMC_IMG_FOOTER_CHECKSUM:       return "Error : invalid footer checksum detected";
+        case FOURMC_IMG_FOOTER_VERSION:        return "Read error : unsupported footer version";
+        case FOURMC_IMG_DST_SMALL:             return "Destination buffer too small";
+        default:                               return "unknown";
+    }
+}
+
+// images parsed so far by the fast path and by the walk (fourmc_gpu_image_parse_stats)
+static std::atomic<unsigned long long> g_img_fast{0}, g_img_walk{0};
+void fourmc_gpu_image_parse_stats(unsigned long long* fast, unsigned long long* walk)
+{
+    if (fast) *fast = g_img_fast.load();
+    if (walk) *walk = g_img_walk.load();
+}
+
+// FOURMC_IMAGE_PARSE=walk: every image takes the file-order walk (test knob; the results are the same).  Read at every call, so
+// that one process can run an image under both parsers.
+static bool image_walk_forced()
+{
+    const char* e = getenv("FOURMC_IMAGE_PARSE");
+    return e && !strcmp(e, "walk");
+}
+
+// Parse (fast path, else the walk) into a summary read back once; descriptors for exactly that many blocks; the container decode
+// (XXH32 verify + codec, fourmc_gpu_4mc_decode_blocks); the reduction into the status, read back.
+int fourmc_gpu_image_decompress(const void* d_image, uint64_t image_bytes, void* d_dst, uint64_t dst_cap,
+                                uint32_t magic, fourmc_image_status* status, void* stream)
+{
+    if (int r = ensure_device()) return r;
+    if (magic != FOURMC_MAGIC_4MC && magic != FOURMC_MAGIC_4MZ) { snprintf(g_err, sizeof g_err, "magic 0x%08x is neither 4mc nor 4mz", magic); return FOURMC_EINVAL; }
+    if (!status || (image_bytes && !d_image)) { snprintf(g_err, sizeof g_err, "image_decompress: null pointer"); return FOURMC_EINVAL; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t o_st = align256(sizeof(fourmc_image_parse)), o_blk = o_st + align256(sizeof(fourmc_image_status));
+    WsLease ws(&g_img_ws); void* w = nullptr;
+    if (int r = ws.get(s, o_blk, &w)) return r;
+    auto* d_ps = static_cast<fourmc_image_parse*>(w);
+    HIP_TRY(hipMemsetAsync(d_ps, 0, sizeof(fourmc_image_parse), s));
+    const bool walk_only = image_walk_forced();
+    HIP_TRY(fourmc_launch_image_parse(d_image, image_bytes, magic, !walk_only, 1, d_ps, nullptr, s));
+    fourmc_image_parse ps;
+    HIP_TRY(hipMemcpyAsync(&ps, d_ps, sizeof ps, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    (ps.fast ? g_img_fast : g_img_walk)++;
+    memset(status, 0, sizeof *status);
+    status->total_bytes = ps.total; status->streams = ps.streams;
+    if (ps.nblocks > 0x7FFFFFFFull) { snprintf(g_err, sizeof g_err, "image_decompress: %llu blocks", (unsigned long long)ps.nblocks); return FOURMC_EUNSUP; }
+    const uint32_t n = uint32_t(ps.nblocks);
+    if (!d_dst) {                                                        // size query: the framing verdict
+        status->blocks = n; status->reason = ps.reason; status->exit_code = fourmc_image_exit_code(ps.reason); status->fail_offset = ps.fail_offset;
+        return FOURMC_OK;
+    }
+    if (ps.total > dst_cap) {
+        status->reason = FOURMC_IMG_DST_SMALL; status->exit_code = fourmc_image_exit_code(FOURMC_IMG_DST_SMALL); status->fail_offset = 0;
+        return FOURMC_OK;
+    }
+    if (int r = ws.get(s, o_blk + size_t(n) * sizeof(fourmc_block), &w)) return r;   // may move the buffer: the summary goes up again
+    char* base = static_cast<char*>(w);
+    d_ps = reinterpret_cast<fourmc_image_parse*>(base);
+    auto* d_st = reinterpret_cast<fourmc_image_status*>(base + o_st);
+    auto* d_blk = reinterpret_cast<fourmc_block*>(base + o_blk);
+    HIP_TRY(hipMemcpyAsync(d_ps, &ps, sizeof ps, hipMemcpyHostToDevice, s));
+    if (n) {
+        HIP_TRY(fourmc_launch_image_parse(d_image, image_bytes, magic, ps.fast, !ps.fast, d_ps, d_blk, s));
+        if (int r = fourmc_gpu_4mc_decode_blocks(d_image, d_dst, d_blk, n, magic == FOURMC_MAGIC_4MZ ? FOURMC_CODEC_ZSTD : FOURMC_CODEC_LZ4_FAST, s)) return r;
+    }
+    HIP_TRY(fourmc_launch_image_reduce(d_blk, n, d_ps, d_st, s));
+    HIP_TRY(hipMemcpyAsync(status, d_st, sizeof *status, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return FOURMC_OK;
 }
 

@@ -30,6 +30,7 @@
 #include <unistd.h>
 #include "fourmc.h"
 #include "fourmc_gpu.h"
+#include "codec_level.h"
 
 #define BLOCKSIZE FOURMC_BLOCKSIZE
 
@@ -367,14 +368,7 @@ static int compress_file(int displayLevel, int overwrite, char* in_name, char* o
     size_t got;
 
     if (displayLevel == 2 && level > 1) displayLevel = 3;            /* native/4mc.c:241       */
-    if (magic == FOURMC_MAGIC_4MC) {                                  /* native/4mc.c:243-253   */
-        if (level <= 1) codec = FOURMC_CODEC_LZ4_FAST;
-        else if (level == 2) codec = FOURMC_CODEC_LZ4_MC;
-        else { codec = FOURMC_CODEC_LZ4_HC; codec_level = (level == 3) ? 4 : 8; }
-    } else {                                                          /* native/4mc.c:411-419   */
-        codec = FOURMC_CODEC_ZSTD;
-        codec_level = level <= 1 ? 1 : level == 2 ? 3 : level == 3 ? 6 : 12;
-    }
+    codec = fourmc_level_codec(magic, level, &codec_level);          /* native/4mc.c:243-253, :411-419 */
     open_io(displayLevel, overwrite, in_name, out_name, &fin, &fout);
     {
         struct stat sin;

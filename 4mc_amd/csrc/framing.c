@@ -13,6 +13,7 @@
 #include <string.h>
 #include "fourmc.h"
 #include "fourmc_gpu.h"
+#include "codec_level.h"
 
 /* ---- XXH32 (host scalar).  Algorithm: native/lz4/xxhash.c:392-415; primes :263-267. -------- */
 static uint32_t rol(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
@@ -37,6 +38,20 @@ unsigned fourmc_XXH32(const void* input, size_t len, unsigned seed)
     for (; left; left--, p++) h = rol(h + *p * E, 11) * A;
     h ^= h >> 15; h *= B; h ^= h >> 13; h *= C; h ^= h >> 16;
     return h;
+}
+
+/* ---- level -> codec (native/4mc.c:243-253, :411-419) ------------------------------------------ */
+int fourmc_level_codec(uint32_t magic, int level, int* codec_level)
+{
+    *codec_level = 0;
+    if (magic == FOURMC_MAGIC_4MC) {
+        if (level <= 1) return FOURMC_CODEC_LZ4_FAST;
+        if (level == 2) return FOURMC_CODEC_LZ4_MC;
+        *codec_level = (level == 3) ? 4 : 8;
+        return FOURMC_CODEC_LZ4_HC;
+    }
+    *codec_level = level <= 1 ? 1 : level == 2 ? 3 : level == 3 ? 6 : 12;
+    return FOURMC_CODEC_ZSTD;
 }
 
 /* ---- big-endian fields ---------------------------------------------------------------------- */

@@ -70,6 +70,30 @@ hipError_t fourmc_launch_lz4hc_opt_encode(const void* d_src, void* d_dst, fourmc
                                           void* d_work, int level, int container_mode, hipStream_t stream);
 hipError_t fourmc_launch_lz4mc_encode(const void* d_src, void* d_dst, fourmc_block* d_blocks, uint32_t n,
                                       void* d_work, int container_mode, hipStream_t stream);
+/* whole file images (image.hip): what the parse leaves for the engine's one read-back, and what the encode's scan leaves */
+typedef struct fourmc_image_parse {
+    uint64_t nblocks;       /* well-formed blocks, in file order, before the parser stopped */
+    uint64_t total;         /* sum of their usize */
+    uint64_t fail_offset;   /* image offset of the framing error (image_bytes when there is none) */
+    uint32_t streams;       /* streams whose header passed */
+    int32_t  reason;        /* FOURMC_IMG_*: the framing verdict */
+    uint32_t fast;          /* 1: the fast path accepted the image (the walk has nothing to do) */
+    uint32_t pad;
+} fourmc_image_parse;
+typedef struct fourmc_image_enc_summary {
+    uint64_t image_bytes;
+    uint32_t bad_blocks;    /* encoder results outside [1, src_len] (never, for the container encode) */
+    uint32_t pad;
+} fourmc_image_enc_summary;
+hipError_t fourmc_launch_image_enc_desc(fourmc_block* d_blocks, uint64_t src_bytes, uint32_t n, hipStream_t s);
+hipError_t fourmc_launch_image_enc_frame(void* d_image, fourmc_block* d_blocks, uint64_t* d_off, uint32_t n, uint32_t magic,
+                                         const void* d_staging, fourmc_image_enc_summary* d_sum, hipStream_t s);
+/* fast: the footer-driven parser; walk: the file-order walk (count mode skips itself when the fast path accepted the image).
+ * d_blocks NULL: count into *d_ps; else fill the descriptors of the parse *d_ps holds. */
+hipError_t fourmc_launch_image_parse(const void* d_image, uint64_t image_bytes, uint32_t magic, int fast, int walk,
+                                     fourmc_image_parse* d_ps, fourmc_block* d_blocks, hipStream_t s);
+hipError_t fourmc_launch_image_reduce(const fourmc_block* d_blocks, uint32_t n, const fourmc_image_parse* d_ps,
+                                      fourmc_image_status* d_status, hipStream_t s);
 #ifdef FOURMC_RESEARCH      /* the research side build exports these two: tools/zstd_timing.py and tools/k7x_prof.py size their read-backs with them */
 #pragma GCC visibility push(default)
 #endif
@@ -91,6 +115,17 @@ hipError_t fourmc_launch_xxh32(const void* d_base, fourmc_block* d_blocks, uint3
 #ifdef __cplusplus
 }
 #endif
+
+// the CLI's exit code for each verdict of an image decode (fourmc_file.c: the DIE() of each message)
+static inline __host__ __device__ int32_t fourmc_image_exit_code(int32_t reason)
+{
+    switch (reason) {
+        case FOURMC_IMG_OK: return 0;
+        case FOURMC_IMG_BLOCK_SIZE_UNREADABLE: case FOURMC_IMG_DATA_UNREADABLE: case FOURMC_IMG_FOOTER_SHORT: return 2;
+        case FOURMC_IMG_FOOTER_UNREADABLE: case FOURMC_IMG_DST_SMALL: return 1;
+        default: return 4;
+    }
+}
 
 #ifdef __HIPCC__
 // A block descriptor arrives through a vector load.  Everything a wave-per-block kernel derives from it (lengths, limits, loop

@@ -3,10 +3,12 @@
 Mirrors the reference's per-block codec calls (LZ4_decompress_safe / LZ4_compress_default /
 XXH32, native/4mc.c:301,311,637,661) in their batched form (include/fourmc_gpu.h).
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
-from .binding import BLOCK_DTYPE, CODEC_LZ4_FAST, check, lib
+from .binding import BLOCK_DTYPE, CODEC_LZ4_FAST, MAGIC_4MC, EngineError, ImageStatus, check, lib
 
 
 def _stream_ptr(stream):
@@ -99,3 +101,45 @@ def pack_image(d_staging, d_image, batch, d_image_off, stream=None):
 def release_workspaces():
     """Frees the device workspaces the engine keeps per stream (fourmc_gpu_release_workspaces); the next call allocates again."""
     check(lib().fourmc_gpu_release_workspaces(), "fourmc_gpu_release_workspaces")
+
+
+def _dev_ptr(t, what):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == torch.uint8):
+        raise EngineError(f"{what}: a contiguous uint8 CUDA tensor is required")
+    return int(t.data_ptr()) if t.numel() else 0
+
+
+def image_bound(src_bytes):
+    """Worst-case image size for src_bytes of input (fourmc_gpu_image_bound)."""
+    return int(lib().fourmc_gpu_image_bound(int(src_bytes)))
+
+
+def compress_image(d_src, d_image, magic=MAGIC_4MC, level=1, stream=None):
+    """The whole .4mc / .4mz file of d_src into d_image (>= image_bound(d_src.numel()) bytes), as the CLI writes it at `level`.
+    Returns the image length."""
+    out = C.c_uint64(0)
+    check(lib().fourmc_gpu_image_compress(_dev_ptr(d_src, "compress_image d_src"), d_src.numel(), _dev_ptr(d_image, "compress_image d_image"),
+                                          d_image.numel(), C.byref(out), magic, level, _stream_ptr(stream)), "fourmc_gpu_image_compress")
+    return int(out.value)
+
+
+def image_parse_stats():
+    """(fast, walk): images decompress_image has parsed so far with the footer-driven fast path and with the file-order walk."""
+    f, w = C.c_ulonglong(0), C.c_ulonglong(0)
+    lib().fourmc_gpu_image_parse_stats(C.byref(f), C.byref(w))
+    return int(f.value), int(w.value)
+
+
+def decompress_image(d_image, d_dst, magic=MAGIC_4MC, image_bytes=None, stream=None):
+    """Decode the file image d_image[:image_bytes] (default: the whole tensor) into d_dst; d_dst None: parse only (size query).
+    Returns the status as a dict; "message" is the CLI's text for the verdict."""
+    n = d_image.numel() if image_bytes is None else int(image_bytes)
+    if n > d_image.numel():
+        raise EngineError("decompress_image: image_bytes beyond the tensor")
+    st = ImageStatus()
+    dst, cap = (0, 0) if d_dst is None else (_dev_ptr(d_dst, "decompress_image d_dst"), d_dst.numel())
+    check(lib().fourmc_gpu_image_decompress(_dev_ptr(d_image, "decompress_image d_image"), n, dst, cap, magic, C.byref(st),
+                                            _stream_ptr(stream)), "fourmc_gpu_image_decompress")
+    res = {name: int(getattr(st, name)) for name, _ in ImageStatus._fields_}
+    res["message"] = lib().fourmc_gpu_image_reason_text(st.reason).decode()
+    return res

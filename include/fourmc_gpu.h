@@ -139,6 +139,63 @@ int fourmc_gpu_4mc_decode_blocks(const void* d_src, void* d_dst, fourmc_block* d
 int fourmc_gpu_4mc_pack_image(const void* d_staging, void* d_image, const fourmc_block* d_blocks,
                               const uint64_t* d_image_off, uint32_t n, void* stream);
 
+/* ---- whole file images in device memory ------------------------------------------------------------------------------------
+ * "device image in -> device bytes out", with the result the CLI gives for the same bytes as a file.  Both calls synchronize
+ * `stream`: the encode once (the image size), the decode twice (the block count its workspace is sized by, then the status).
+ * No per-block data crosses to the host. */
+/* worst-case image size for src_bytes of input: header + 12 per block + src_bytes + end mark + footer */
+uint64_t fourmc_gpu_image_bound(uint64_t src_bytes);
+/* d_src[0, src_bytes) -> a complete .4mc (magic FOURMC_MAGIC_4MC) or .4mz (FOURMC_MAGIC_4MZ) file image at d_image, byte-identical
+ * to what fourMCcompressFilename / fourMZcompressFilename(level) write for the same input (level as the file API and the CLI:
+ * 4mc 1 fast, 2 medium, 3 high, >= 4 ultra; 4mz zstd 1 / 3 / 6 / 12).  image_cap must be >= fourmc_gpu_image_bound(src_bytes);
+ * *image_bytes (host) = the image's length. */
+int fourmc_gpu_image_compress(const void* d_src, uint64_t src_bytes, void* d_image, uint64_t image_cap,
+                              uint64_t* image_bytes, uint32_t magic, int level, void* stream);
+
+/* the verdict of an image decode: which of the CLI's messages (fourmc_file.c: decode_stream) it ends with */
+enum {
+    FOURMC_IMG_OK                    = 0,
+    FOURMC_IMG_MAGIC_UNREADABLE      = 1,   /* exit 4 */
+    FOURMC_IMG_NOT_4MC               = 2,   /* exit 4 */
+    FOURMC_IMG_HEADER_UNREADABLE     = 3,   /* exit 4 */
+    FOURMC_IMG_VERSION               = 4,   /* exit 4 */
+    FOURMC_IMG_HEADER_CHECKSUM       = 5,   /* exit 4 */
+    FOURMC_IMG_BLOCK_SIZE_UNREADABLE = 6,   /* exit 2 */
+    FOURMC_IMG_CSIZE_BEYOND          = 7,   /* exit 4 */
+    FOURMC_IMG_DATA_UNREADABLE       = 8,   /* exit 2 */
+    FOURMC_IMG_USIZE_BEYOND          = 9,   /* exit 4 */
+    FOURMC_IMG_BLOCK_CHECKSUM        = 10,  /* exit 4 */
+    FOURMC_IMG_CORRUPT               = 11,  /* exit 4 */
+    FOURMC_IMG_FOOTER_UNREADABLE     = 12,  /* exit 1 */
+    FOURMC_IMG_FOOTER_SHORT          = 13,  /* exit 2 */
+    FOURMC_IMG_FOOTER_CHECKSUM       = 14,  /* exit 4 */
+    FOURMC_IMG_FOOTER_VERSION        = 15,  /* exit 4 */
+    FOURMC_IMG_DST_SMALL             = 16   /* exit 1: total_bytes > dst_cap, nothing decoded (the CLI has no such case) */
+};
+typedef struct fourmc_image_status {
+    uint64_t decoded_bytes;   /* bytes at d_dst the CLI would have written before it stopped: the sum of the decoded sizes.
+                               * Exception: a crafted block that decodes to fewer bytes than its usize is no error to the CLI,
+                               * which writes what it decoded and closes the gap; here block i still sits at the usize prefix,
+                               * so d_dst[:decoded_bytes] is then not the CLI's output although the verdict is OK           */
+    uint64_t total_bytes;     /* sum of usize of every well-formed block before the framing verdict (the size query's answer)  */
+    uint64_t fail_offset;     /* image offset of the header / block header / footer that ended decoding; image_bytes if none   */
+    uint32_t streams, blocks; /* streams whose header passed; blocks decoded (parse only: well-formed blocks)                    */
+    int32_t  exit_code;       /* 0, or the CLI's exit code for this image (1, 2, 4)                                            */
+    int32_t  reason;          /* FOURMC_IMG_*                                                                                  */
+} fourmc_image_status;
+/* d_image[0, image_bytes) -> decoded bytes at d_dst: block i at the sum of the usizes of the blocks before it, across streams.
+ * d_dst NULL: parse only (total_bytes, blocks and the framing verdict; no payload is checked).  As the CLI's loop over
+ * concatenated streams, decoding ends cleanly after a stream whose blocks add up to 0 bytes, whatever follows it.  Bytes past decoded_bytes are
+ * unspecified.  total_bytes > dst_cap: FOURMC_IMG_DST_SMALL, nothing written.  The decoders may read up to 64 bytes past a
+ * payload, as with fourmc_gpu_4mc_decode_blocks.  env FOURMC_IMAGE_PARSE=walk forces the file-order walk (test knob). */
+int fourmc_gpu_image_decompress(const void* d_image, uint64_t image_bytes, void* d_dst, uint64_t dst_cap,
+                                uint32_t magic, fourmc_image_status* status, void* stream);
+/* the exact text fourmc_file.c prints for a FOURMC_IMG_* verdict ("" for FOURMC_IMG_OK) */
+const char* fourmc_gpu_image_reason_text(int reason);
+/* Statistics (read-only): images fourmc_gpu_image_decompress has parsed so far with the footer-driven fast path and with the
+ * file-order walk (everything the fast path does not prove: concatenations, damage, FOURMC_IMAGE_PARSE=walk). */
+void fourmc_gpu_image_parse_stats(unsigned long long* fast, unsigned long long* walk);
+
 /* ---- host-buffer conveniences with the reference's per-block signatures ------------------- */
 /* These stage one block through HBM (H2D, one launch, D2H).  They exist so the JNI entry points
  * keep their exact one-call-one-block contract (SURVEY.md §8(b) "Batching constraint").        */
