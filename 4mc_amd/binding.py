@@ -27,6 +27,27 @@ class ImageStatus(C.Structure):
 assert C.sizeof(ImageStatus) == 40
 
 
+# struct fourmc_image_entry / fourmc_image_index_info / fourmc_image_range (include/fourmc_gpu.h: random access)
+class ImageEntry(C.Structure):
+    _fields_ = [("image_off", C.c_uint64), ("data_off", C.c_uint64), ("usize", C.c_uint32), ("csize", C.c_uint32),
+                ("xxh32", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class ImageIndexInfo(C.Structure):
+    _fields_ = [("nblocks", C.c_int64), ("framing", C.c_int64), ("total_bytes", C.c_uint64), ("is_zstd", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class ImageRange(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint64), ("dst_off", C.c_uint64), ("result", C.c_int64)]
+
+
+IMAGE_ENTRY_DTYPE = np.dtype([("image_off", "<u8"), ("data_off", "<u8"), ("usize", "<u4"), ("csize", "<u4"),
+                              ("xxh32", "<u4"), ("pad", "<u4")])
+assert C.sizeof(ImageEntry) == 32 and C.sizeof(ImageRange) == 32 and C.sizeof(ImageIndexInfo) == 32
+assert IMAGE_ENTRY_DTYPE.itemsize == 32
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -83,6 +104,9 @@ _GPU_API = {
     "fourmc_gpu_image_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_reason_text": (C.c_char_p, [C.c_int]),
     "fourmc_gpu_image_parse_stats": (None, [C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_image_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_image_decode_blocks": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_image_read": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
     "fourmc_LZ4_compressBound": (C.c_int, [C.c_int]),
     "fourmc_LZ4_compress_default": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "fourmc_LZ4_compressMC": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

@@ -80,6 +80,9 @@ StreamWs* g_ws_last = nullptr;          // for fourmc_gpu_debug_read_workspace
 // The image calls (image.hip) keep their descriptors, offsets and staging slots in a second registry of the same kind: they hold
 // that lease while the codec launches they make lease the stream's workspace.
 std::map<hipStream_t, StreamWs*> g_img_ws;
+// image_read's descriptors and staging slots: a third registry, so that sizing them after the plan's read-back cannot move the
+// index and the plan that the second one holds
+std::map<hipStream_t, StreamWs*> g_img_stage;
 
 class WsLease {
     StreamWs* w_ = nullptr;
@@ -125,7 +128,8 @@ public:
 extern "C" int fourmc_gpu_release_workspaces(void)
 {
     std::vector<std::pair<hipStream_t, StreamWs*>> all;
-    { std::lock_guard<std::mutex> lk(g_wsmu); for (auto& kv : g_ws) all.push_back(kv); for (auto& kv : g_img_ws) all.push_back(kv); }
+    { std::lock_guard<std::mutex> lk(g_wsmu); for (auto& kv : g_ws) all.push_back(kv); for (auto& kv : g_img_ws) all.push_back(kv);
+      for (auto& kv : g_img_stage) all.push_back(kv); }
     for (auto& kv : all) {
         std::lock_guard<std::mutex> lk(kv.second->mu);
         if (kv.second->p) {
@@ -574,6 +578,157 @@ int fourmc_gpu_image_decompress(const void* d_image, uint64_t image_bytes, void*
     HIP_TRY(fourmc_launch_image_reduce(d_blk, n, d_ps, d_st, s));
     HIP_TRY(hipMemcpyAsync(status, d_st, sizeof *status, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return FOURMC_OK;
+}
+
+// ------------------------------------------------------------------------ random access into images (image.hip)
+// Workspace of the three calls (g_img_ws): the index summary, then - sized after its read-back - the entries and what the call
+// needs besides.  A buffer that grows loses its contents: everything after the first read-back is recomputed on the device.
+namespace {
+constexpr size_t kIdxBytes = 256;           // fourmc_image_index_dev
+int image_args(const void* d_image, uint64_t image_bytes, const char* who)
+{
+    if (image_bytes && !d_image) { snprintf(g_err, sizeof g_err, "%s: null image", who); return FOURMC_EINVAL; }
+    return FOURMC_OK;
+}
+// the summary, read back (the call's first synchronization)
+int image_index_count(WsLease& ws, hipStream_t s, const void* d_image, uint64_t image_bytes, fourmc_image_index_dev* out)
+{
+    void* w = nullptr;
+    if (int r = ws.get(s, kIdxBytes, &w)) return r;
+    auto* d_idx = static_cast<fourmc_image_index_dev*>(w);
+    HIP_TRY(fourmc_launch_image_index(d_image, image_bytes, d_idx, nullptr, 0, s));
+    HIP_TRY(hipMemcpyAsync(out, d_idx, sizeof *out, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return FOURMC_OK;
+}
+int image_codec(const fourmc_image_index_dev& idx) { return idx.info.is_zstd ? FOURMC_CODEC_ZSTD : FOURMC_CODEC_LZ4_FAST; }
+} // namespace
+
+// One wave reads the footer and every block header; one read-back.
+int fourmc_gpu_image_index(const void* d_image, uint64_t image_bytes, fourmc_image_entry* d_entries, uint64_t entries_cap,
+                           fourmc_image_index_info* info, void* stream)
+{
+    if (!info) { snprintf(g_err, sizeof g_err, "image_index: null info"); return FOURMC_EINVAL; }
+    if (int r = image_args(d_image, image_bytes, "image_index")) return r;
+    if (int r = ensure_device()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    WsLease ws(&g_img_ws); void* w = nullptr;
+    if (int r = ws.get(s, kIdxBytes, &w)) return r;
+    auto* d_idx = static_cast<fourmc_image_index_dev*>(w);
+    HIP_TRY(fourmc_launch_image_index(d_image, image_bytes, d_idx, d_entries, d_entries ? entries_cap : 0, s));
+    fourmc_image_index_dev h;
+    HIP_TRY(hipMemcpyAsync(&h, d_idx, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *info = h.info;
+    return FOURMC_OK;
+}
+
+// The summary (first read-back) gives n; the entries, the range's checks and descriptors, ONE container decode straight into d_dst,
+// the reduction; the result (second read-back).
+int fourmc_gpu_image_decode_blocks(const void* d_image, uint64_t image_bytes, uint32_t first, uint32_t count,
+                                   void* d_dst, uint64_t dst_cap, int64_t* result, void* stream)
+{
+    if (!result) { snprintf(g_err, sizeof g_err, "image_decode_blocks: null result"); return FOURMC_EINVAL; }
+    if (int r = image_args(d_image, image_bytes, "image_decode_blocks")) return r;
+    if (int r = ensure_device()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    WsLease ws(&g_img_ws);
+    fourmc_image_index_dev idx;
+    if (int r = image_index_count(ws, s, d_image, image_bytes, &idx)) return r;
+    const int64_t n = idx.info.nblocks;
+    if (n < 0) { *result = n; return FOURMC_OK; }                          // fourmc_file_decode_blocks' order
+    if (uint64_t(first) + count > uint64_t(n)) { *result = -3; return FOURMC_OK; }
+    if (count == 0) { *result = 0; return FOURMC_OK; }
+    const size_t o_span = kIdxBytes, o_res = o_span + 256, o_ent = o_res + 256;
+    const size_t o_desc = o_ent + align256(size_t(n) * sizeof(fourmc_image_entry));
+    void* w = nullptr;
+    if (int r = ws.get(s, o_desc + size_t(count) * sizeof(fourmc_block), &w)) return r;
+    char* base = static_cast<char*>(w);
+    auto* d_idx = reinterpret_cast<fourmc_image_index_dev*>(base);
+    auto* d_span = reinterpret_cast<fourmc_image_span*>(base + o_span);
+    auto* d_res = reinterpret_cast<int64_t*>(base + o_res);
+    auto* d_ent = reinterpret_cast<fourmc_image_entry*>(base + o_ent);
+    auto* d_desc = reinterpret_cast<fourmc_block*>(base + o_desc);
+    HIP_TRY(fourmc_launch_image_index(d_image, image_bytes, d_idx, d_ent, uint64_t(n), s));
+    HIP_TRY(fourmc_launch_image_span(d_ent, d_idx, image_bytes, first, count, dst_cap, d_span, d_desc, s));
+    if (int r = fourmc_gpu_4mc_decode_blocks(d_image, d_dst, d_desc, count, image_codec(idx), s)) return r;
+    HIP_TRY(fourmc_launch_image_span_reduce(d_desc, count, d_span, d_res, s));
+    HIP_TRY(hipMemcpyAsync(result, d_res, sizeof *result, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return FOURMC_OK;
+}
+
+// Three read-backs: the summary (n, framing, total), the plan's counts (direct descriptors, staging slots, longest piece), the
+// results.  Between the last two: descriptors, ONE container decode over direct and staged blocks together (relative to the lower
+// of d_dst and the staging, so that every offset is positive), the copies out of staging, the per-range reduction.
+int fourmc_gpu_image_read(const void* d_image, uint64_t image_bytes, fourmc_image_range* ranges, uint32_t nranges,
+                          void* d_dst, uint64_t dst_cap, void* stream)
+{
+    if (nranges && !ranges) { snprintf(g_err, sizeof g_err, "image_read: null ranges"); return FOURMC_EINVAL; }
+    if (int r = image_args(d_image, image_bytes, "image_read")) return r;
+    if (nranges > (1u << 30)) { snprintf(g_err, sizeof g_err, "image_read: %u ranges", nranges); return FOURMC_EINVAL; }
+    {   // destinations may not overlap (empty ranges have none)
+        std::vector<std::pair<uint64_t, uint64_t>> d;
+        d.reserve(nranges);
+        for (uint32_t i = 0; i < nranges; i++)
+            if (ranges[i].length) d.emplace_back(ranges[i].dst_off, ranges[i].dst_off + std::min(ranges[i].length, ~uint64_t(0) - ranges[i].dst_off));
+        std::sort(d.begin(), d.end());
+        for (size_t i = 1; i < d.size(); i++)
+            if (d[i].first < d[i - 1].second) {
+                snprintf(g_err, sizeof g_err, "image_read: destinations overlap at %llu", (unsigned long long)d[i].first);
+                return FOURMC_EINVAL;
+            }
+        if (!d.empty() && !d_dst) { snprintf(g_err, sizeof g_err, "image_read: null destination"); return FOURMC_EINVAL; }
+    }
+    if (int r = ensure_device()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    WsLease ws(&g_img_ws);
+    fourmc_image_index_dev idx;
+    if (int r = image_index_count(ws, s, d_image, image_bytes, &idx)) return r;
+    const int64_t code = idx.info.nblocks < 0 ? idx.info.nblocks : idx.info.framing;
+    if (code != 0) { for (uint32_t i = 0; i < nranges; i++) ranges[i].result = code; return FOURMC_OK; }
+    if (!nranges) return FOURMC_OK;
+    const uint32_t n = uint32_t(idx.info.nblocks);
+    const size_t o_plan = kIdxBytes, o_ent = o_plan + 256;
+    const size_t o_rng = o_ent + align256(size_t(n) * sizeof(fourmc_image_entry));
+    const size_t o_rp = o_rng + align256(size_t(nranges) * sizeof(fourmc_image_range));
+    const size_t o_flag = o_rp + align256(size_t(nranges) * sizeof(fourmc_image_rplan));
+    void* w = nullptr;
+    if (int r = ws.get(s, o_flag + size_t(n) * 4 + 4, &w)) return r;
+    char* base = static_cast<char*>(w);
+    auto* d_idx = reinterpret_cast<fourmc_image_index_dev*>(base);
+    auto* d_plan = reinterpret_cast<fourmc_image_plan*>(base + o_plan);
+    auto* d_ent = reinterpret_cast<fourmc_image_entry*>(base + o_ent);
+    auto* d_rng = reinterpret_cast<fourmc_image_range*>(base + o_rng);
+    auto* d_rp = reinterpret_cast<fourmc_image_rplan*>(base + o_rp);
+    auto* d_flag = reinterpret_cast<uint32_t*>(base + o_flag);
+    HIP_TRY(hipMemsetAsync(d_plan, 0, sizeof(fourmc_image_plan), s));
+    HIP_TRY(hipMemsetAsync(d_flag, 0, size_t(n) * 4 + 4, s));
+    HIP_TRY(hipMemcpyAsync(d_rng, ranges, size_t(nranges) * sizeof(fourmc_image_range), hipMemcpyHostToDevice, s));
+    HIP_TRY(fourmc_launch_image_index(d_image, image_bytes, d_idx, d_ent, n, s));
+    HIP_TRY(fourmc_launch_image_plan(d_ent, n, d_idx, d_rng, nranges, dst_cap, d_rp, d_flag, d_plan, s));
+    fourmc_image_plan plan;
+    HIP_TRY(hipMemcpyAsync(&plan, d_plan, sizeof plan, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint64_t ndesc = plan.ndirect + plan.nstaged;
+    if (ndesc > 0x7FFFFFFFull) { snprintf(g_err, sizeof g_err, "image_read: %llu blocks to decode", (unsigned long long)ndesc); return FOURMC_EUNSUP; }
+    WsLease ws2(&g_img_stage); void* w2 = nullptr;
+    const size_t o_stage = align256(size_t(ndesc) * sizeof(fourmc_block));
+    if (int r = ws2.get(s, o_stage + size_t(plan.nstaged) * FOURMC_BLOCKSIZE, &w2)) return r;
+    auto* d_desc = static_cast<fourmc_block*>(w2);
+    char* d_stage = static_cast<char*>(w2) + o_stage;
+    if (ndesc) {
+        const uintptr_t pd = reinterpret_cast<uintptr_t>(d_dst), ps = reinterpret_cast<uintptr_t>(d_stage), lo = std::min(pd, ps);
+        HIP_TRY(fourmc_launch_image_read_desc(d_ent, n, d_rng, nranges, d_rp, d_flag, plan.nstaged, plan.ndirect, pd - lo, ps - lo, d_desc, s));
+        if (int r = fourmc_gpu_4mc_decode_blocks(d_image, reinterpret_cast<void*>(lo), d_desc, uint32_t(ndesc), image_codec(idx), s)) return r;
+        HIP_TRY(fourmc_launch_image_read_copy(d_ent, d_rng, nranges, d_rp, d_flag, d_stage, d_dst, plan.max_piece, s));
+        HIP_TRY(fourmc_launch_image_read_reduce(d_ent, d_rng, nranges, d_rp, d_flag, d_desc, plan.ndirect, s));
+    }
+    std::vector<fourmc_image_range> back(nranges);
+    HIP_TRY(hipMemcpyAsync(back.data(), d_rng, size_t(nranges) * sizeof(fourmc_image_range), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint32_t i = 0; i < nranges; i++) ranges[i].result = back[i].result;
     return FOURMC_OK;
 }
 

@@ -11,10 +11,13 @@
 // The walk is decode_stream's loop on one lane, in file order, for everything else (a damaged or lying footer, a truncated
 // image, trailing bytes, a concatenation of streams).  Both write the same summary and, after the engine has allocated for the
 // count it read back, the same descriptors.  Header fields are big-endian u32 at any byte offset.
+// Random access (second half): the footer index of a single stream, block-range decodes and byte-range reads, each with the
+// verdict fourmc_file_decode_blocks (fourmc_file.c) reaches on the same bytes as a file.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fourmc_gpu.h"
 #include "kernels.h"
+#include "devcopy.h"
 
 namespace {
 
@@ -289,6 +292,320 @@ void image_reduce_kernel(const fourmc_block* __restrict__ blocks, uint32_t n, co
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------- random access
+// The footer index and the block-range / byte-range reads.  Every check is fourmc_file.c's read_index and the per-block loop of
+// fourmc_file_decode_blocks, in their order; the offsets are its 64-bit prefix sums of the footer's deltas.
+constexpr uint32_t kSlot = FOURMC_BLOCKSIZE;            // staging slot per partly covered block
+
+// 64-bit inclusive prefix of u32 values: their two 16-bit halves through scan_add (64 x 0xffff cannot overflow a lane)
+__device__ __forceinline__ uint64_t scan_add64(uint32_t v)
+{ return uint64_t(scan_add(v & 0xffffu)) + (uint64_t(scan_add(v >> 16)) << 16); }
+__device__ __forceinline__ uint64_t lane_u64(uint64_t v, int l)
+{
+    return (uint64_t(uint32_t(__builtin_amdgcn_readlane(int(uint32_t(v >> 32)), l))) << 32) |
+           uint32_t(__builtin_amdgcn_readlane(int(uint32_t(v)), l));
+}
+__device__ __forceinline__ uint64_t up_u64(uint64_t v)  // lane l gets lane l-1's value (lane 0 its own)
+{ return uint64_t(__shfl_up((unsigned long long)v, 1)); }
+
+// read_index on every lane (the same addresses: one request): n, or -1 / -2; *F: the footer's offset, *fsz: the tail's size field
+__device__ int64_t index_header(const uint8_t* img, uint64_t N, uint32_t* magic, uint64_t* F, uint64_t* fsz)
+{
+    if (N < 12) return -1;
+    const uint32_t m = be32(img);
+    if (m != FOURMC_MAGIC_4MC && m != FOURMC_MAGIC_4MZ) return -2;
+    if (be32(img + 4) != 1 || be32(img + 8) != xxh32_lane(img, 8, 0)) return -2;
+    const uint64_t fs = be32(img + N - 12);
+    if (fs < 20 || fs + 24 > N) return -2;
+    const uint8_t* foot = img + N - fs;                  // fourmc_frame_parse_footer(foot, fs): its size field may be below fs
+    const uint32_t size = be32(foot);
+    if (size < 20 || size > fs || ((size - 20) & 3)) return -2;
+    if (be32(foot + size - 4) != xxh32_lane(foot, size - 4, 0)) return -2;
+    if (be32(foot + 4) != 1) return -2;
+    if (be32(foot + size - 12) != size || be32(foot + size - 8) != m) return -2;
+    *magic = m; *F = N - fs; *fsz = fs;
+    return (size - 20) / 4;
+}
+
+// The index, one wave, 64 blocks per step: offsets and data offsets by scan, each block's header where the footer puts it, and the
+// verdict of fourmc_file_decode_blocks(0, n) with unlimited capacity - the first block, in order, that fails a check.
+__global__ __launch_bounds__(64)
+void image_index_kernel(const uint8_t* __restrict__ img, uint64_t N, fourmc_image_index_dev* __restrict__ idx,
+                        fourmc_image_entry* __restrict__ ent, uint64_t cap)
+{
+    const int lane = threadIdx.x;
+    uint32_t magic = 0;
+    uint64_t F = 0, fsz = 0;
+    const int64_t n = index_header(img, N, &magic, &F, &fsz);
+    if (n < 0) {
+        if (lane == 0) { idx->info.nblocks = n; idx->info.framing = n; idx->info.total_bytes = 0; idx->info.is_zstd = 0; idx->info.pad = 0; idx->data_end = 0; }
+        return;
+    }
+    const uint32_t k = uint32_t(n);
+    const uint64_t end = N - fsz - 12;                   // the end of the last block: where the end mark starts
+    int64_t framing = 0;
+    if (k && !(uint64_t(be32(img + F + 8)) < end)) framing = -1;          // lo < hi, else nothing is read
+    uint64_t carry = 0, ucarry = 0, prev_off = 0;
+    uint32_t prev_csize = 0, prev_read = 0;
+    for (uint32_t i0 = 0; i0 < k; i0 += 64) {
+        const uint32_t i = i0 + uint32_t(lane);
+        const bool have = i < k;
+        const uint32_t delta = have ? be32(img + F + 8 + 4ull * i) : 0u;
+        const uint64_t incl = scan_add64(delta);
+        const uint64_t off = carry + incl;
+        const bool readable = have && off + 12 <= N;
+        uint32_t usize = 0, csize = 0, sum = 0;
+        if (readable) { usize = be32(img + off); csize = be32(img + off + 4); sum = be32(img + off + 8); }
+        uint64_t poff = up_u64(off);
+        uint32_t pcs = uint32_t(__shfl_up(int(csize), 1)), prd = uint32_t(__shfl_up(int(readable), 1));
+        if (lane == 0) { poff = prev_off; pcs = prev_csize; prd = prev_read; }
+        const bool chain = i == 0 || (prd && off == poff + 12 + pcs);   // the index and the block headers agree
+        int32_t code = 0;
+        if (!chain || off + 12 > end) code = -2;
+        else if (csize > kBlock || usize > kBlock || off + 12 + csize > end) code = -4;
+        const uint64_t uincl = scan_add64(usize);
+        if (ent && have && i < cap) {
+            fourmc_image_entry e;
+            e.image_off = off; e.data_off = ucarry + uincl - usize; e.usize = usize; e.csize = csize; e.xxh32 = sum; e.pad = 0;
+            ent[i] = e;
+        }
+        const unsigned long long bad = __ballot(have && code != 0);
+        if (bad && framing == 0) framing = __shfl(code, int(__builtin_ctzll(bad)));
+        carry += lane_u64(incl, 63); ucarry += lane_u64(uincl, 63);
+        prev_off = lane_u64(off, 63);
+        prev_csize = uint32_t(__builtin_amdgcn_readlane(int(csize), 63));
+        prev_read = uint32_t(__builtin_amdgcn_readlane(int(readable), 63));
+    }
+    if (lane == 0) {
+        idx->info.nblocks = n; idx->info.framing = framing; idx->info.total_bytes = ucarry;
+        idx->info.is_zstd = magic == FOURMC_MAGIC_4MZ; idx->info.pad = 0;
+        idx->data_end = end;
+    }
+}
+
+// fourmc_file_decode_blocks(first, count, dst_cap) after read_index, one wave: lo / hi, then its loop's checks (-2 index and
+// headers disagree, -4 sizes, -5 capacity) per block, the first failure in order deciding.  Then the descriptors, block i at
+// data_off[i] - data_off[first]; all-zero descriptors (nothing read, nothing written) when a check failed.
+__global__ __launch_bounds__(64)
+void image_span_kernel(const fourmc_image_entry* __restrict__ ent, const fourmc_image_index_dev* __restrict__ idx, uint64_t N,
+                       uint32_t first, uint32_t count, uint64_t dst_cap, fourmc_image_span* __restrict__ span,
+                       fourmc_block* __restrict__ desc)
+{
+    const int lane = threadIdx.x;
+    const uint64_t n = uint64_t(idx->info.nblocks);
+    const uint64_t lo = ent[first].image_off;
+    const uint64_t hi = uint64_t(first) + count < n ? ent[first + count].image_off : idx->data_end;
+    const uint64_t d0 = ent[first].data_off;
+    int64_t code = (lo < hi && hi <= N) ? 0 : -1;
+    for (uint32_t b0 = 0; b0 < count && code == 0; b0 += 64) {
+        const uint32_t b = b0 + uint32_t(lane);
+        int32_t c = 0;
+        if (b < count) {
+            const fourmc_image_entry e = ent[first + b];
+            bool chain = true;
+            if (b) {
+                const fourmc_image_entry p = ent[first + b - 1];
+                chain = p.image_off + 12 <= N && e.image_off == p.image_off + 12 + p.csize;
+            }
+            if (!chain || e.image_off + 12 > hi) c = -2;
+            else if (e.csize > kBlock || e.usize > kBlock || e.image_off + 12 + e.csize > hi) c = -4;
+            else if (e.data_off - d0 + e.usize > dst_cap) c = -5;
+        }
+        const unsigned long long bad = __ballot(c != 0);
+        if (bad) code = __shfl(c, int(__builtin_ctzll(bad)));
+    }
+    for (uint32_t b0 = 0; b0 < count; b0 += 64) {
+        const uint32_t b = b0 + uint32_t(lane);
+        if (b >= count) break;
+        fourmc_block d = {};
+        if (code == 0) {
+            const fourmc_image_entry e = ent[first + b];
+            d.src_off = e.image_off + 12; d.dst_off = e.data_off - d0; d.src_len = e.csize; d.dst_cap = e.usize; d.xxh32 = e.xxh32;
+        }
+        desc[b] = d;
+    }
+    if (lane == 0) {
+        const uint64_t last = uint64_t(first) + count - 1;
+        span->framing = code;
+        span->out = code == 0 ? ent[last].data_off + ent[last].usize - d0 : 0;
+    }
+}
+
+// the file function's ending: its framing code, else -4 for any block whose result is not its usize, else the bytes
+__global__ __launch_bounds__(64)
+void image_span_reduce_kernel(const fourmc_block* __restrict__ desc, uint32_t count, const fourmc_image_span* __restrict__ span,
+                              int64_t* __restrict__ result)
+{
+    const int lane = threadIdx.x;
+    int64_t r = span->framing;
+    if (r == 0) {
+        bool bad = false;
+        for (uint32_t b = uint32_t(lane); b < count; b += 64) {
+            const fourmc_block d = desc[b];
+            bad |= d.result < 0 || uint32_t(d.result) != d.dst_cap;
+        }
+        r = __ballot(bad) ? -4 : int64_t(span->out);
+    }
+    if (lane == 0) *result = r;
+}
+
+// first block whose data ends beyond `pos` (data_off + usize is non-decreasing); n if none
+__device__ uint32_t block_after(const fourmc_image_entry* ent, uint32_t n, uint64_t pos)
+{
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (ent[mid].data_off + ent[mid].usize > pos) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+__device__ __forceinline__ bool partial(const fourmc_image_entry& e, uint64_t a, uint64_t z)
+{ return e.data_off < a || e.data_off + e.usize > z; }
+
+// One lane per range (the image's framing is 0 here): the early results, the covering blocks [b0, b1], how many of them lie wholly
+// inside (decoded straight into the destination), and a flag on each partly covered one (decoded once into staging).  Result
+// `length` marks a range still to be read.
+__global__ __launch_bounds__(256)
+void image_plan_kernel(const fourmc_image_entry* __restrict__ ent, uint32_t n, const fourmc_image_index_dev* __restrict__ idx,
+                       fourmc_image_range* __restrict__ ranges, uint32_t nranges, uint64_t dst_cap, fourmc_image_rplan* __restrict__ rp,
+                       uint32_t* __restrict__ flags, fourmc_image_plan* __restrict__ plan)
+{
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= nranges) return;
+    const fourmc_image_range q = ranges[r];
+    fourmc_image_rplan p = {};
+    const uint64_t total = idx->info.total_bytes;
+    int64_t res = int64_t(q.length);
+    if (q.length == 0) res = 0;
+    else if (q.offset > total || q.length > total - q.offset) res = -3;
+    else if (q.dst_off > dst_cap || q.length > dst_cap - q.dst_off) res = -5;
+    if (res > 0) {
+        const uint64_t a = q.offset, z = q.offset + q.length;
+        p.b0 = block_after(ent, n, a);
+        p.b1 = block_after(ent, n, z - 1);
+        const bool s0 = partial(ent[p.b0], a, z), s1 = p.b1 != p.b0 && partial(ent[p.b1], a, z);
+        p.nd = p.b1 - p.b0 + 1 - s0 - s1;
+        uint32_t piece = 0;
+        if (s0) { flags[p.b0] = 1; const fourmc_image_entry e = ent[p.b0]; piece = uint32_t(min(z, e.data_off + e.usize) - max(a, e.data_off)); }
+        if (s1) { flags[p.b1] = 1; const fourmc_image_entry e = ent[p.b1]; piece = max(piece, uint32_t(z - e.data_off)); }
+        if (piece) atomicMax(&plan->max_piece, piece);
+    }
+    ranges[r].result = res;
+    rp[r] = p;
+}
+
+// Two exclusive scans in one workgroup each: block 0 the direct counts of the ranges into their first descriptor, block 1 the staging
+// flags into slot numbers (in place).  Each thread sums a contiguous run; a wave scan plus the 16 wave totals in LDS order them.
+template <class Get, class Put>
+__device__ uint64_t block_scan(uint32_t m, Get get, Put put)
+{
+    __shared__ uint64_t wsum[16];
+    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const uint32_t per = uint32_t((uint64_t(m) + 1023) / 1024), a = min(m, t * per), z = uint32_t(min(uint64_t(m), uint64_t(a) + per));
+    uint64_t mine = 0;
+    for (uint32_t i = a; i < z; i++) mine += get(i);
+    uint64_t incl = mine;                                  // 64-bit wave scan: the counts of one thread may exceed 32 bits
+    for (int o = 1; o < 64; o <<= 1) { const uint64_t v = uint64_t(__shfl_up((unsigned long long)incl, o)); if (int(lane) >= o) incl += v; }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    uint64_t base = 0, total = 0;
+    for (uint32_t j = 0; j < 16; j++) { if (j < w) base += wsum[j]; total += wsum[j]; }
+    uint64_t run = base + incl - mine;
+    for (uint32_t i = a; i < z; i++) { const uint64_t v = get(i); put(i, run); run += v; }
+    return total;
+}
+__global__ __launch_bounds__(1024)
+void image_plan_scan_kernel(fourmc_image_rplan* __restrict__ rp, uint32_t nranges, uint32_t* __restrict__ flags, uint32_t n,
+                            fourmc_image_plan* __restrict__ plan)
+{
+    if (blockIdx.x == 0) {
+        const uint64_t t = block_scan(nranges, [&](uint32_t i) { return uint64_t(rp[i].nd); }, [&](uint32_t i, uint64_t v) { rp[i].dbase = v; });
+        if (threadIdx.x == 0) plan->ndirect = t;
+    } else {
+        const uint64_t t = block_scan(n, [&](uint32_t i) { return uint64_t(flags[i]); }, [&](uint32_t i, uint64_t v) { flags[i] = uint32_t(v); });
+        if (threadIdx.x == 0) plan->nstaged = uint32_t(t);
+    }
+}
+
+// Descriptors.  Blocks [0, nranges): one wave per range writes its direct descriptors.  Blocks from nranges on: one lane per image
+// block writes the staged descriptor of each flagged block (the slots are the scanned flags: a block is flagged iff the next slot
+// number differs).
+__global__ __launch_bounds__(64)
+void image_read_desc_kernel(const fourmc_image_entry* __restrict__ ent, uint32_t n, const fourmc_image_range* __restrict__ ranges,
+                            uint32_t nranges, const fourmc_image_rplan* __restrict__ rp, const uint32_t* __restrict__ slot,
+                            uint32_t nstaged, uint64_t ndirect, uint64_t dst_delta, uint64_t stage_delta, fourmc_block* __restrict__ desc)
+{
+    const uint32_t lane = threadIdx.x;
+    if (blockIdx.x < nranges) {
+        const uint32_t r = blockIdx.x;
+        const fourmc_image_range q = ranges[r];
+        if (q.result <= 0) return;
+        const fourmc_image_rplan p = rp[r];
+        const uint64_t a = q.offset, z = q.offset + q.length;
+        const uint32_t s0 = partial(ent[p.b0], a, z) ? 1u : 0u;
+        for (uint32_t j = lane; j < p.nd; j += 64) {
+            const fourmc_image_entry e = ent[p.b0 + s0 + j];
+            fourmc_block d;
+            d.src_off = e.image_off + 12; d.dst_off = dst_delta + q.dst_off + (e.data_off - a);
+            d.src_len = e.csize; d.dst_cap = e.usize; d.result = 0; d.xxh32 = e.xxh32;
+            desc[p.dbase + j] = d;
+        }
+        return;
+    }
+    const uint32_t b = (blockIdx.x - nranges) * 64 + lane;
+    if (b >= n) return;
+    const uint32_t s = slot[b], next = b + 1 < n ? slot[b + 1] : nstaged;
+    if (next == s) return;
+    const fourmc_image_entry e = ent[b];
+    fourmc_block d;
+    d.src_off = e.image_off + 12; d.dst_off = stage_delta + uint64_t(s) * kSlot;
+    d.src_len = e.csize; d.dst_cap = e.usize; d.result = 0; d.xxh32 = e.xxh32;
+    desc[ndirect + s] = d;
+}
+
+// The covered bytes of each (range, staged block) piece from its slot to the destination: one wave per 64 KiB chunk of a piece;
+// blockIdx.x = 2 * range + (0: the first covering block, 1: the last), blockIdx.y = chunk.
+constexpr uint32_t kChunk = 64 * 1024;
+__global__ __launch_bounds__(64)
+void image_read_copy_kernel(const fourmc_image_entry* __restrict__ ent, const fourmc_image_range* __restrict__ ranges,
+                            const fourmc_image_rplan* __restrict__ rp, const uint32_t* __restrict__ slot,
+                            const uint8_t* __restrict__ stage, uint8_t* __restrict__ dst)
+{
+    const uint32_t r = blockIdx.x >> 1, which = blockIdx.x & 1;
+    const fourmc_image_range q = ranges[r];
+    if (q.result <= 0) return;
+    const fourmc_image_rplan p = rp[r];
+    const uint64_t a = q.offset, z = q.offset + q.length;
+    const uint32_t b = which ? p.b1 : p.b0;
+    if (which && p.b1 == p.b0) return;
+    const fourmc_image_entry e = ent[b];
+    if (!partial(e, a, z)) return;
+    const uint64_t from = max(a, e.data_off), to = min(z, e.data_off + e.usize);
+    const uint64_t c0 = from + uint64_t(blockIdx.y) * kChunk;
+    if (c0 >= to) return;
+    const int len = int(min(to - c0, uint64_t(kChunk)));
+    wave_copy(dst + q.dst_off + (c0 - a), stage + uint64_t(slot[b]) * kSlot + (c0 - e.data_off), len, int(threadIdx.x));
+}
+
+// Per range, one wave: -4 when any covering block's result is not its usize
+__global__ __launch_bounds__(64)
+void image_read_reduce_kernel(const fourmc_image_entry* __restrict__ ent, fourmc_image_range* __restrict__ ranges,
+                              const fourmc_image_rplan* __restrict__ rp, const uint32_t* __restrict__ slot,
+                              const fourmc_block* __restrict__ desc, uint64_t ndirect)
+{
+    const uint32_t r = blockIdx.x, lane = threadIdx.x;
+    const fourmc_image_range q = ranges[r];
+    if (q.result <= 0) return;
+    const fourmc_image_rplan p = rp[r];
+    const uint64_t a = q.offset, z = q.offset + q.length;
+    auto bad = [](const fourmc_block& d) { return d.result < 0 || uint32_t(d.result) != d.dst_cap; };
+    bool b = false;
+    for (uint32_t j = lane; j < p.nd; j += 64) b |= bad(desc[p.dbase + j]);
+    if (lane == 0 && partial(ent[p.b0], a, z)) b |= bad(desc[ndirect + slot[p.b0]]);
+    if (lane == 1 && p.b1 != p.b0 && partial(ent[p.b1], a, z)) b |= bad(desc[ndirect + slot[p.b1]]);
+    if (__ballot(b) && lane == 0) ranges[r].result = -4;
+}
+
 } // namespace
 
 extern "C" {
@@ -329,6 +646,71 @@ hipError_t fourmc_launch_image_reduce(const fourmc_block* d_blocks, uint32_t n, 
                                       fourmc_image_status* d_status, hipStream_t s)
 {
     hipLaunchKernelGGL(image_reduce_kernel, dim3(1), dim3(64), 0, s, d_blocks, n, d_ps, d_status);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_image_index(const void* d_image, uint64_t image_bytes, fourmc_image_index_dev* d_idx,
+                                     fourmc_image_entry* d_ent, uint64_t cap, hipStream_t s)
+{
+    hipLaunchKernelGGL(image_index_kernel, dim3(1), dim3(64), 0, s, static_cast<const uint8_t*>(d_image), image_bytes, d_idx, d_ent, cap);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_image_span(const fourmc_image_entry* d_ent, const fourmc_image_index_dev* d_idx, uint64_t image_bytes,
+                                    uint32_t first, uint32_t count, uint64_t dst_cap, fourmc_image_span* d_span,
+                                    fourmc_block* d_desc, hipStream_t s)
+{
+    hipLaunchKernelGGL(image_span_kernel, dim3(1), dim3(64), 0, s, d_ent, d_idx, image_bytes, first, count, dst_cap, d_span, d_desc);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_image_span_reduce(const fourmc_block* d_desc, uint32_t count, const fourmc_image_span* d_span,
+                                           int64_t* d_result, hipStream_t s)
+{
+    hipLaunchKernelGGL(image_span_reduce_kernel, dim3(1), dim3(64), 0, s, d_desc, count, d_span, d_result);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_image_plan(const fourmc_image_entry* d_ent, uint32_t n, const fourmc_image_index_dev* d_idx,
+                                    fourmc_image_range* d_ranges, uint32_t nranges, uint64_t dst_cap, fourmc_image_rplan* d_rp,
+                                    uint32_t* d_flags, fourmc_image_plan* d_plan, hipStream_t s)
+{
+    if (nranges) {
+        hipLaunchKernelGGL(image_plan_kernel, dim3((nranges + 255) / 256), dim3(256), 0, s, d_ent, n, d_idx, d_ranges, nranges,
+                           dst_cap, d_rp, d_flags, d_plan);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    hipLaunchKernelGGL(image_plan_scan_kernel, dim3(2), dim3(1024), 0, s, d_rp, nranges, d_flags, n, d_plan);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_image_read_desc(const fourmc_image_entry* d_ent, uint32_t n, const fourmc_image_range* d_ranges,
+                                         uint32_t nranges, const fourmc_image_rplan* d_rp, const uint32_t* d_slot, uint32_t nstaged,
+                                         uint64_t ndirect, uint64_t dst_delta, uint64_t stage_delta, fourmc_block* d_desc, hipStream_t s)
+{
+    const uint32_t grid = nranges + (nstaged ? (n + 63) / 64 : 0);
+    if (!grid) return hipSuccess;
+    hipLaunchKernelGGL(image_read_desc_kernel, dim3(grid), dim3(64), 0, s, d_ent, n, d_ranges, nranges, d_rp, d_slot, nstaged,
+                       ndirect, dst_delta, stage_delta, d_desc);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_image_read_copy(const fourmc_image_entry* d_ent, const fourmc_image_range* d_ranges, uint32_t nranges,
+                                         const fourmc_image_rplan* d_rp, const uint32_t* d_slot, const void* d_stage, void* d_dst,
+                                         uint32_t max_piece, hipStream_t s)
+{
+    if (!nranges || !max_piece) return hipSuccess;
+    hipLaunchKernelGGL(image_read_copy_kernel, dim3(2 * nranges, (max_piece + kChunk - 1) / kChunk), dim3(64), 0, s, d_ent, d_ranges,
+                       d_rp, d_slot, static_cast<const uint8_t*>(d_stage), static_cast<uint8_t*>(d_dst));
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_image_read_reduce(const fourmc_image_entry* d_ent, fourmc_image_range* d_ranges, uint32_t nranges,
+                                           const fourmc_image_rplan* d_rp, const uint32_t* d_slot, const fourmc_block* d_desc,
+                                           uint64_t ndirect, hipStream_t s)
+{
+    if (!nranges) return hipSuccess;
+    hipLaunchKernelGGL(image_read_reduce_kernel, dim3(nranges), dim3(64), 0, s, d_ent, d_ranges, d_rp, d_slot, d_desc, ndirect);
     return hipGetLastError();
 }
 

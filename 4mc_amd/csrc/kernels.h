@@ -94,6 +94,54 @@ hipError_t fourmc_launch_image_parse(const void* d_image, uint64_t image_bytes, 
                                      fourmc_image_parse* d_ps, fourmc_block* d_blocks, hipStream_t s);
 hipError_t fourmc_launch_image_reduce(const fourmc_block* d_blocks, uint32_t n, const fourmc_image_parse* d_ps,
                                       fourmc_image_status* d_status, hipStream_t s);
+/* random access (image.hip, second half): the index summary plus where the last block must end (read_index's data_end) */
+typedef struct fourmc_image_index_dev {
+    fourmc_image_index_info info;
+    uint64_t data_end;
+} fourmc_image_index_dev;
+/* what the read plan leaves for the engine's second read-back */
+typedef struct fourmc_image_plan {
+    uint64_t ndirect;       /* descriptors decoded straight into a range's destination */
+    uint32_t nstaged;       /* distinct partly covered blocks = staging slots */
+    uint32_t max_piece;     /* longest (range, staged block) piece in bytes */
+} fourmc_image_plan;
+/* per range: the blocks it covers, its direct descriptors, where they start */
+typedef struct fourmc_image_rplan {
+    uint32_t b0, b1;        /* first and last covering block */
+    uint32_t nd, pad;       /* direct descriptors */
+    uint64_t dbase;         /* index of its first direct descriptor */
+    uint64_t pad2;
+} fourmc_image_rplan;
+/* decode_blocks: the framing verdict of [first, first+count) and the bytes it holds */
+typedef struct fourmc_image_span {
+    int64_t  framing;
+    uint64_t out;
+} fourmc_image_span;
+/* d_ent NULL: the summary only; else min(n, cap) entries */
+hipError_t fourmc_launch_image_index(const void* d_image, uint64_t image_bytes, fourmc_image_index_dev* d_idx,
+                                     fourmc_image_entry* d_ent, uint64_t cap, hipStream_t s);
+/* decode_blocks: the range's framing checks into *d_span, then its `count` descriptors (all-zero ones if a check failed) */
+hipError_t fourmc_launch_image_span(const fourmc_image_entry* d_ent, const fourmc_image_index_dev* d_idx, uint64_t image_bytes,
+                                    uint32_t first, uint32_t count, uint64_t dst_cap, fourmc_image_span* d_span,
+                                    fourmc_block* d_desc, hipStream_t s);
+hipError_t fourmc_launch_image_span_reduce(const fourmc_block* d_desc, uint32_t count, const fourmc_image_span* d_span,
+                                           int64_t* d_result, hipStream_t s);
+/* image_read, before the second read-back: covering blocks, early results, direct counts, staging flags -> slots, totals.
+ * d_flags (n words) must be zero. */
+hipError_t fourmc_launch_image_plan(const fourmc_image_entry* d_ent, uint32_t n, const fourmc_image_index_dev* d_idx,
+                                    fourmc_image_range* d_ranges, uint32_t nranges, uint64_t dst_cap, fourmc_image_rplan* d_rp,
+                                    uint32_t* d_flags, fourmc_image_plan* d_plan, hipStream_t s);
+/* after it: the descriptors (direct ones at d_dst_delta + dst_off, staged ones at d_stage_delta + slot * 4 MiB, both relative to
+ * the decode's base), the decode, the copies out of staging, the per-range results */
+hipError_t fourmc_launch_image_read_desc(const fourmc_image_entry* d_ent, uint32_t n, const fourmc_image_range* d_ranges,
+                                         uint32_t nranges, const fourmc_image_rplan* d_rp, const uint32_t* d_slot, uint32_t nstaged,
+                                         uint64_t ndirect, uint64_t dst_delta, uint64_t stage_delta, fourmc_block* d_desc, hipStream_t s);
+hipError_t fourmc_launch_image_read_copy(const fourmc_image_entry* d_ent, const fourmc_image_range* d_ranges, uint32_t nranges,
+                                         const fourmc_image_rplan* d_rp, const uint32_t* d_slot, const void* d_stage, void* d_dst,
+                                         uint32_t max_piece, hipStream_t s);
+hipError_t fourmc_launch_image_read_reduce(const fourmc_image_entry* d_ent, fourmc_image_range* d_ranges, uint32_t nranges,
+                                           const fourmc_image_rplan* d_rp, const uint32_t* d_slot, const fourmc_block* d_desc,
+                                           uint64_t ndirect, hipStream_t s);
 #ifdef FOURMC_RESEARCH      /* the research side build exports these two: tools/zstd_timing.py and tools/k7x_prof.py size their read-backs with them */
 #pragma GCC visibility push(default)
 #endif

@@ -8,7 +8,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .binding import BLOCK_DTYPE, CODEC_LZ4_FAST, MAGIC_4MC, EngineError, ImageStatus, check, lib
+from .binding import (BLOCK_DTYPE, CODEC_LZ4_FAST, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageIndexInfo, ImageRange,
+                      ImageStatus, check, lib)
 
 
 def _stream_ptr(stream):
@@ -143,3 +144,55 @@ def decompress_image(d_image, d_dst, magic=MAGIC_4MC, image_bytes=None, stream=N
     res = {name: int(getattr(st, name)) for name, _ in ImageStatus._fields_}
     res["message"] = lib().fourmc_gpu_image_reason_text(st.reason).decode()
     return res
+
+
+def _image_len(d_image, image_bytes, what):
+    n = d_image.numel() if image_bytes is None else int(image_bytes)
+    if n > d_image.numel():
+        raise EngineError(f"{what}: image_bytes beyond the tensor")
+    return n
+
+
+def image_index(d_image, image_bytes=None, stream=None):
+    """The footer index of the single-stream image d_image[:image_bytes] (default: the whole tensor), built on the device.
+    Returns (info, entries): info as a dict (nblocks, framing, total_bytes, is_zstd: the file API's answers for the same bytes)
+    and the entries (image_off, data_off, usize, csize, xxh32) as a numpy structured array of nblocks rows."""
+    ptr = _dev_ptr(d_image, "image_index d_image")
+    n = _image_len(d_image, image_bytes, "image_index")
+    info = ImageIndexInfo()
+    check(lib().fourmc_gpu_image_index(ptr, n, 0, 0, C.byref(info), _stream_ptr(stream)), "fourmc_gpu_image_index")
+    k = max(int(info.nblocks), 0)
+    ent = np.zeros(k, dtype=IMAGE_ENTRY_DTYPE)
+    if k:
+        d_ent = torch.empty(k * IMAGE_ENTRY_DTYPE.itemsize, dtype=torch.uint8, device=d_image.device)
+        check(lib().fourmc_gpu_image_index(ptr, n, _ptr(d_ent), k, C.byref(info), _stream_ptr(stream)), "fourmc_gpu_image_index")
+        ent = d_ent.cpu().numpy().view(IMAGE_ENTRY_DTYPE).copy()
+    res = {name: int(getattr(info, name)) for name, _ in ImageIndexInfo._fields_ if name != "pad"}
+    return res, ent
+
+
+def image_decode_blocks(d_image, first, count, d_dst, image_bytes=None, stream=None):
+    """Blocks [first, first+count) of the image into d_dst (fourmc_file_decode_blocks on the device).  Returns what the file
+    function returns for the same bytes: the decoded bytes, or -1 / -2 / -3 / -4 / -5."""
+    ptr = _dev_ptr(d_image, "image_decode_blocks d_image")
+    dst = _dev_ptr(d_dst, "image_decode_blocks d_dst")
+    n = _image_len(d_image, image_bytes, "image_decode_blocks")
+    out = C.c_int64(0)
+    check(lib().fourmc_gpu_image_decode_blocks(ptr, n, int(first), int(count), dst, d_dst.numel(), C.byref(out), _stream_ptr(stream)),
+          "fourmc_gpu_image_decode_blocks")
+    return int(out.value)
+
+
+def image_read(d_image, ranges, d_dst, image_bytes=None, stream=None):
+    """Decoded byte ranges of the image: `ranges` is a sequence of (offset, length, dst_off); range i writes the content's bytes
+    [offset, offset+length) to d_dst[dst_off:].  Returns an int64 numpy array of the per-range results (length, 0, the index
+    code, -3, -5 or -4; include/fourmc_gpu.h)."""
+    ptr = _dev_ptr(d_image, "image_read d_image")
+    dst = _dev_ptr(d_dst, "image_read d_dst")
+    n = _image_len(d_image, image_bytes, "image_read")
+    q = np.asarray(ranges, dtype=np.uint64).reshape(-1, 3)
+    arr = (ImageRange * len(q))()
+    for i, (o, ln, d) in enumerate(q.tolist()):
+        arr[i].offset, arr[i].length, arr[i].dst_off, arr[i].result = o, ln, d, 0
+    check(lib().fourmc_gpu_image_read(ptr, n, C.cast(arr, C.c_void_p), len(q), dst, d_dst.numel(), _stream_ptr(stream)), "fourmc_gpu_image_read")
+    return np.array([arr[i].result for i in range(len(q))], dtype=np.int64)

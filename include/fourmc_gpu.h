@@ -196,6 +196,51 @@ const char* fourmc_gpu_image_reason_text(int reason);
  * file-order walk (everything the fast path does not prove: concatenations, damage, FOURMC_IMAGE_PARSE=walk). */
 void fourmc_gpu_image_parse_stats(unsigned long long* fast, unsigned long long* walk);
 
+/* ---- random access into single-stream images in device memory ---------------------------------------------------------------
+ * The device twins of fourmc_file_block_count / fourmc_file_decode_blocks (include/fourmc.h): the image's footer index, the
+ * decode of a block range, and reads of decoded byte ranges.  Every verdict is the one fourmc_file_decode_blocks reaches on the
+ * same bytes written to a file (its read_index and per-block checks, in their order); the format comes from the image's header.
+ * Synchronizations of `stream`: image_index 1, image_decode_blocks 2, image_read 3.  No per-block data crosses to the host, and
+ * the decoders may read up to 64 bytes past a payload, as with fourmc_gpu_4mc_decode_blocks. */
+/* one block: its footer entry and its block header (zeros when the header lies beyond the image).  32 bytes. */
+typedef struct fourmc_image_entry {
+    uint64_t image_off;   /* offset of the block's 12-byte header (the footer index, absolute)  */
+    uint64_t data_off;    /* offset of its first decoded byte = sum of usize of the blocks before it */
+    uint32_t usize, csize, xxh32, pad;
+} fourmc_image_entry;
+typedef struct fourmc_image_index_info {
+    int64_t  nblocks;       /* what fourmc_file_block_count returns for the same bytes: n, or -1 / -2                    */
+    int64_t  framing;       /* what fourmc_file_decode_blocks(0, n) with unlimited dst_cap would return if every payload
+                             * decoded correctly: 0, or its -1 / -2 / -4 from the per-block header checks (nblocks when < 0) */
+    uint64_t total_bytes;   /* sum of usize (meaningful when framing == 0)                                               */
+    int32_t  is_zstd, pad;  /* 1 for a .4mz image (0 when nblocks < 0)                                                   */
+} fourmc_image_index_info;
+/* The index of d_image[0, image_bytes).  d_entries NULL: the summary only; else min(nblocks, entries_cap) entries. */
+int fourmc_gpu_image_index(const void* d_image, uint64_t image_bytes, fourmc_image_entry* d_entries, uint64_t entries_cap,
+                           fourmc_image_index_info* info, void* stream);
+/* Blocks [first, first+count) into d_dst, block i at data_off[i] - data_off[first].  *result (host) is what
+ * fourmc_file_decode_blocks returns for the same bytes as a file: decoded bytes, or -1 / -2 / -3 / -4 / -5; its -6 (engine error)
+ * is this function's return code instead.  Nothing is written to d_dst unless every framing check of the range passes. */
+int fourmc_gpu_image_decode_blocks(const void* d_image, uint64_t image_bytes, uint32_t first, uint32_t count,
+                                   void* d_dst, uint64_t dst_cap, int64_t* result, void* stream);
+/* Batched reads of decoded bytes: range i writes bytes [offset, offset+length) of the image's content to d_dst + dst_off.
+ * `ranges` is a host array; each range's result, in order of precedence:
+ *   info.nblocks if < 0, else info.framing if != 0   the image cannot be indexed: every range gets this code;
+ *   0                        length == 0;
+ *   -3                       offset + length > total_bytes (nothing written);
+ *   -5                       dst_off + length > dst_cap (nothing written);
+ *   -4                       a block the range covers failed its XXH32, failed to decode, or decoded to a size other than its
+ *                            usize; the range's destination bytes are then unspecified;
+ *   length                   all bytes written.
+ * The blocks a range covers are those from the one holding its first byte to the one holding its last.  A block wholly inside a
+ * range is decoded straight into the range's destination; a partly covered one is decoded once into a 4 MiB staging slot, however
+ * many ranges share it, and the covered bytes are copied from there.  Destinations that overlap are FOURMC_EINVAL, checked
+ * before any launch.  Bytes of d_dst outside every range's [dst_off, dst_off+length) are never written.  The staging stays with
+ * the stream until fourmc_gpu_release_workspaces. */
+typedef struct fourmc_image_range { uint64_t offset, length, dst_off; int64_t result; } fourmc_image_range;   /* 32 bytes */
+int fourmc_gpu_image_read(const void* d_image, uint64_t image_bytes, fourmc_image_range* ranges, uint32_t nranges,
+                          void* d_dst, uint64_t dst_cap, void* stream);
+
 /* ---- host-buffer conveniences with the reference's per-block signatures ------------------- */
 /* These stage one block through HBM (H2D, one launch, D2H).  They exist so the JNI entry points
  * keep their exact one-call-one-block contract (SURVEY.md §8(b) "Batching constraint").        */
