@@ -493,6 +493,198 @@ int fourmc_gpu_image_compress(const void* d_src, uint64_t src_bytes, void* d_ima
     return FOURMC_OK;
 }
 
+// ------------------------------------------------------------------------ streaming image writer (image.hip)
+// One device allocation per writer, made by begin and freed by finish / abort: the running state, the descriptors of one batch, the
+// index (the absolute offset of every block header, then the running offset behind the last one), the carry slot and the staging.
+// The carry slot sits in front of the staging, so a codec reading past the slot's end stays inside the allocation.
+}   // extern "C"
+struct fourmc_image_writer {
+    hipStream_t s;
+    uint8_t* image;
+    uint64_t cap;
+    uint32_t magic;
+    int codec, codec_level;
+    uint32_t batch;                  // blocks per encode batch
+    uint64_t max_blocks;             // the most blocks image_cap can hold (the index has one entry more)
+    uint64_t total;                  // bytes appended so far
+    uint32_t nblocks;                // blocks queued for encoding: the next one's number in the index
+    uint32_t carry;                  // bytes of the incomplete block waiting in the carry slot
+    int err;                         // the first failure: every later call returns it
+    void* mem;
+    fourmc_image_enc_summary* d_sum;
+    fourmc_block* d_blk;
+    uint64_t* d_idx;
+    uint8_t* d_carry;
+    uint8_t* d_stage;
+};
+namespace {
+
+// One batch: the carry slot as block 0 when lead_len > 0, then m full blocks of src from src0; one container encode, the scan from
+// the running offset, the pack at the offsets it wrote into the index.  A codec launch takes one source base and adds each block's
+// 64-bit src_off to it, so the carry block shares the launch of the chunk's blocks: the base is the lower of the two addresses and
+// both offsets count from there.  (Encoding the carry block alone costs a whole block's encode latency per append: see
+// profiles/r09_image_writer.md.)
+int writer_batch(fourmc_image_writer* w, const uint8_t* src, uint64_t src0, uint32_t m, uint32_t lead_len)
+{
+    hipStream_t s = w->s;
+    const uint32_t lead = lead_len ? 1u : 0u;
+    const uint8_t* base = !lead ? src : (!m || uintptr_t(w->d_carry) < uintptr_t(src)) ? w->d_carry : src;
+    if (lead) HIP_TRY(fourmc_launch_image_wr_desc(w->d_blk, uint64_t(uintptr_t(w->d_carry) - uintptr_t(base)), 0, lead_len, 1, s));
+    if (m) {
+        HIP_TRY(fourmc_launch_image_wr_desc(w->d_blk + lead, uint64_t(uintptr_t(src) - uintptr_t(base)) + src0,
+                                            uint64_t(lead) * FOURMC_BLOCKSIZE, uint64_t(m) * FOURMC_BLOCKSIZE, m, s));
+    }
+    if (int r = fourmc_gpu_4mc_encode_blocks(base, w->d_stage, w->d_blk, lead + m, w->codec, w->codec_level, s)) return r;
+    HIP_TRY(fourmc_launch_image_wr_batch(w->image, w->d_blk, w->d_idx + w->nblocks, lead + m, w->d_stage, w->d_sum, s));
+    w->nblocks += lead + m;
+    return FOURMC_OK;
+}
+
+// The chunk after the capacity check: fill the carry slot; every complete block in batches; the rest into the carry slot.
+int writer_append(fourmc_image_writer* w, const uint8_t* src, uint64_t bytes)
+{
+    hipStream_t s = w->s;
+    uint64_t at = 0;
+    uint32_t lead = 0;
+    if (w->carry) {
+        const uint64_t need = FOURMC_BLOCKSIZE - w->carry, take = bytes < need ? bytes : need;
+        HIP_TRY(hipMemcpyAsync(w->d_carry + w->carry, src, take, hipMemcpyDeviceToDevice, s));
+        at = take;
+        if (take < need) { w->carry += uint32_t(take); return FOURMC_OK; }
+        lead = FOURMC_BLOCKSIZE; w->carry = 0;
+    }
+    uint64_t full = (bytes - at) / FOURMC_BLOCKSIZE;
+    while (lead || full) {
+        const uint64_t room = w->batch - (lead ? 1u : 0u);
+        const uint32_t m = uint32_t(full < room ? full : room);
+        if (int r = writer_batch(w, src, at, m, lead)) return r;
+        at += uint64_t(m) * FOURMC_BLOCKSIZE; full -= m; lead = 0;
+    }
+    if (at < bytes) {
+        HIP_TRY(hipMemcpyAsync(w->d_carry, src + at, bytes - at, hipMemcpyDeviceToDevice, s));
+        w->carry = uint32_t(bytes - at);
+    }
+    return FOURMC_OK;
+}
+
+// The carried tail as the last short block, the header / end mark / footer, one read-back of the running offset and the bad count.
+int writer_finish(fourmc_image_writer* w, uint64_t* image_bytes)
+{
+    if (int r = ensure_device()) return r;
+    hipStream_t s = w->s;
+    if (w->carry) {
+        if (int r = writer_batch(w, nullptr, 0, 0, w->carry)) return r;
+        w->carry = 0;
+    }
+    HIP_TRY(fourmc_launch_image_wr_tail(w->image, w->d_idx, w->nblocks, w->magic, s));
+    fourmc_image_enc_summary h;
+    uint64_t end = 0;
+    HIP_TRY(hipMemcpyAsync(&h, w->d_sum, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&end, w->d_idx + w->nblocks, sizeof end, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h.bad_blocks) { snprintf(g_err, sizeof g_err, "image_writer_finish: %u blocks with an encoder result outside [1, src_len]", h.bad_blocks); return FOURMC_EINVAL; }
+    *image_bytes = end + 12 + 20 + 4ull * w->nblocks;
+    return FOURMC_OK;
+}
+
+// Work may still be queued on the buffers unless the stream has just been synchronized.
+void writer_free(fourmc_image_writer* w, bool synced)
+{
+    if (w->mem) {
+        if (!synced) (void)hipStreamSynchronize(w->s);
+        (void)hipFree(w->mem);
+        (void)hipGetLastError();
+    }
+    delete w;
+}
+
+} // namespace
+extern "C" {
+
+int fourmc_gpu_image_writer_begin(fourmc_image_writer** out, void* d_image, uint64_t image_cap, uint32_t magic, int level,
+                                  uint32_t batch_blocks, void* stream)
+{
+    if (!out) { snprintf(g_err, sizeof g_err, "image_writer_begin: null writer"); return FOURMC_EINVAL; }
+    *out = nullptr;
+    if (magic != FOURMC_MAGIC_4MC && magic != FOURMC_MAGIC_4MZ) { snprintf(g_err, sizeof g_err, "magic 0x%08x is neither 4mc nor 4mz", magic); return FOURMC_EINVAL; }
+    if (!d_image) { snprintf(g_err, sizeof g_err, "image_writer_begin: null image"); return FOURMC_EINVAL; }
+    if (image_cap < fourmc_gpu_image_bound(0)) {
+        snprintf(g_err, sizeof g_err, "image capacity %llu below the bound %llu of an empty input", (unsigned long long)image_cap,
+                 (unsigned long long)fourmc_gpu_image_bound(0));
+        return FOURMC_EINVAL;
+    }
+    if (int r = ensure_device()) return r;
+    // n blocks need at least bound((n-1) * 4 MiB + 1) = 45 + 16 n + (n-1) * 4 MiB bytes of image
+    uint64_t max_blocks = (image_cap - 45 + FOURMC_BLOCKSIZE) / (FOURMC_BLOCKSIZE + 16);
+    if (max_blocks > 0x3FFFFFFFull) max_blocks = 0x3FFFFFFFull;
+    uint64_t batch = batch_blocks ? batch_blocks : 512;
+    if (batch > max_blocks) batch = max_blocks ? max_blocks : 1;
+    const size_t o_blk = align256(sizeof(fourmc_image_enc_summary)), o_idx = o_blk + align256(size_t(batch) * sizeof(fourmc_block));
+    const size_t o_carry = o_idx + align256((size_t(max_blocks) + 1) * 8), o_stage = o_carry + FOURMC_BLOCKSIZE;
+    const size_t bytes = o_stage + size_t(batch) * FOURMC_BLOCKSIZE;
+    auto* w = new fourmc_image_writer();
+    w->s = static_cast<hipStream_t>(stream);
+    w->image = static_cast<uint8_t*>(d_image); w->cap = image_cap; w->magic = magic;
+    w->codec = fourmc_level_codec(magic, level, &w->codec_level);
+    w->batch = uint32_t(batch); w->max_blocks = max_blocks;
+    const hipError_t me = hipMalloc(&w->mem, bytes);
+    if (me != hipSuccess) {
+        (void)hipGetLastError(); w->mem = nullptr;
+        delete w;
+        if (me == hipErrorOutOfMemory) { snprintf(g_err, sizeof g_err, "hipMalloc(%zu bytes of image writer): out of memory", bytes); return FOURMC_ENOMEM; }
+        return fail_hip(me, "hipMalloc(image writer)");
+    }
+    char* base = static_cast<char*>(w->mem);
+    w->d_sum = reinterpret_cast<fourmc_image_enc_summary*>(base);
+    w->d_blk = reinterpret_cast<fourmc_block*>(base + o_blk);
+    w->d_idx = reinterpret_cast<uint64_t*>(base + o_idx);
+    w->d_carry = reinterpret_cast<uint8_t*>(base + o_carry);
+    w->d_stage = reinterpret_cast<uint8_t*>(base + o_stage);
+    // no bad result yet; the running offset starts behind the 12-byte file header
+    hipError_t e = hipMemsetAsync(w->d_sum, 0, sizeof(fourmc_image_enc_summary), w->s);
+    if (e == hipSuccess) e = hipMemsetAsync(w->d_idx, 0, 8, w->s);
+    if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w->d_idx), 12, 1, w->s);
+    if (e != hipSuccess) { const int r = fail_hip(e, "image_writer_begin: state"); writer_free(w, false); return r; }
+    *out = w;
+    return FOURMC_OK;
+}
+
+int fourmc_gpu_image_writer_append(fourmc_image_writer* w, const void* d_src, uint64_t bytes)
+{
+    if (!w) { snprintf(g_err, sizeof g_err, "image_writer_append: null writer"); return FOURMC_EINVAL; }
+    if (w->err) { snprintf(g_err, sizeof g_err, "image_writer_append: the writer failed earlier (%d)", w->err); return w->err; }
+    if (bytes && !d_src) { snprintf(g_err, sizeof g_err, "image_writer_append: null source"); return w->err = FOURMC_EINVAL; }
+    // the capacity refusal: the host knows the total exactly; nothing is queued and the writer stays usable
+    const uint64_t total = w->total + bytes;
+    if (total < w->total || (total + FOURMC_BLOCKSIZE - 1) / FOURMC_BLOCKSIZE > w->max_blocks || fourmc_gpu_image_bound(total) > w->cap) {
+        snprintf(g_err, sizeof g_err, "image_writer_append: %llu bytes after %llu would pass the image capacity %llu",
+                 (unsigned long long)bytes, (unsigned long long)w->total, (unsigned long long)w->cap);
+        return FOURMC_EINVAL;
+    }
+    if (!bytes) return FOURMC_OK;
+    int r = ensure_device();
+    if (!r) r = writer_append(w, static_cast<const uint8_t*>(d_src), bytes);
+    if (r) return w->err = r;
+    w->total = total;
+    return FOURMC_OK;
+}
+
+int fourmc_gpu_image_writer_finish(fourmc_image_writer* w, uint64_t* image_bytes)
+{
+    if (!w) { snprintf(g_err, sizeof g_err, "image_writer_finish: null writer"); return FOURMC_EINVAL; }
+    int r = w->err;
+    if (r) snprintf(g_err, sizeof g_err, "image_writer_finish: the writer failed earlier (%d)", r);
+    else if (!image_bytes) { snprintf(g_err, sizeof g_err, "image_writer_finish: null image_bytes"); r = FOURMC_EINVAL; }
+    else r = writer_finish(w, image_bytes);
+    writer_free(w, r == FOURMC_OK);
+    return r;
+}
+
+void fourmc_gpu_image_writer_abort(fourmc_image_writer* w)
+{
+    if (w) writer_free(w, false);
+}
+
 const char* fourmc_gpu_image_reason_text(int reason)
 {
     switch (reason) {                       // fourmc_file.c: decode_stream, the writer thread (wjob_main)

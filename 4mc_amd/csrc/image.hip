@@ -11,6 +11,8 @@
 // The walk is decode_stream's loop on one lane, in file order, for everything else (a damaged or lying footer, a truncated
 // image, trailing bytes, a concatenation of streams).  Both write the same summary and, after the engine has allocated for the
 // count it read back, the same descriptors.  Header fields are big-endian u32 at any byte offset.
+// Streaming writes reuse the encode half: a batch's descriptors may start inside a chunk or in the writer's carry slot, and its scan
+// runs on from the offset the previous batch left in the writer's device index.
 // Random access (second half): the footer index of a single stream, block-range decodes and byte-range reads, each with the
 // verdict fourmc_file_decode_blocks (fourmc_file.c) reaches on the same bytes as a file.
 #include <hip/hip_runtime.h>
@@ -67,27 +69,38 @@ __device__ __forceinline__ uint32_t scan_add(uint32_t v)
 __device__ __forceinline__ uint32_t wave_total(uint32_t incl) { return uint32_t(__builtin_amdgcn_readlane(int(incl), 63)); }
 
 // ------------------------------------------------------------------------------------------------------------- encode
-__global__ __launch_bounds__(256)
-void image_enc_desc_kernel(fourmc_block* __restrict__ blocks, uint64_t src_bytes, uint32_t n)
+// block b of n: src0 + b * 4 MiB of the source, dst0 + b * 4 MiB of the staging, src_len = what is left of src_bytes, at most 4 MiB
+__device__ __forceinline__ void enc_desc(fourmc_block* __restrict__ blocks, uint64_t src0, uint64_t dst0, uint64_t src_bytes, uint32_t n)
 {
     const uint32_t b = blockIdx.x * 256 + threadIdx.x;
     if (b >= n) return;
     const uint64_t at = uint64_t(b) * kBlock;
     fourmc_block d;
-    d.src_off = at; d.dst_off = at;
+    d.src_off = src0 + at; d.dst_off = dst0 + at;
     d.src_len = uint32_t(src_bytes - at < kBlock ? src_bytes - at : kBlock);
     d.dst_cap = d.src_len; d.result = 0; d.xxh32 = 0;
     blocks[b] = d;
 }
+__global__ __launch_bounds__(256)
+void image_enc_desc_kernel(fourmc_block* __restrict__ blocks, uint64_t src_bytes, uint32_t n)
+{ enc_desc(blocks, 0, 0, src_bytes, n); }
+// a batch of the streaming writer: its blocks start at src0 of its chunk (or of the carry slot) and at dst0 of its staging
+__global__ __launch_bounds__(256)
+void image_wr_desc_kernel(fourmc_block* __restrict__ blocks, uint64_t src0, uint64_t dst0, uint64_t src_bytes, uint32_t n)
+{ enc_desc(blocks, src0, dst0, src_bytes, n); }
 
 // off[b] = 12 + sum_{j<b} (12 + csize_j), b = 0..n (off[n]: where the end mark goes); one wave, 64 blocks per step with a 64-bit
 // carry.  A result outside [1, src_len] cannot come from the container encode; it is counted (the engine fails the call) and
 // clamped so that the pack and the footer stay inside the bound the engine checked the capacity against.
+// kWriter: one batch of the streaming writer.  `off` is its device index at the batch's first block number; the scan starts from
+// off[0], the running image offset the previous batch left there as its off[n] (12 before the first), and adds its bad results to
+// the running count.
+template <bool kWriter>
 __global__ __launch_bounds__(64)
 void image_enc_scan_kernel(fourmc_block* __restrict__ blocks, uint64_t* __restrict__ off, uint32_t n, fourmc_image_enc_summary* sum)
 {
     const int lane = threadIdx.x;
-    uint64_t carry = 12;
+    uint64_t carry = kWriter ? off[0] : 12;
     uint32_t bad = 0;
     for (uint32_t b0 = 0; b0 < n; b0 += 64) {
         const uint32_t b = b0 + uint32_t(lane);
@@ -105,8 +118,12 @@ void image_enc_scan_kernel(fourmc_block* __restrict__ blocks, uint64_t* __restri
     for (int o = 32; o; o >>= 1) bad += uint32_t(__shfl_xor(int(bad), o));
     if (lane == 0) {
         off[n] = carry;
-        sum->image_bytes = carry + 12 + 20 + 4ull * n;
-        sum->bad_blocks = bad;
+        if (kWriter) {
+            sum->bad_blocks += bad;
+        } else {
+            sum->image_bytes = carry + 12 + 20 + 4ull * n;
+            sum->bad_blocks = bad;
+        }
     }
 }
 
@@ -620,9 +637,31 @@ hipError_t fourmc_launch_image_enc_desc(fourmc_block* d_blocks, uint64_t src_byt
 hipError_t fourmc_launch_image_enc_frame(void* d_image, fourmc_block* d_blocks, uint64_t* d_off, uint32_t n, uint32_t magic,
                                          const void* d_staging, fourmc_image_enc_summary* d_sum, hipStream_t s)
 {
-    hipLaunchKernelGGL(image_enc_scan_kernel, dim3(1), dim3(64), 0, s, d_blocks, d_off, n, d_sum);
+    hipLaunchKernelGGL(image_enc_scan_kernel<false>, dim3(1), dim3(64), 0, s, d_blocks, d_off, n, d_sum);
     if (hipError_t e = hipGetLastError()) return e;
     if (hipError_t e = fourmc_launch_pack_image(d_staging, d_image, d_blocks, d_off, n, s)) return e;
+    hipLaunchKernelGGL(image_enc_tail_kernel, dim3(1), dim3(256), 0, s, static_cast<uint8_t*>(d_image), d_off, n, magic);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_image_wr_desc(fourmc_block* d_blocks, uint64_t src0, uint64_t dst0, uint64_t src_bytes, uint32_t n, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(image_wr_desc_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_blocks, src0, dst0, src_bytes, n);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_image_wr_batch(void* d_image, fourmc_block* d_blocks, uint64_t* d_off, uint32_t n, const void* d_staging,
+                                        fourmc_image_enc_summary* d_sum, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(image_enc_scan_kernel<true>, dim3(1), dim3(64), 0, s, d_blocks, d_off, n, d_sum);
+    if (hipError_t e = hipGetLastError()) return e;
+    return fourmc_launch_pack_image(d_staging, d_image, d_blocks, d_off, n, s);
+}
+
+hipError_t fourmc_launch_image_wr_tail(void* d_image, const uint64_t* d_off, uint32_t n, uint32_t magic, hipStream_t s)
+{
     hipLaunchKernelGGL(image_enc_tail_kernel, dim3(1), dim3(256), 0, s, static_cast<uint8_t*>(d_image), d_off, n, magic);
     return hipGetLastError();
 }

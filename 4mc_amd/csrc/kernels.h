@@ -88,6 +88,13 @@ typedef struct fourmc_image_enc_summary {
 hipError_t fourmc_launch_image_enc_desc(fourmc_block* d_blocks, uint64_t src_bytes, uint32_t n, hipStream_t s);
 hipError_t fourmc_launch_image_enc_frame(void* d_image, fourmc_block* d_blocks, uint64_t* d_off, uint32_t n, uint32_t magic,
                                          const void* d_staging, fourmc_image_enc_summary* d_sum, hipStream_t s);
+/* the streaming writer's batches (fourmc_gpu_image_writer_*): descriptors of n blocks of src_bytes at src0 of their source and dst0
+ * of the staging; the scan of one batch from the running offset d_off[0] (the writer's index at the batch's first block number) into
+ * d_off[0..n], its bad results added to d_sum->bad_blocks, then the pack; the header, end mark and footer of n blocks from d_off */
+hipError_t fourmc_launch_image_wr_desc(fourmc_block* d_blocks, uint64_t src0, uint64_t dst0, uint64_t src_bytes, uint32_t n, hipStream_t s);
+hipError_t fourmc_launch_image_wr_batch(void* d_image, fourmc_block* d_blocks, uint64_t* d_off, uint32_t n, const void* d_staging,
+                                        fourmc_image_enc_summary* d_sum, hipStream_t s);
+hipError_t fourmc_launch_image_wr_tail(void* d_image, const uint64_t* d_off, uint32_t n, uint32_t magic, hipStream_t s);
 /* fast: the footer-driven parser; walk: the file-order walk (count mode skips itself when the fast path accepted the image).
  * d_blocks NULL: count into *d_ps; else fill the descriptors of the parse *d_ps holds. */
 hipError_t fourmc_launch_image_parse(const void* d_image, uint64_t image_bytes, uint32_t magic, int fast, int walk,

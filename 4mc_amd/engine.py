@@ -196,3 +196,65 @@ def image_read(d_image, ranges, d_dst, image_bytes=None, stream=None):
         arr[i].offset, arr[i].length, arr[i].dst_off, arr[i].result = o, ln, d, 0
     check(lib().fourmc_gpu_image_read(ptr, n, C.cast(arr, C.c_void_p), len(q), dst, d_dst.numel(), _stream_ptr(stream)), "fourmc_gpu_image_read")
     return np.array([arr[i].result for i in range(len(q))], dtype=np.int64)
+
+
+class ImageWriter:
+    """Streaming writes of one .4mc / .4mz image into d_image (fourmc_gpu_image_writer_*): append() chunks of any size as they
+    arrive, finish() for the image length.  The image is the one compress_image writes for the concatenation of the chunks.
+    Appends queue work on `stream` (default: the current stream) and return; only finish() synchronizes.  As a context manager
+    the writer is aborted when the block raises, or when it ends without finish()."""
+
+    def __init__(self, d_image, magic=MAGIC_4MC, level=1, batch_blocks=0, stream=None):
+        ptr = _dev_ptr(d_image, "ImageWriter d_image")
+        self._stream = torch.cuda.current_stream() if stream is None else stream
+        h = C.c_void_p(0)
+        check(lib().fourmc_gpu_image_writer_begin(C.byref(h), ptr, d_image.numel(), magic, level, batch_blocks,
+                                                  _stream_ptr(self._stream)), "fourmc_gpu_image_writer_begin")
+        self._h = h.value
+        self._image = d_image                     # the queued packs write into it until finish
+
+    def _handle(self, what):
+        if not self._h:
+            raise EngineError(f"ImageWriter.{what}: the writer is finished or aborted")
+        return self._h
+
+    def append(self, chunk):
+        """Queues the chunk (a contiguous uint8 CUDA tensor); the caching allocator keeps its memory until the stream has read it."""
+        h = self._handle("append")
+        ptr = _dev_ptr(chunk, "ImageWriter.append chunk")
+        if chunk.numel():
+            chunk.record_stream(self._stream)
+        check(lib().fourmc_gpu_image_writer_append(h, ptr, chunk.numel()), "fourmc_gpu_image_writer_append")
+
+    def finish(self):
+        """Writes the last block, the header and the footer; returns the image length.  The writer is closed whatever happens."""
+        h = self._handle("finish")
+        self._h = None
+        out = C.c_uint64(0)
+        check(lib().fourmc_gpu_image_writer_finish(h, C.byref(out)), "fourmc_gpu_image_writer_finish")
+        return int(out.value)
+
+    def abort(self):
+        """Frees the writer without an image."""
+        h = self._handle("abort")
+        self._h = None
+        lib().fourmc_gpu_image_writer_abort(h)
+
+    @property
+    def closed(self):
+        return not self._h
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self._h:
+            self.abort()
+        return False
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                self.abort()
+            except Exception:
+                pass

@@ -152,6 +152,46 @@ uint64_t fourmc_gpu_image_bound(uint64_t src_bytes);
 int fourmc_gpu_image_compress(const void* d_src, uint64_t src_bytes, void* d_image, uint64_t image_cap,
                               uint64_t* image_bytes, uint32_t magic, int level, void* stream);
 
+/* ---- streaming writes of one image: append chunks of any size as they arrive --------------------------------------------------
+ * Output.  After finish, d_image[0, *image_bytes) is byte-identical to what fourmc_gpu_image_compress writes for the concatenation
+ *   of every appended chunk at the same magic and level, and so to the file `4mc -<level>` / `4mc -z -<level>` writes for that
+ *   input.  This holds for every way the input is cut into appends (empty ones, 1-byte ones, appends ending inside a block, exact
+ *   multiples of 4 MiB, single appends larger than batch_blocks blocks): blocks are cut at every 4 MiB of the CONCATENATED input,
+ *   as the CLI cuts them, and the last block is short.  The level -> codec mapping is the one image_compress shares with the file API, and every setting it
+ *   obeys (FOURMC_LZ4_ENCODE among them) applies to the writer in the same way.
+ * Begin.  Checks the magic and the pointers, then allocates everything the writer owns in one piece: a 4 MiB carry slot for the
+ *   incomplete block, batch_blocks x 4 MiB of staging, the descriptors of one batch, the device index (one 8-byte offset per block
+ *   image_cap can hold, plus one) and the device state.  batch_blocks 0 means 512, the file API's batch; it is lowered to the most
+ *   blocks image_cap can hold.  The capacity check of append guarantees that the block count never exceeds the index, which never
+ *   grows.  FOURMC_EINVAL for a bad magic, a NULL pointer or image_cap < fourmc_gpu_image_bound(0); FOURMC_ENODEV without a device;
+ *   FOURMC_ENOMEM when the allocation fails.  On any error *w is left NULL.
+ * Append.  Queues work on the writer's stream and returns: no host synchronization, no device-to-host copy, no hipMalloc / hipFree
+ *   of its own (the engine's codec workspaces may still grow the first time a batch size is seen, as in every codec call; after
+ *   that, appends of the same shape allocate nothing).  The chunk may be reused or freed once the stream has passed the append
+ *   (the usual stream-order rule): the bytes of a block still incomplete are copied into the carry slot on the stream, and nothing
+ *   reads d_src after the work this append queued.  Capacity is checked on the host before anything is queued: if
+ *   fourmc_gpu_image_bound(total + bytes) > image_cap, where total is every byte appended so far, the append returns FOURMC_EINVAL
+ *   and the writer is unchanged and still usable.  Chunks larger than batch_blocks blocks are encoded in pieces of at most
+ *   batch_blocks blocks, so the writer's own memory stays bounded whatever the input's size.  A completed carry block is encoded
+ *   in the same codec launch as the chunk's blocks (from the lower of the two addresses, with 64-bit offsets).
+ * Finish.  Encodes the carried tail as the last short block, if there is one, then writes the file header, the end mark and the
+ *   footer with its XXH32.  It synchronizes the stream once, to read back the image length and the count of bad encoder results;
+ *   if any block's result fell outside [1, src_len] it fails with FOURMC_EINVAL, the guard image_compress has.  *image_bytes is
+ *   the image's length.  finish frees the writer whatever it returns.
+ * Failures.  After any failure other than the capacity refusal (FOURMC_ENOMEM from a codec workspace, FOURMC_EHIP, ...) the
+ *   writer is poisoned: later appends return that first error, and finish returns it and frees.
+ * Independence.  The writer owns its buffers and holds no per-stream workspace of the engine between calls, so other engine calls
+ *   on the same stream may run between appends (image compress, decompress and read, block encode and decode), and several
+ *   writers may be open at once, on one stream or several.  fourmc_gpu_release_workspaces does not touch a writer's buffers: only
+ *   finish and abort free them.  A writer is used by one thread at a time.  abort frees the writer without an image (it waits for
+ *   the work queued on the stream first); abort(NULL) does nothing. */
+typedef struct fourmc_image_writer fourmc_image_writer;      /* opaque */
+int  fourmc_gpu_image_writer_begin(fourmc_image_writer** w, void* d_image, uint64_t image_cap, uint32_t magic, int level,
+                                   uint32_t batch_blocks, void* stream);
+int  fourmc_gpu_image_writer_append(fourmc_image_writer* w, const void* d_src, uint64_t bytes);
+int  fourmc_gpu_image_writer_finish(fourmc_image_writer* w, uint64_t* image_bytes);   /* frees w, whatever it returns */
+void fourmc_gpu_image_writer_abort(fourmc_image_writer* w);                         /* frees w; NULL is a no-op */
+
 /* the verdict of an image decode: which of the CLI's messages (fourmc_file.c: decode_stream) it ends with */
 enum {
     FOURMC_IMG_OK                    = 0,
