@@ -11,15 +11,22 @@ value = uncompressed bytes of all ranks / wall time of a step (compress + decomp
 its own 8 GiB shard of blocks (block ranges are independent; the only collective is the gather of
 per-block compressed sizes for the footer index).
 
-Beside the headline (never part of `value`), at N = 1:
+A plain run does only what the headline needs: set up, warm up, time the steps, check the round trip of the last one at full
+size, write --dump-outputs, print the line (headline, compress / decompress rates, ratio, stored blocks, per_rank for N > 1).
+With --full it also measures, never as part of `value`:
+  kernel_ms       per-kernel times in an extra pass after the timed steps, with `roofline` / `roofline_decode` and the HBM
+                  traffic of the two headline kernels (tools/traffic_probe.py under rocprofv3 at N = 1, else profiles/)
+and at N = 1 (--no-cpu drops the host legs, --no-extras the rest):
+  cpu_baseline    the reference's LZ4 path on the host cores (bounded sample), with ratio_vs_reference
   other_configs   BASELINE configs[2] 4mz Fast (zstd 1), 4mz Medium (zstd 3), configs[3] 4mc High (LZ4 HC 4) on the same
                   corpus, and configs[4]'s workload - 4mz Ultra (zstd 12) on the synthetic LOG corpus - at a single-GPU
                   size; each with the reference's own code timed on the host cores next to it
-  decode_64GiB    the 64 GiB decode-only configuration the north-star target is quoted on
-  cpu_baseline    the reference's LZ4 path on the host cores (bounded sample)
+  lz4_fast_tolerant, decode_paths, decode_64GiB (the 64 GiB decode-only configuration the north-star target is quoted on),
+  decode_64GiB_lz4_only, cli_wallclock
 Corpus: S-mix (tools/corpus.c) unless SILESIA_DIR names a directory with the silesia files.
 
-Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]   (N>1 via torch.distributed.run)
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full [--no-cpu] [--no-extras]]
+      (N>1 via torch.distributed.run)
 --dump-outputs DIR: after the timed steps, what the last one computed (rank 0's) is written as DIR/<name>.npy (float64 per-block
 arrays, float32 seeded byte samples of the .4mc image and of the decoded output; 34 MB at most), for comparing two builds.
 """
@@ -129,8 +136,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--blocks", type=int, default=int(os.environ.get("FOURMC_BENCH_BLOCKS", 2048)),
                     help="4 MiB blocks per GPU (2048 = 8 GiB, BASELINE configs[1])")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the other BASELINE configs and the 64 GiB decode leg timed after the headline")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure what the module docstring lists under --full")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the host-core baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the traffic probe, the other BASELINE configs and the 64 GiB decode leg timed after the headline")
     ap.add_argument("--decode-blocks", type=int, default=16384, help="blocks of the decode-only leg (16384 = 64 GiB)")
     ap.add_argument("--config", choices=["fast", "ultra_logs"], default="fast",
                     help="fast: BASELINE configs[1], 4mc Fast on the S-mix (the headline).  ultra_logs: configs[4]'s codec and corpus - 4mz Ultra (zstd 12) on the "
@@ -571,13 +579,14 @@ def main():
     csz = state["csz"]
     U = nb * B
     Cbytes = int((csz + 12).sum().item())
-    kts = kernel_times()
     ms_step = wall / args.steps * 1e3
     comp_ms = float(np.mean(phase["compress"])); dec_ms = float(np.mean(phase["decompress"]))
-    alg_enc = U + int(csz.sum().item())          # encode launch: reads U, writes payloads
-    alg_dec = int(csz.sum().item()) + U          # decode launch: reads payloads, writes U
-    dom = ENC if kts[ENC] >= kts[DEC] else DEC
-    alg = alg_enc if dom == ENC else alg_dec
+    kts = kernel_times() if args.full else None  # an extra pass of every launch: --full only
+    if kts is not None:
+        alg_enc = U + int(csz.sum().item())      # encode launch: reads U, writes payloads
+        alg_dec = int(csz.sum().item()) + U      # decode launch: reads payloads, writes U
+        dom = ENC if kts[ENC] >= kts[DEC] else DEC
+        alg = alg_enc if dom == ENC else alg_dec
 
     # HBM bytes per launch from the PMC passes (rocprofv3 FETCH_SIZE + WRITE_SIZE, separate runs of this same script at
     # --blocks 512; summary and calibration note in profiles/), scaled to this launch: NOT measured in this run
@@ -586,7 +595,7 @@ def main():
     # passes around the same launches at this launch size), else taken from the committed passes of the round
     traffic_src = {}
     probe = None
-    if rank == 0 and world == 1 and not args.no_extras and not os.environ.get("FOURMC_BENCH_NO_PMC"):
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not os.environ.get("FOURMC_BENCH_NO_PMC"):
         try:
             import shutil, subprocess
             if shutil.which("rocprofv3"):
@@ -596,7 +605,7 @@ def main():
                     traffic[k] = probe[k]["traffic"]; traffic_src[k] = probe["source"]
         except Exception as e:
             probe = {"error": repr(e)[:300]}
-    if not traffic:
+    if kts is not None and not traffic:
         try:
             tj = json.load(open(os.path.join(ROOT, TRAFFIC_JSON)))
             for k in ("lz4_encode", "lz4_decode"):
@@ -627,17 +636,18 @@ def main():
             "decompress_GBps": round(world * U / (dec_ms * 1e-3) / 1e9, 3),
             "ratio": round(U / (12 + Cbytes + 12 + 20 + 4 * nb), 4),
             "stored_blocks": int((csz == B).sum().item()),
-            "kernel_ms": {k: round(v, 3) for k, v in kts.items()},
-            "kernel_ms_note": "HIP events on the launch stream in an extra pass after the timed steps; the hash launches are timed alone and subtracted from the fused calls, so the parts need not add up to ms_per_step",
-            "roofline": roof(dom, alg),
-            "roofline_decode": roof(DEC, alg_dec),
         }
+        if kts is not None:
+            line["kernel_ms"] = {k: round(v, 3) for k, v in kts.items()}
+            line["kernel_ms_note"] = "HIP events on the launch stream in an extra pass after the timed steps; the hash launches are timed alone and subtracted from the fused calls, so the parts need not add up to ms_per_step"
+            line["roofline"] = roof(dom, alg)
+            line["roofline_decode"] = roof(DEC, alg_dec)
         if per_rank is not None:
             line["per_rank"] = per_rank; line["rccl_ranks"] = rccl_ranks
             line["footer_index_check"] = "every rank's first block offset equals 12 + the bytes of the ranks before it (recomputed from the gathered sizes)"
         if probe is not None:
             line["traffic_probe"] = probe
-        if world == 1 and not args.no_cpu:             # the host-core baseline is measured at N = 1 only
+        if args.full and world == 1 and not args.no_cpu:   # the host-core baseline is measured at N = 1 only
             cb, ref_cs = cpu_leg(helpers, base, base_blocks, "zstd12" if ULTRA else "lz4", 12.0, B, logs=ULTRA)
             line["cpu_baseline"] = cb
             mine = csz[:base_blocks].cpu().numpy()
@@ -647,7 +657,7 @@ def main():
         else:
             line["cpu_baseline"] = None
             line["ratio_vs_reference"] = None
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             line["other_configs"] = other_configs()
             line["lz4_fast_tolerant"] = tolerant_leg()
             tl = line["lz4_fast_tolerant"]

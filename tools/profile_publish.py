@@ -27,8 +27,8 @@ t["lz4_decode"] = {"fetch_KiB": sum(fe[k]["FETCH_SIZE"] for k in dks), "write_Ki
 t["xxh32"] = {"fetch_KiB": fe[xk]["FETCH_SIZE"], "write_KiB": wr[xk]["WRITE_SIZE"]}
 t["pack"] = {"fetch_KiB": fe["pack_image_kernel"]["FETCH_SIZE"], "write_KiB": wr["pack_image_kernel"]["WRITE_SIZE"]}
 json.dump(t, open(traffic_json, "w"), indent=1)
-open(f"profiles/{name}_kernel_stats.md", "w").write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 2 --warmup 1 --no-cpu   (tools/profile_round.sh)\n\n" + open(o + "summary_stats.md").read())
-open(f"profiles/{name}_hbm_traffic.md", "w").write("# rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate passes) -- python bench.py --no-extras --no-cpu --steps 2 --warmup 1   (2048 blocks: the kernels of the headline launch)\n# per-dispatch values are KiB (see the calibration note in the round's *_traffic.json); the LZ4 decode path = " + " + ".join(dks) + "\n\n" + open(o + "summary_fetch.md").read() + "\n" + open(o + "summary_write.md").read())
+open(f"profiles/{name}_kernel_stats.md", "w").write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 2 --warmup 1 --full --no-cpu   (tools/profile_round.sh)\n\n" + open(o + "summary_stats.md").read())
+open(f"profiles/{name}_hbm_traffic.md", "w").write("# rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate passes) -- python bench.py --full --no-extras --no-cpu --steps 2 --warmup 1   (2048 blocks: the kernels of the headline launch)\n# per-dispatch values are KiB (see the calibration note in the round's *_traffic.json); the LZ4 decode path = " + " + ".join(dks) + "\n\n" + open(o + "summary_fetch.md").read() + "\n" + open(o + "summary_write.md").read())
 open(f"profiles/{name}_bench_under_rocprof.json", "w").write(open(o + "bench_stats.json").read())
 HDR = "| kernel | waves' time parked (s_waitcnt) | issuing | issue stalls | VALU busy (of 1024 SIMDs) | SALU : VALU instructions | instructions per output byte (VALU+SALU+LDS+VMEM) | LDS instr | VMEM rd / wr instr |\n|---|---|---|---|---|---|---|---|---|\n"
 def sqrow(label, x, y, out_bytes):
@@ -39,7 +39,7 @@ def sqrow(label, x, y, out_bytes):
     return "| %s | %.0f %% | %.0f %% | %.0f %% | %.0f %% | %.2f | %.3f | %.2e | %.2e / %.2e |\n" % (label, 100 * x["SQ_WAIT_ANY"] / wc, 100 * x["SQ_ACTIVE_INST_ANY"] / wc, 100 * x["SQ_WAIT_INST_ANY"] / wc,
             100 * 4 * av / (1024 * cyc), x["SQ_INSTS_SALU"] / max(x["SQ_INSTS_VALU"], 1), n / out_bytes, lds, y.get("SQ_INSTS_VMEM_RD", 0), y.get("SQ_INSTS_VMEM_WR", 0))
 a, b = rows(o + "summary_sq.md"), rows(o + "summary_sq2.md")
-out = "# rocprofv3 --pmc <SQ group> -- python bench.py --no-extras --no-cpu --steps 2 --warmup 1   (2048 blocks; two passes, tools/profile_round.sh)\n# per-dispatch sums over all waves; SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles, GRBM_GUI_ACTIVE is summed over the 8 XCDs\n\n" + HDR
+out = "# rocprofv3 --pmc <SQ group> -- python bench.py --full --no-extras --no-cpu --steps 2 --warmup 1   (2048 blocks; two passes, tools/profile_round.sh)\n# per-dispatch sums over all waves; SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles, GRBM_GUI_ACTIVE is summed over the 8 XCDs\n\n" + HDR
 for k in ["lz4_encode_fast_kernel"] + [k for k in DEC if k in a] + [k for k in a if k.startswith("xxh32")][:1]:
     out += sqrow(k, a[k], b.get(k, {}), 2048 * 4194304.0)
 out += "\n" + open(o + "summary_sq.md").read() + "\n" + open(o + "summary_sq2.md").read()

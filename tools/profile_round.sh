@@ -10,11 +10,11 @@ export TMPDIR=/tmp
 here=$(pwd)
 sum() { db=$(find $raw/$1 -name "*_results.db" | head -1); [ -n "$db" ] && python $here/tools/rocpd_summary.py $db > $here/$out/summary_$1.md; }
 run() { name=$1; shift; (cd /tmp && rocprofv3 "$@" -d $raw/$name -o $name -- python $here/bench.py --steps 2 --warmup 1 ${BENCH_ARGS:-} > $here/$out/$name.log 2>&1); sum $name; grep "^{\"metric\"" $out/$name.log | tail -1 > $out/bench_$name.json; }
-BENCH_ARGS="--no-cpu" run stats --kernel-trace --stats
-BENCH_ARGS="--no-extras --no-cpu" run fetch --pmc FETCH_SIZE
-BENCH_ARGS="--no-extras --no-cpu" run write --pmc WRITE_SIZE
-BENCH_ARGS="--no-extras --no-cpu" run sq --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU
-BENCH_ARGS="--no-extras --no-cpu" run sq2 --pmc SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE
+BENCH_ARGS="--full --no-cpu" run stats --kernel-trace --stats
+BENCH_ARGS="--full --no-extras --no-cpu" run fetch --pmc FETCH_SIZE
+BENCH_ARGS="--full --no-extras --no-cpu" run write --pmc WRITE_SIZE
+BENCH_ARGS="--full --no-extras --no-cpu" run sq --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU
+BENCH_ARGS="--full --no-extras --no-cpu" run sq2 --pmc SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE
 # the LZ4 decode paths alone (tools/k1_timing.py, decode only): the segment-parallel path at 2048 and at 8192 blocks (one workspace-full:
 # the regime of the 64 GiB leg), the tile path at 2048 and at 512 blocks (what the file API sends: auto takes it up to 1536)
 k1() { name=$1; mode=$2; nb=$3; shift 3; (cd /tmp && FOURMC_DECODE=$mode FOURMC_BENCH_BLOCKS=$nb rocprofv3 "$@" -d $raw/$name -o $name -- python $here/tools/k1_timing.py > $here/$out/$name.log 2>&1); sum $name; }
