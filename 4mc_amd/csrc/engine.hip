@@ -278,8 +278,10 @@ static int lz4_fast_encode(const void* d_src, void* d_dst, fourmc_block* d_block
         return in_pieces(s, n, 4096, fourmc_lz4_par_work_bytes, [&](uint32_t b0, uint32_t m, void* work) -> int {
             HIP_TRY(fourmc_launch_lz4_encode_par(d_src, d_dst, d_blocks + b0, m, container_mode, work, s)); return FOURMC_OK; });
     }
-    HIP_TRY(fourmc_launch_lz4_encode_fast(d_src, d_dst, d_blocks, n, container_mode, s));
-    return FOURMC_OK;
+    // the reference's parse writes sequence records (16 bytes each, a 4 MiB block's area is 16 MiB), the emit kernel the bytes; the
+    // headline's blocks stay ONE parse launch (every piece costs a whole per-block chain), pieces only when the records do not fit
+    return in_pieces(s, n, 0, fourmc_lz4_fast_work_bytes, [&](uint32_t b0, uint32_t m, void* work) -> int {
+        HIP_TRY(fourmc_launch_lz4_encode_fast(d_src, d_dst, d_blocks + b0, m, container_mode, work, s)); return FOURMC_OK; });
 }
 
 int fourmc_gpu_lz4_compress_fast(const void* d_src, void* d_dst, fourmc_block* d_blocks, uint32_t n, void* stream)

@@ -54,8 +54,14 @@ hipError_t fourmc_launch_lz4_parse(const void* d_src, const void* d_dst, fourmc_
                                    int container_mode, void* d_work, hipStream_t stream);
 hipError_t fourmc_launch_lz4_exec(const void* d_src, void* d_dst, fourmc_block* d_blocks, uint32_t n,
                                   const void* d_work, hipStream_t stream);
+/* LZ4 fast encode, the reference's parse (lz4_encode.hip): the parse writes sequence records to d_work, then the emit kernel
+ * (lz4_emit.hip) writes the payloads on the same stream.  d_work holds fourmc_lz4_fast_work_bytes(n) bytes */
+uint32_t   fourmc_lz4_fast_reccap(void);
+size_t     fourmc_lz4_fast_work_bytes(uint32_t n);
 hipError_t fourmc_launch_lz4_encode_fast(const void* d_src, void* d_dst, fourmc_block* d_blocks,
-                                         uint32_t n, int container_mode, hipStream_t stream);
+                                         uint32_t n, int container_mode, void* d_work, hipStream_t stream);
+hipError_t fourmc_launch_lz4_emit(const void* d_src, void* d_dst, const fourmc_block* d_blocks, uint32_t n,
+                                  const void* d_work, uint32_t reccap, hipStream_t stream);
 size_t     fourmc_lz4_par_work_bytes(uint32_t n);
 hipError_t fourmc_launch_lz4_encode_par(const void* d_src, void* d_dst, fourmc_block* d_blocks, uint32_t n,
                                         int container_mode, void* d_work, hipStream_t stream);

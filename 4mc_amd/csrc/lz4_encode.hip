@@ -16,9 +16,9 @@
 //   * "dense window": lane l takes position sp+l whatever role the walk will give it, prepares
 //     candidate / 4-byte test / match extents against the table as it stands; lanes sharing a
 //     slot are found on the table itself (lane tags, atomic max); a scalar walk of one readlane
-//     per sequence chooses the hit lanes; sizes, positions and all bytes of the chosen sequences
-//     are then written by all lanes at once, and the visited lanes enter the table (latest
-//     position of a slot wins);
+//     per sequence chooses the hit lanes; sizes and output positions of the chosen sequences are
+//     then computed by all lanes at once and their records (lz4emit.h) written in one store, and the
+//     visited lanes enter the table (latest position of a slot wins);
 //   * "sparse batch": lane l speculatively executes probe k0+l of the running search at its
 //     strided position (block start / end, long searches); a ballot finds the FIRST lane (serial
 //     order) that hits or runs into the end-of-block limit, only lanes before it commit their
@@ -26,12 +26,15 @@
 //     earlier one - an LDS atomic-min scoreboard; the cut lane becomes lane 0 of the next batch;
 //   * whatever the registers do not hold (long matches, long catch-up, output nearly full) goes
 //     through one general sequence routine with wave-wide compares and copies.
-// Per block HBM traffic: n bytes read (+ candidate re-reads that hit L1/L2), csize written.
+// The parse never writes the payload: lz4_emit.hip turns the records into bytes after it, outside the chain.
+// Per block HBM traffic: n bytes read (+ candidate re-reads that hit L1/L2), 16 bytes per sequence of records written.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "fourmc_gpu.h"
 #include "kernels.h"
 #include "devenc.h"
+#include "lz4emit.h"
 
 namespace {
 
@@ -83,7 +86,7 @@ template <bool U32TAB> __device__ __forceinline__ uint32_t hash_of(uint64_t v)
 
 template <bool U32TAB>
 __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, const int cap,
-                                uint32_t* tab32, uint32_t* score, const int lane)
+                                uint32_t* tab32, uint32_t* score, uint4* rec, const uint32_t reccap, uint32_t& nrec, const int lane)
 {
     uint16_t* tab16 = reinterpret_cast<uint16_t*>(tab32);
 #ifdef K2_PROF   // one-off phase profile (tools/k2_phases.py builds a side library with -DK2_PROF): cycles per phase
@@ -96,6 +99,7 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
 #endif
     const bool limited = cap < n + n / 255 + 16;                       // lz4.c:1352
     uint32_t op = 0, anchor = 0;
+    uint32_t rc = 0;                                                    // records written (lz4emit.h): the parse never writes dst
 
     for (int i = lane; i < (1 << kHashLog); i += 64) tab32[i] = 0;     // LZ4_initStream
     for (int i = lane; i < kScore; i += 64) score[i] = 0xFFFFFFFFu;
@@ -120,12 +124,12 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
 
         // One sequence (lz4.c:1080-1200): catch-up, literals, offset, match length.  `ip`/`cand` are the hit; `back`
         // (0..4) bytes before them and `fwd` bytes after ip+4 are already known equal, `*_more` says the comparison
-        // has to go on in memory.  Literals at [wsp, wsp+64) come from `wbyte` (lane l holds src[wsp+l]).
+        // has to go on in memory.  Writes the sequence's record and advances `op` by its size.
         // Returns 0 and the end of the match in ip_out, 1 = go to the last literals, 2 = output full.
         auto sequence = [&](uint32_t ip, uint32_t cand, const bool rt_hit, const uint32_t back, const bool back_more,
-                            uint32_t fwd, const bool fwd_more, const uint32_t wsp, const uint32_t wbyte, uint32_t& ip_out) -> int {
-            uint32_t token_pos, tok;
-            if (rt_hit) { token_pos = op++; tok = 0; }                 // lz4.c:1250-1256: zero literals, straight to _next_match
+                            uint32_t fwd, const bool fwd_more, uint32_t& ip_out) -> int {
+            uint32_t token_pos, lit = 0;
+            if (rt_hit) token_pos = op++;                              // lz4.c:1250-1256: zero literals, straight to _next_match
             else {
                 const uint32_t maxback = min(ip - anchor, cand);
                 uint32_t b = min(back, maxback);
@@ -142,20 +146,14 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 b = U(b);
                 ip = U(ip - b); cand = U(cand - b);
                 fwd += b;                                              // everything in [new ip, old ip + 4 + fwd) is equal
-                const uint32_t lit = ip - anchor;                      // literals (lz4.c:1083-1107)
+                lit = ip - anchor;                                     // literals (lz4.c:1083-1107)
                 token_pos = op++;
                 if (limited && op + lit + (2 + 1 + kLastLit) + lit / 255 > uint32_t(cap)) return 2;
-                if (lit >= 15) { tok = 0xF0; op += emit_len(dst + op, lit - 15, lane); }
-                else tok = lit << 4;
-                if (wsp != 0xFFFFFFFFu && ip > wsp && ip <= wsp + 64) {
-                    if (anchor < wsp) copy_bytes(dst + op, src + anchor, wsp - anchor, lane);
-                    const uint32_t q = wsp + lane;
-                    if (q >= anchor && q < ip) dst[op + (q - anchor)] = uint8_t(wbyte);
-                } else copy_bytes(dst + op, src + anchor, lit, lane);
+                if (lit >= 15) op += (lit - 15) / 255 + 1;
                 op += lit;
             }
             // _next_match (lz4.c:1109-1200)
-            const uint32_t off = ip - cand, off_pos = op;
+            const uint32_t off = ip - cand;
             op += 2;
             uint32_t mcode = fwd;
             if (fwd_more) {
@@ -186,14 +184,9 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
             mcode = U(mcode);
             ip = U(ip + mcode + 4);
             if (limited && op + (1 + kLastLit) + (mcode + 240) / 255 > uint32_t(cap)) return 2;
-            uint32_t tok_add;
-            if (mcode >= 15) { tok_add = 15; op += emit_len(dst + op, mcode - 15, lane); }
-            else tok_add = mcode;
-            if (lane < 3) {                                            // token, offset low, offset high: one store
-                const uint32_t at = lane == 0 ? token_pos : off_pos + uint32_t(lane) - 1;
-                const uint32_t v  = lane == 0 ? tok + tok_add : (lane == 1 ? off : off >> 8);
-                dst[at] = uint8_t(v);
-            }
+            if (mcode >= 15) op += (mcode - 15) / 255 + 1;
+            if (lane == 0) rec[rc] = make_uint4(token_pos, anchor, lit, off);
+            rc = U(rc + 1);
             anchor = ip; op = U(op);
             ip_out = ip;
             return ip >= lim ? 1 : 0;
@@ -203,8 +196,15 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
         // whose ip-2 refill and immediate re-test (lz4.c:1207-1259) are still owed and whose search starts at sp+1;
         // otherwise it is probe number k0 of the running search.
         uint32_t sp = 1, k0 = 0; bool retest = false;
-        uint32_t pw_sp = 0xFFFFFFFFu, pwbyte = 0;                      // previous dense window: start, and the byte each lane held
+        uint32_t pw_sp = 0xFFFFFFFFu;                                   // previous dense window: start
         for (;;) {
+            if (rc > reccap - kRecSlack) {
+                // the record area is full (only a block above FOURMC_BLOCKSIZE gets here): its bytes go out now
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                for (uint32_t i0 = 0; i0 < rc; i0 += 64) emit_records(rec, i0, rc, anchor, src, dst, lane);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                rc = 0;
+            }
             if (sp >= 4 && sp + 132 <= un && k0 <= 32) {
                 // ------------------------------------------------------------ dense window
                 // Probes 0..65 of a search are one byte apart, so around a fresh search the parse walks consecutive
@@ -299,7 +299,6 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 const bool hitA = second && wpred == q0.d1;
                 const unsigned long long m_cond = __ballot(second && (hitA || hit));
                 const unsigned long long m_hit = __ballot(hit) & ~m_cond, m_dirty = __ballot(dirty), m_slow = __ballot(hit && slow);
-                const uint32_t wbyte = q0.d1;
                 K2PH(pt_gather);
                 // The first sequence may own literals of the previous window: they are still in registers if that was
                 // a dense window too (pw_sp); anything older goes through the general path.  Near the end of the
@@ -386,7 +385,8 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                     }
                     K2PH(pt_ext);
                     if (sel) {
-                        // sizes, positions and bytes of the chosen sequences, all at once (lz4.c:1080-1200)
+                        // sizes, output positions and records of the chosen sequences, all at once (lz4.c:1080-1200): one
+                        // store of the chosen lanes, record k of the window at rc + k
                         const bool mine = (sel >> lane) & 1;
                         const unsigned long long below = sel & ~(~0ull << lane);
                         const int P = below ? 63 - __builtin_clzll(below) : 0;
@@ -394,34 +394,10 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                         const int myanc = below ? endP : anc0;           // my anchor: the end of the sequence chosen before me
                         const uint32_t b = uint32_t(min(int((info >> 8) & 7), lane - myanc));
                         const uint32_t lit = uint32_t(lane - myanc) - b, mc = (info & 255) - uint32_t(lane) - 4 + b;
-                        const uint32_t xl = lit >= 15 ? 1u : 0u;
-                        const uint32_t size = mine ? 3 + lit + xl + (mc >= 15 ? 1u : 0u) : 0u;
+                        const uint32_t size = mine ? 3 + lit + (lit >= 15 ? 1u : 0u) + (mc >= 15 ? 1u : 0u) : 0u;
                         const uint32_t incl = scan_add(size);
-                        const uint32_t opb = op + incl - size;
-                        const uint32_t pk = uint32_t(myanc + 128) | (b << 9) | (xl << 12);
-                        // a literal lane belongs to the next chosen hit lane E at or after it, if it lies in that
-                        // sequence's [anchor, ip)
-                        const unsigned long long ahead = sel >> lane;
-                        const int E = lane + (ahead ? __builtin_ctzll(ahead) : 0);
-                        const uint32_t opbE = __shfl(opb, E), pkE = __shfl(pk, E);
-                        const int aE = int(pkE & 511) - 128, ipnE = E - int((pkE >> 9) & 7);
-                        if (ahead && lane >= aE && lane < ipnE) dst[opbE + 1 + ((pkE >> 12) & 1) + uint32_t(lane - aE)] = uint8_t(wbyte);
-                        const int E1 = __builtin_ctzll(sel);
-                        const int a1 = int(rl(pk, E1) & 511) - 128;
-                        if (a1 < 0) {                                   // literals still held by the previous window's lanes
-                            const uint32_t pk1 = rl(pk, E1), opb1 = rl(opb, E1);
-                            const int pl = int(pw_sp - sp0) + lane, ipn1 = E1 - int((pk1 >> 9) & 7);
-                            if (pl >= a1 && pl < min(0, ipn1)) dst[opb1 + 1 + ((pk1 >> 12) & 1) + uint32_t(pl - a1)] = uint8_t(pwbyte);
-                        }
-                        if (mine) {
-                            const uint32_t off = pos - c;
-                            uint32_t o = opb;
-                            dst[o++] = uint8_t((min(lit, 15u) << 4) | min(mc, 15u));
-                            if (xl) dst[o++] = uint8_t(lit - 15);
-                            o += lit;
-                            dst[o] = uint8_t(off); dst[o + 1] = uint8_t(off >> 8);
-                            if (mc >= 15) dst[o + 2] = uint8_t(mc - 15);
-                        }
+                        if (mine) rec[rc + uint32_t(__popcll(below))] = make_uint4(op + incl - size, sp0 + uint32_t(myanc), lit, pos - c);
+                        rc = U(rc + uint32_t(__popcll(sel)));
                         op = U(op + rl(incl, 63));
                         anchor = sp0 + uint32_t(anc);
                         selw |= sel; any = true; fresh = false;
@@ -488,7 +464,7 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                         const uint32_t inf = s_inf;
                         uint32_t ip;
                         status = sequence(sp0 + uint32_t(e), s_cand, any && e == anc, (inf >> 12) & 7, (inf >> 15) & 1,
-                                          (inf & 255) - uint32_t(e) - 4, (inf >> 16) & 1, sp0, wbyte, ip);
+                                          (inf & 255) - uint32_t(e) - 4, (inf >> 16) & 1, ip);
                         if (status) break;
                         any = true; fresh = false;
                         if (ip - sp0 >= 64) {
@@ -515,7 +491,7 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                         else for (;;) { tab16[h] = uint16_t(pos); asm volatile("" ::: "memory"); if (uint32_t(tab16[h]) >= pos) break; }
                     }
                 }
-                pw_sp = sp0; pwbyte = wbyte;
+                pw_sp = sp0;
                 sp = U(sp); k0 = U(k0);
                 K2PH(pt_match);
                 continue;
@@ -583,7 +559,7 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                         fwd_more = !((eq < 8) || (room <= 8));
                     }
                     uint32_t ipn;
-                    const int status = sequence(ip, cand, rt && e == 0, back, back_more, fwd, fwd_more, 0xFFFFFFFFu, 0, ipn);
+                    const int status = sequence(ip, cand, rt && e == 0, back, back_more, fwd, fwd_more, ipn);
                     if (status == 2) return 0;
                     if (status == 1) goto last_literals;
                     sp = U(ipn); k0 = 0; retest = true;
@@ -602,29 +578,25 @@ last_literals:
     {
         const uint32_t run = uint32_t(n) - anchor;                      // lz4.c:1266-1293
         if (limited && op + run + 1 + (run + 255 - 15) / 255 > uint32_t(cap)) return 0;
-        if (run >= 15) {
-            if (lane == 0) dst[op] = 0xF0;
-            op++;
-            op += emit_len(dst + op, run - 15, lane);
-        } else {
-            if (lane == 0) dst[op] = uint8_t(run << 4);
-            op++;
-        }
-        copy_bytes(dst + op, src + anchor, run, lane);
-        op += run;
+        if (lane == 0) rec[rc] = make_uint4(op, anchor, run, kRecLast);
+        rc++;
+        op += 1 + (run >= 15 ? (run - 15) / 255 + 1 : 0) + run;
     }
 #ifdef K2_PROF
     if (lane == 0 && n == (4 << 20)) { uint64_t* c = reinterpret_cast<uint64_t*>(dst + n - 32); c[0] = pt_search; c[1] = pt_ext; c[2] = pt_match; uint64_t* d = reinterpret_cast<uint64_t*>(dst + n - 128); d[0] = pt_cur; d[1] = pt_tab; d[2] = pt_gather; d[3] = pt_emit; d[4] = pt_nwin; d[5] = pt_nseq; d[6] = pt_nslow; uint64_t* f = reinterpret_cast<uint64_t*>(dst + n - 192); f[0] = pt_none; f[1] = pt_cross; f[2] = pt_dcut; f[3] = pt_scut; f[4] = pt_prep; f[5] = pt_gen; f[6] = pt_nit; }
 #endif
+    nrec = rc;
     return int(op);
 }
 
 // container_mode = 0: result = LZ4_compress_default(src, dst, src_len, dst_cap).
 // container_mode = 1: one iteration of fourMCcompressFilename's loop (native/4mc.c:301-329):
 //   capacity src_len-1; a result <= 0 stores the block raw (payload = input, result = src_len).
+// The payload bytes are written by lz4_emit.hip from the records this kernel leaves in `work` (lz4emit.h): per block
+// the record count (0: nothing to write, kRecRawCopy: store the input raw), then the block's record area.
 __global__ __launch_bounds__(64)
 void lz4_encode_fast_kernel(const uint8_t* __restrict__ src_base, uint8_t* dst_base,
-                            fourmc_block* blocks, uint32_t nblocks, int container_mode)
+                            fourmc_block* blocks, uint32_t nblocks, int container_mode, uint8_t* work, uint32_t reccap)
 {
     __shared__ uint32_t tab[1 << kHashLog];
     __shared__ uint32_t score[kScore];
@@ -633,32 +605,50 @@ void lz4_encode_fast_kernel(const uint8_t* __restrict__ src_base, uint8_t* dst_b
     const fourmc_block blk = uniform_block(blocks[b]);
     const uint8_t* src = src_base + blk.src_off;
     uint8_t* dst = dst_base + blk.dst_off;
+    uint4* rec = reinterpret_cast<uint4*>(work + lz4rec_count_bytes(nblocks) + size_t(b) * lz4rec_area_bytes(reccap));
     const int n = int(blk.src_len);
     const int cap = container_mode ? n - 1 : int(blk.dst_cap);
     const int lane = threadIdx.x;
     int r;
+    uint32_t nrec = 0;
     if (uint32_t(n) > 0x7E000000u) r = 0;                               // lz4.c:1324
     else if (n == 0) {                                                  // lz4.c:1325-1335
         const bool limited = cap < 16;
         if (limited && cap <= 0) r = 0; else { if (lane == 0) dst[0] = 0; r = 1; }
     }
-    else if (n < kSmallLim) r = lz4_encode_block<false>(src, dst, n, cap, tab, score, lane);
-    else                    r = lz4_encode_block<true>(src, dst, n, cap, tab, score, lane);
-    if (container_mode && r <= 0) {
-        copy_bytes(dst, src, uint32_t(n), lane);
-        r = n;
-    }
-    if (lane == 0) blocks[b].result = r;
+    else if (n < kSmallLim) r = lz4_encode_block<false>(src, dst, n, cap, tab, score, rec, reccap, nrec, lane);
+    else                    r = lz4_encode_block<true>(src, dst, n, cap, tab, score, rec, reccap, nrec, lane);
+    if (r <= 0) nrec = 0;
+    if (container_mode && r <= 0) { nrec = kRecRawCopy; r = n; }
+    if (lane == 0) { blocks[b].result = r; reinterpret_cast<uint32_t*>(work)[b] = nrec; }
 }
 
 } // namespace
 
+extern "C" uint32_t fourmc_lz4_fast_reccap(void)
+{
+    // records per block: a block of FOURMC_BLOCKSIZE bytes has at most n/4 + 1 sequences and never drains its area;
+    // FOURMC_LZ4_RECORDS=N (test aid, >= 2 * kRecSlack) makes the areas smaller so that the drain inside the parse runs
+    static const uint32_t cap = [] {
+        const char* e = getenv("FOURMC_LZ4_RECORDS");
+        const uint32_t v = e ? uint32_t(strtoul(e, nullptr, 10)) : 0u;
+        return v >= 2 * kRecSlack ? v : FOURMC_BLOCKSIZE / 4 + 2 * kRecSlack;
+    }();
+    return cap;
+}
+
+extern "C" size_t fourmc_lz4_fast_work_bytes(uint32_t n)
+{ return lz4rec_count_bytes(n) + size_t(n) * lz4rec_area_bytes(fourmc_lz4_fast_reccap()); }
+
 extern "C" hipError_t fourmc_launch_lz4_encode_fast(const void* d_src, void* d_dst, fourmc_block* d_blocks,
-                                                    uint32_t n, int container_mode, hipStream_t stream)
+                                                    uint32_t n, int container_mode, void* d_work, hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
+    if (d_work == nullptr) return hipErrorInvalidValue;
+    const uint32_t reccap = fourmc_lz4_fast_reccap();
     hipLaunchKernelGGL(lz4_encode_fast_kernel, dim3(n), dim3(64), 0, stream,
                        static_cast<const uint8_t*>(d_src), static_cast<uint8_t*>(d_dst), d_blocks, n,
-                       container_mode);
-    return hipGetLastError();
+                       container_mode, static_cast<uint8_t*>(d_work), reccap);
+    if (hipError_t e = hipGetLastError()) return e;
+    return fourmc_launch_lz4_emit(d_src, d_dst, d_blocks, n, d_work, reccap, stream);
 }

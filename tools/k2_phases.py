@@ -30,4 +30,4 @@ for b in range(12):
     p.decode_blocks(stage, out, dec); torch.cuda.synchronize()
     ds.record(); p.decode_blocks(stage, out, dec); de.record(); torch.cuda.synchronize()
     print(f"        K1 dec {ds.elapsed_time(de):7.2f} ms")
-    print(f"{names[b]:7s} csize {r:8d} enc {s.elapsed_time(e):8.2f} ms   dense: cursor {100*d[0]/tot:4.1f}% table {100*d[1]/tot:4.1f}% gather {100*d[2]/tot:4.1f}% prep {100*f[4]/tot:4.1f}% general {100*f[5]/tot:4.1f}% walk {100*c[1]/tot:4.1f}% emit {100*d[3]/tot:4.1f}% commit {100*c[2]/tot:4.1f}% | sparse {100*c[0]/tot:4.1f}%  windows {int(d[4])} seq {int(d[5])} slow-seq {int(d[6])} | window ends: none {int(f[0])} cross {int(f[1])} dirty-cut {int(f[2])} stride-cut {int(f[3])} inner-iterations {int(f[6])} total-clk {tot:.3g}")
+    print(f"{names[b]:7s} csize {r:8d} enc {s.elapsed_time(e):8.2f} ms   dense: cursor {100*d[0]/tot:4.1f}% table {100*d[1]/tot:4.1f}% gather {100*d[2]/tot:4.1f}% prep {100*f[4]/tot:4.1f}% general {100*f[5]/tot:4.1f}% walk {100*c[1]/tot:4.1f}% records {100*d[3]/tot:4.1f}% commit {100*c[2]/tot:4.1f}% | sparse {100*c[0]/tot:4.1f}%  windows {int(d[4])} seq {int(d[5])} slow-seq {int(d[6])} | window ends: none {int(f[0])} cross {int(f[1])} dirty-cut {int(f[2])} stride-cut {int(f[3])} inner-iterations {int(f[6])} total-clk {tot:.3g}")
