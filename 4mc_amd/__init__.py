@@ -20,6 +20,7 @@ from .binding import (  # noqa: F401
 from .engine import (  # noqa: F401
     lz4_decompress, zstd_decompress, zstd_compress, lz4_compress_fast, lz4_compress_hc, lz4_compress_mc, xxh32, encode_blocks, decode_blocks, pack_image, DeviceBatch, release_workspaces,
     compress_image, decompress_image, image_bound, image_parse_stats, image_index, image_decode_blocks, image_read, ImageWriter,
+    ImageReader,
 )
 from .container import (  # noqa: F401
     frame_header, frame_footer, parse_footer, assemble_container, split_container, shard_range,

@@ -111,6 +111,10 @@ _GPU_API = {
     "fourmc_gpu_image_writer_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "fourmc_gpu_image_writer_finish": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_writer_abort": (None, [C.c_void_p]),
+    "fourmc_gpu_image_reader_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "fourmc_gpu_image_reader_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "fourmc_gpu_image_reader_finish": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_image_reader_abort": (None, [C.c_void_p]),
     "fourmc_LZ4_compressBound": (C.c_int, [C.c_int]),
     "fourmc_LZ4_compress_default": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "fourmc_LZ4_compressMC": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

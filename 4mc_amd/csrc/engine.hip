@@ -687,6 +687,155 @@ void fourmc_gpu_image_writer_abort(fourmc_image_writer* w)
     if (w) writer_free(w, false);
 }
 
+// ------------------------------------------------------------------------ streaming image reader (image.hip)
+// One device allocation per reader, made by begin and freed by finish / abort: the walk's state, the status, the descriptors and
+// header offsets of one batch, the copy pieces of one walk and batch_blocks staging slots (64 bytes of slack behind the last one
+// for the decoders' read-ahead).  A block cut by the end of a chunk waits in its own slot, so there is no separate carry slot.
+}   // extern "C"
+struct fourmc_image_reader {
+    hipStream_t s;
+    uint8_t* dst;
+    uint64_t cap;
+    uint32_t magic;
+    int codec;
+    uint32_t batch;                  // blocks per decode batch
+    uint64_t total;                  // bytes appended so far: N
+    uint32_t pending;                // complete blocks waiting in the current batch
+    bool final_;                     // the framing verdict is final: later appends only count
+    int err;                         // the first failure: every later call returns it
+    void* mem;
+    fourmc_image_rd_state* d_st;
+    fourmc_image_status* d_status;
+    fourmc_block* d_desc;
+    uint64_t* d_at;
+    fourmc_image_piece* d_pc;
+    uint8_t* d_stage;
+};
+namespace {
+
+// the current batch: the container decode from staging (XXH32 check, then the codec), then the fold into the running verdict
+int reader_decode(fourmc_image_reader* r)
+{
+    if (!r->pending) return FOURMC_OK;
+    if (int e = fourmc_gpu_4mc_decode_blocks(r->d_stage, r->dst, r->d_desc, r->pending, r->codec, r->s)) return e;
+    HIP_TRY(fourmc_launch_image_rd_fold(r->d_desc, r->d_at, r->pending, r->d_st, r->s));
+    r->pending = 0;
+    return FOURMC_OK;
+}
+
+// One walk per batch the chunk fills, each read back once: the gather of its pieces, and the decode when its batch is full.
+int reader_append(fourmc_image_reader* r, const uint8_t* chunk, uint64_t bytes)
+{
+    uint64_t at = 0;
+    for (;;) {
+        HIP_TRY(fourmc_launch_image_rd_walk(chunk, bytes, at, r->d_st, r->magic, r->cap, r->batch, r->d_stage, r->d_desc, r->d_at,
+                                            r->d_pc, r->s));
+        struct { uint64_t cpos; uint32_t batch_n, npieces, max_piece, final_; } h;
+        static_assert(sizeof h == 24 && offsetof(fourmc_image_rd_state, final_) == 20, "the read-back head of the walk's state");
+        HIP_TRY(hipMemcpyAsync(&h, r->d_st, sizeof h, hipMemcpyDeviceToHost, r->s));
+        HIP_TRY(hipStreamSynchronize(r->s));
+        HIP_TRY(fourmc_launch_image_rd_gather(r->d_pc, h.npieces, h.max_piece, r->s));
+        r->pending = h.batch_n;
+        r->final_ = h.final_ != 0;
+        if (r->pending == r->batch) { if (int e = reader_decode(r)) return e; }
+        if (r->final_ || h.cpos >= bytes) return FOURMC_OK;
+        at = h.cpos;
+    }
+}
+
+int reader_finish(fourmc_image_reader* r, fourmc_image_status* status)
+{
+    if (int e = ensure_device()) return e;
+    if (int e = reader_decode(r)) return e;
+    HIP_TRY(fourmc_launch_image_rd_finish(r->d_st, r->total, r->cap, r->d_status, r->s));
+    HIP_TRY(hipMemcpyAsync(status, r->d_status, sizeof *status, hipMemcpyDeviceToHost, r->s));
+    HIP_TRY(hipStreamSynchronize(r->s));
+    return FOURMC_OK;
+}
+
+void reader_free(fourmc_image_reader* r, bool synced)
+{
+    if (r->mem) {
+        if (!synced) (void)hipStreamSynchronize(r->s);
+        (void)hipFree(r->mem);
+        (void)hipGetLastError();
+    }
+    delete r;
+}
+
+} // namespace
+extern "C" {
+
+int fourmc_gpu_image_reader_begin(fourmc_image_reader** out, void* d_dst, uint64_t dst_cap, uint32_t magic, uint32_t batch_blocks,
+                                  void* stream)
+{
+    if (!out) { snprintf(g_err, sizeof g_err, "image_reader_begin: null reader"); return FOURMC_EINVAL; }
+    *out = nullptr;
+    if (magic != FOURMC_MAGIC_4MC && magic != FOURMC_MAGIC_4MZ) { snprintf(g_err, sizeof g_err, "magic 0x%08x is neither 4mc nor 4mz", magic); return FOURMC_EINVAL; }
+    if (!d_dst) { snprintf(g_err, sizeof g_err, "image_reader_begin: null destination"); return FOURMC_EINVAL; }
+    if (int r = ensure_device()) return r;
+    const uint32_t batch = batch_blocks ? batch_blocks : 512;
+    const size_t o_status = align256(sizeof(fourmc_image_rd_state)), o_desc = o_status + align256(sizeof(fourmc_image_status));
+    const size_t o_at = o_desc + align256(size_t(batch) * sizeof(fourmc_block)), o_pc = o_at + align256(size_t(batch) * 8);
+    const size_t o_stage = o_pc + align256((size_t(batch) + 1) * sizeof(fourmc_image_piece));
+    const size_t bytes = o_stage + size_t(batch) * FOURMC_BLOCKSIZE + 256;
+    auto* r = new fourmc_image_reader();
+    r->s = static_cast<hipStream_t>(stream);
+    r->dst = static_cast<uint8_t*>(d_dst); r->cap = dst_cap; r->magic = magic;
+    r->codec = magic == FOURMC_MAGIC_4MZ ? FOURMC_CODEC_ZSTD : FOURMC_CODEC_LZ4_FAST;
+    r->batch = batch;
+    const hipError_t me = hipMalloc(&r->mem, bytes);
+    if (me != hipSuccess) {
+        (void)hipGetLastError(); r->mem = nullptr;
+        delete r;
+        if (me == hipErrorOutOfMemory) { snprintf(g_err, sizeof g_err, "hipMalloc(%zu bytes of image reader): out of memory", bytes); return FOURMC_ENOMEM; }
+        return fail_hip(me, "hipMalloc(image reader)");
+    }
+    char* base = static_cast<char*>(r->mem);
+    r->d_st = reinterpret_cast<fourmc_image_rd_state*>(base);
+    r->d_status = reinterpret_cast<fourmc_image_status*>(base + o_status);
+    r->d_desc = reinterpret_cast<fourmc_block*>(base + o_desc);
+    r->d_at = reinterpret_cast<uint64_t*>(base + o_at);
+    r->d_pc = reinterpret_cast<fourmc_image_piece*>(base + o_pc);
+    r->d_stage = reinterpret_cast<uint8_t*>(base + o_stage);
+    // the walk starts at the file header of the first stream, nothing counted
+    const hipError_t e = hipMemsetAsync(r->d_st, 0, sizeof(fourmc_image_rd_state), r->s);
+    if (e != hipSuccess) { const int rr = fail_hip(e, "image_reader_begin: state"); reader_free(r, false); return rr; }
+    *out = r;
+    return FOURMC_OK;
+}
+
+int fourmc_gpu_image_reader_append(fourmc_image_reader* r, const void* d_chunk, uint64_t bytes)
+{
+    if (!r) { snprintf(g_err, sizeof g_err, "image_reader_append: null reader"); return FOURMC_EINVAL; }
+    if (r->err) { snprintf(g_err, sizeof g_err, "image_reader_append: the reader failed earlier (%d)", r->err); return r->err; }
+    if (bytes && !d_chunk) { snprintf(g_err, sizeof g_err, "image_reader_append: null chunk"); return FOURMC_EINVAL; }
+    if (r->total + bytes < r->total) { snprintf(g_err, sizeof g_err, "image_reader_append: image length overflows"); return FOURMC_EINVAL; }
+    if (bytes && !r->final_) {                       // once the verdict is final, appends only count toward N
+        int e = ensure_device();
+        if (!e) e = reader_append(r, static_cast<const uint8_t*>(d_chunk), bytes);
+        if (e) return r->err = e;
+    }
+    r->total += bytes;
+    return FOURMC_OK;
+}
+
+int fourmc_gpu_image_reader_finish(fourmc_image_reader* r, fourmc_image_status* status)
+{
+    if (!r) { snprintf(g_err, sizeof g_err, "image_reader_finish: null reader"); return FOURMC_EINVAL; }
+    int e = r->err;
+    if (e) snprintf(g_err, sizeof g_err, "image_reader_finish: the reader failed earlier (%d)", e);
+    else if (!status) { snprintf(g_err, sizeof g_err, "image_reader_finish: null status"); e = FOURMC_EINVAL; }
+    else e = reader_finish(r, status);
+    reader_free(r, e == FOURMC_OK);
+    return e;
+}
+
+void fourmc_gpu_image_reader_abort(fourmc_image_reader* r)
+{
+    if (r) reader_free(r, false);
+}
+
 const char* fourmc_gpu_image_reason_text(int reason)
 {
     switch (reason) {                       // fourmc_file.c: decode_stream, the writer thread (wjob_main)

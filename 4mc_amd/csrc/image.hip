@@ -15,6 +15,8 @@
 // runs on from the offset the previous batch left in the writer's device index.
 // Random access (second half): the footer index of a single stream, block-range decodes and byte-range reads, each with the
 // verdict fourmc_file_decode_blocks (fourmc_file.c) reaches on the same bytes as a file.
+// Streaming reads (last part): the walk restated to stop at the end of each appended chunk and resume at the next, the gather of
+// payload bytes into staging slots, the fold of each decoded batch and the finish that decides what waited for more bytes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fourmc_gpu.h"
@@ -211,6 +213,29 @@ void image_parse_fast_kernel(const uint8_t* __restrict__ img, uint64_t N, uint32
     }
 }
 
+// decode_stream's per-field checks (fourmc_file.c:473-592), shared by the whole-image walk and the streaming reader's walk.  Each
+// one is decided once the bytes it reads are there; the checks of "unreadable" kinds (N - p < k) are the callers'.
+// the file header after its magic: version, then the header checksum (computed over its first 8 bytes)
+__device__ __forceinline__ int32_t file_header_verdict(uint32_t version, uint32_t stored, uint32_t computed)
+{
+    if (version != 1) return FOURMC_IMG_VERSION;
+    if (stored != computed) return FOURMC_IMG_HEADER_CHECKSUM;
+    return FOURMC_IMG_OK;
+}
+__device__ __forceinline__ bool end_mark(uint32_t usize, uint32_t csize, uint32_t sum) { return (usize | csize | sum) == 0; }
+__device__ __forceinline__ bool csize_beyond(uint32_t csize) { return csize > kBlock; }
+__device__ __forceinline__ bool usize_beyond(uint32_t usize, uint32_t csize) { return usize != csize && usize > kBlock; }
+// an oversized usize ends with one of two messages: the payload's XXH32 decides (fourmc_file.c:521-525)
+__device__ __forceinline__ int32_t usize_verdict(uint32_t payload_hash, uint32_t sum)
+{ return payload_hash != sum ? FOURMC_IMG_BLOCK_CHECKSUM : FOURMC_IMG_USIZE_BEYOND; }
+// the footer once all fsz bytes are there: its checksum (over fsz - 4 bytes), then its version
+__device__ __forceinline__ int32_t footer_verdict(uint32_t computed, uint32_t stored, uint32_t version)
+{
+    if (computed != stored) return FOURMC_IMG_FOOTER_CHECKSUM;
+    if (version != 1) return FOURMC_IMG_FOOTER_VERSION;
+    return FOURMC_IMG_OK;
+}
+
 // The walk: decode_stream (fourmc_file.c:473-592) and decompress_file's loop over concatenated streams on one lane, the checks in
 // their order.  That loop (`do got = decode_stream(..); while (got)`, fourmc_file.c:606-609, native/4mc.c:908-912) ends after a
 // stream that decoded 0 bytes, whatever follows it: the walk ends cleanly after a stream whose blocks add up to 0 usize.  count mode (blocks NULL): nothing to do when the fast path has accepted the image; else the summary.  fill mode:
@@ -231,8 +256,7 @@ void image_parse_walk_kernel(const uint8_t* __restrict__ img, uint64_t N, uint32
         if (N - p < 4)                     { reason = FOURMC_IMG_MAGIC_UNREADABLE; break; }
         if (be32(img + p) != magic)        { reason = FOURMC_IMG_NOT_4MC; break; }
         if (N - p < 12)                    { reason = FOURMC_IMG_HEADER_UNREADABLE; break; }
-        if (be32(img + p + 4) != 1)        { reason = FOURMC_IMG_VERSION; break; }
-        if (be32(img + p + 8) != xxh32_lane(img + p, 8, 0)) { reason = FOURMC_IMG_HEADER_CHECKSUM; break; }
+        if ((reason = file_header_verdict(be32(img + p + 4), be32(img + p + 8), xxh32_lane(img + p, 8, 0)))) break;
         p += 12; streams++;
         const uint64_t stream_total0 = total;
         for (;;) {
@@ -240,13 +264,10 @@ void image_parse_walk_kernel(const uint8_t* __restrict__ img, uint64_t N, uint32
             if (N - p < 12)                { reason = FOURMC_IMG_BLOCK_SIZE_UNREADABLE; break; }
             const uint32_t usize = be32(img + p), csize = be32(img + p + 4), sum = be32(img + p + 8);
             p += 12;
-            if ((usize | csize | sum) == 0) break;
-            if (csize > kBlock)            { reason = FOURMC_IMG_CSIZE_BEYOND; break; }
+            if (end_mark(usize, csize, sum)) break;
+            if (csize_beyond(csize))       { reason = FOURMC_IMG_CSIZE_BEYOND; break; }
             if (N - p < csize)             { reason = FOURMC_IMG_DATA_UNREADABLE; break; }
-            if (usize != csize && usize > kBlock) {
-                reason = xxh32_lane(img + p, csize, 0) != sum ? FOURMC_IMG_BLOCK_CHECKSUM : FOURMC_IMG_USIZE_BEYOND;
-                break;
-            }
+            if (usize_beyond(usize, csize)) { reason = usize_verdict(xxh32_lane(img + p, csize, 0), sum); break; }
             if (blocks) {
                 fourmc_block d;
                 d.src_off = p; d.dst_off = total; d.src_len = csize; d.dst_cap = usize; d.result = 0; d.xxh32 = sum;
@@ -259,8 +280,7 @@ void image_parse_walk_kernel(const uint8_t* __restrict__ img, uint64_t N, uint32
         if (N - p < 4)                     { reason = FOURMC_IMG_FOOTER_UNREADABLE; break; }
         const uint32_t fsz = be32(img + p);
         if (fsz < 8 || N - p < fsz)        { reason = FOURMC_IMG_FOOTER_SHORT; break; }
-        if (xxh32_lane(img + p, fsz - 4, 0) != be32(img + p + fsz - 4)) { reason = FOURMC_IMG_FOOTER_CHECKSUM; break; }
-        if (be32(img + p + 4) != 1)        { reason = FOURMC_IMG_FOOTER_VERSION; break; }
+        if ((reason = footer_verdict(xxh32_lane(img + p, fsz - 4, 0), be32(img + p + fsz - 4), be32(img + p + 4)))) break;
         p += fsz;
         if (total == stream_total0) break;                                       // an empty stream ends the file
     }
@@ -270,10 +290,9 @@ void image_parse_walk_kernel(const uint8_t* __restrict__ img, uint64_t N, uint32
     }
 }
 
-// The verdict: the first block that failed its checksum or its decode ends decoding there (file order puts it before any
-// framing error, which the parsers only ever report behind the last block they counted); otherwise the parser's verdict.
-__global__ __launch_bounds__(64)
-void image_reduce_kernel(const fourmc_block* __restrict__ blocks, uint32_t n, const fourmc_image_parse* ps, fourmc_image_status* st)
+// image_reduce's scan, one wave: the index of the first block whose result is negative (n if none) and *done, the sum of the
+// positive results before it
+__device__ __forceinline__ uint32_t first_failing(const fourmc_block* __restrict__ blocks, uint32_t n, uint64_t* done_out)
 {
     const int lane = threadIdx.x;
     uint64_t done = 0;
@@ -292,14 +311,26 @@ void image_reduce_kernel(const fourmc_block* __restrict__ blocks, uint32_t n, co
         done += mine;
         if (badm) break;
     }
-    if (lane) return;
+    *done_out = done;
+    return first;
+}
+__device__ __forceinline__ int32_t block_reason(int32_t result)
+{ return result == FOURMC_BLK_BADSUM ? FOURMC_IMG_BLOCK_CHECKSUM : FOURMC_IMG_CORRUPT; }
+
+// The verdict: the first block that failed its checksum or its decode ends decoding there (file order puts it before any
+// framing error, which the parsers only ever report behind the last block they counted); otherwise the parser's verdict.
+__global__ __launch_bounds__(64)
+void image_reduce_kernel(const fourmc_block* __restrict__ blocks, uint32_t n, const fourmc_image_parse* ps, fourmc_image_status* st)
+{
+    uint64_t done = 0;
+    const uint32_t first = first_failing(blocks, n, &done);
+    if (threadIdx.x) return;
     st->decoded_bytes = done;
     st->total_bytes = ps->total;
     st->streams = ps->streams;
     st->blocks = first;
     if (first < n) {
-        const int32_t r = blocks[first].result;
-        st->reason = r == FOURMC_BLK_BADSUM ? FOURMC_IMG_BLOCK_CHECKSUM : FOURMC_IMG_CORRUPT;
+        st->reason = block_reason(blocks[first].result);
         st->exit_code = 4;
         st->fail_offset = blocks[first].src_off - 12;
     } else {
@@ -623,6 +654,207 @@ void image_read_reduce_kernel(const fourmc_image_entry* __restrict__ ent, fourmc
     if (__ballot(b) && lane == 0) ranges[r].result = -4;
 }
 
+// ------------------------------------------------------------------------------------------------------------- streaming reads
+// The reader's walk is the whole-image walk restated so that it stops at the end of the appended bytes and carries on at the next
+// append: its state (fourmc_image_rd_state) lives in device memory, a unit in progress (a header, a payload, a footer) is carried
+// by what it has received so far, and every check is decided as soon as the bytes it reads are there.  A check that needs bytes
+// not yet appended waits: the finish kernel decides it with N = everything appended.  Payload bytes go from the chunk straight
+// into the block's staging slot (assigned when its header completes), so a block cut by the end of a chunk waits in its own slot.
+enum : uint32_t { RD_FHDR = 0, RD_BHDR = 1, RD_PAY = 2, RD_BADPAY = 3, RD_FSIZE = 4, RD_FBODY = 5 };
+constexpr uint32_t kNoSlot = ~0u;
+constexpr uint64_t kRdSlot = FOURMC_BLOCKSIZE;           // staging slot stride of the reader
+
+__device__ __forceinline__ uint32_t avalanche(uint32_t h)
+{ h ^= h >> 15; h *= P2; h ^= h >> 13; h *= P3; h ^= h >> 16; return h; }
+__device__ __forceinline__ void xxh_round4(uint32_t* v, uint32_t a, uint32_t b, uint32_t c, uint32_t d)
+{
+    v[0] = rotl(v[0] + a * P2, 13) * P1; v[1] = rotl(v[1] + b * P2, 13) * P1;
+    v[2] = rotl(v[2] + c * P2, 13) * P1; v[3] = rotl(v[3] + d * P2, 13) * P1;
+}
+// 16 bytes held as two little-endian words: byte k at bits 8 (k % 8) of word k / 8
+__device__ __forceinline__ void put_byte(uint64_t* w, uint32_t k, uint8_t b) { w[k >> 3] |= uint64_t(b) << (8 * (k & 7)); }
+__device__ __forceinline__ uint32_t word_le32(const uint64_t* w, uint32_t k)   // k = 0, 4, 8, 12
+{ return uint32_t(w[k >> 3] >> (8 * (k & 7))); }
+__device__ __forceinline__ uint32_t word_be32(const uint64_t* w, uint32_t k) { return __builtin_bswap32(word_le32(w, k)); }
+
+// streaming XXH32 (seed 0): xxh32_lane's result for the concatenation of every update
+__device__ __forceinline__ void xs_reset(fourmc_image_rd_state& S)
+{
+    S.xv[0] = P1 + P2; S.xv[1] = P2; S.xv[2] = 0; S.xv[3] = 0u - P1;
+    S.xlen = 0; S.xbn = 0; S.xbuf[0] = S.xbuf[1] = 0;
+}
+__device__ void xs_update(fourmc_image_rd_state& S, const uint8_t* p, uint64_t n)
+{
+    S.xlen += n;
+    while (S.xbn && n) {
+        put_byte(S.xbuf, S.xbn, *p++); n--;
+        if (++S.xbn == 16) {
+            xxh_round4(S.xv, word_le32(S.xbuf, 0), word_le32(S.xbuf, 4), word_le32(S.xbuf, 8), word_le32(S.xbuf, 12));
+            S.xbn = 0; S.xbuf[0] = S.xbuf[1] = 0;
+        }
+    }
+    for (; n >= 16; n -= 16, p += 16) xxh_round4(S.xv, le32(p), le32(p + 4), le32(p + 8), le32(p + 12));
+    for (; n; n--) put_byte(S.xbuf, S.xbn++, *p++);
+}
+__device__ uint32_t xs_digest(const fourmc_image_rd_state& S)
+{
+    uint32_t h = S.xlen >= 16 ? rotl(S.xv[0], 1) + rotl(S.xv[1], 7) + rotl(S.xv[2], 12) + rotl(S.xv[3], 18) : P5;
+    h += uint32_t(S.xlen);
+    uint32_t k = 0;
+    for (; k + 4 <= S.xbn; k += 4) h = rotl(h + word_le32(S.xbuf, k) * P3, 17) * P4;
+    for (; k < S.xbn; k++) h = rotl(h + uint32_t(uint8_t(S.xbuf[k >> 3] >> (8 * (k & 7)))) * P5, 11) * P1;
+    return avalanche(h);
+}
+
+__device__ __forceinline__ void rd_enter(fourmc_image_rd_state& S, uint32_t phase)
+{ S.phase = phase; S.at = S.pos; S.have = 0; S.part[0] = S.part[1] = 0; S.got = 0; }
+__device__ __forceinline__ void rd_final(fourmc_image_rd_state& S, int32_t reason) { S.final_ = 1; S.reason = reason; }
+
+// One lane.  Consumes chunk[i, L) until the chunk ends, the batch is full or the verdict is final; the chunk is read only inside
+// [c, c + L).  A block whose payload is complete gets its descriptor in its slot; its payload bytes in this chunk become a copy piece.
+__global__ __launch_bounds__(64)
+void image_rd_walk_kernel(const uint8_t* __restrict__ c, uint64_t L, uint64_t i, fourmc_image_rd_state* __restrict__ st,
+                          uint32_t magic, uint64_t dst_cap, uint32_t batch, uint8_t* __restrict__ stage,
+                          fourmc_block* __restrict__ desc, uint64_t* __restrict__ at_out, fourmc_image_piece* __restrict__ pc)
+{
+    if (threadIdx.x != 0) return;
+    fourmc_image_rd_state S = *st;
+    uint32_t np = 0;
+    uint64_t maxp = 0;
+    while (!S.final_ && S.batch_n < batch) {
+        // a payload with all its bytes completes without another one (an empty payload right after its header)
+        if ((S.phase == RD_PAY || S.phase == RD_BADPAY) && S.got == S.csize) {
+            if (S.phase == RD_BADPAY) { rd_final(S, usize_verdict(xs_digest(S), S.sum)); break; }
+            if (S.slot != kNoSlot) {
+                fourmc_block d;
+                d.src_off = uint64_t(S.slot) * kRdSlot; d.dst_off = S.total; d.src_len = S.csize; d.dst_cap = S.usize;
+                d.result = 0; d.xxh32 = S.sum;
+                desc[S.slot] = d;
+                at_out[S.slot] = S.at;
+                S.batch_n++;
+            }
+            S.nblocks++; S.total += S.usize;
+            rd_enter(S, RD_BHDR);
+            continue;
+        }
+        if (i == L) break;
+        const uint64_t left = L - i;
+        if (S.phase == RD_FHDR || S.phase == RD_BHDR || S.phase == RD_FSIZE) {
+            const uint32_t want = S.phase == RD_FSIZE ? 4u : 12u;
+            while (S.have < want && i < L) { put_byte(S.part, S.have++, c[i++]); S.pos++; }
+            if (S.phase == RD_FHDR) {
+                if (S.have >= 4 && word_be32(S.part, 0) != magic) { rd_final(S, FOURMC_IMG_NOT_4MC); break; }
+                if (S.have < 12) continue;
+                const uint32_t w0 = word_le32(S.part, 0), w1 = word_le32(S.part, 4);      // XXH32 of the first 8 bytes
+                const uint32_t hsum = avalanche(rotl(rotl(P5 + 8 + w0 * P3, 17) * P4 + w1 * P3, 17) * P4);
+                if (const int32_t r = file_header_verdict(word_be32(S.part, 4), word_be32(S.part, 8), hsum)) { rd_final(S, r); break; }
+                S.streams++; S.stream_total0 = S.total;
+                rd_enter(S, RD_BHDR);
+            } else if (S.phase == RD_BHDR) {
+                if (S.have < 12) continue;
+                const uint32_t usize = word_be32(S.part, 0), csize = word_be32(S.part, 4), sum = word_be32(S.part, 8);
+                if (end_mark(usize, csize, sum)) { rd_enter(S, RD_FSIZE); continue; }
+                if (csize_beyond(csize)) { rd_final(S, FOURMC_IMG_CSIZE_BEYOND); break; }
+                S.usize = usize; S.csize = csize; S.sum = sum; S.got = 0;
+                if (usize_beyond(usize, csize)) { S.phase = RD_BADPAY; xs_reset(S); continue; }
+                S.phase = RD_PAY;
+                S.slot = usize <= dst_cap && S.total <= dst_cap - usize ? S.batch_n : kNoSlot;   // else DST_SMALL decides
+            } else {
+                if (S.have < 4) continue;
+                S.fsz = word_be32(S.part, 0);
+                if (S.fsz < 8) { rd_final(S, FOURMC_IMG_FOOTER_SHORT); break; }
+                xs_reset(S);
+                S.xbuf[0] = uint32_t(S.part[0]); S.xbn = 4; S.xlen = 4;                  // the size field opens the hashed bytes
+                S.phase = RD_FBODY; S.got = 4;
+            }
+            continue;
+        }
+        if (S.phase == RD_PAY || S.phase == RD_BADPAY) {
+            const uint64_t take = min(uint64_t(S.csize) - S.got, left);
+            if (S.phase == RD_BADPAY) xs_update(S, c + i, take);
+            else if (S.slot != kNoSlot) {
+                fourmc_image_piece q;
+                q.src = uint64_t(uintptr_t(c + i)); q.dst = uint64_t(uintptr_t(stage + uint64_t(S.slot) * kRdSlot + S.got));
+                q.len = take; q.pad = 0;
+                pc[np++] = q;
+                maxp = max(maxp, take);
+            }
+            S.got += take; i += take; S.pos += take;
+            continue;
+        }
+        // RD_FBODY: footer bytes [got, fsz): XXH32 over [0, fsz - 4), the version at [4, 8), the checksum at [fsz - 4, fsz)
+        const uint64_t fsz = S.fsz, a = S.got, take = min(fsz - a, left), z = a + take;
+        const uint64_t hz = min(z, fsz - 4);
+        if (a < hz) xs_update(S, c + i, hz - a);
+        for (uint64_t q = max(a, uint64_t(4)); q < min(z, uint64_t(8)); q++) put_byte(S.part, uint32_t(q), c[i + (q - a)]);
+        for (uint64_t q = max(a, fsz - 4); q < z; q++) put_byte(S.part, uint32_t(8 + q - (fsz - 4)), c[i + (q - a)]);
+        S.got = z; i += take; S.pos += take;
+        if (S.got < fsz) continue;
+        if (const int32_t r = footer_verdict(xs_digest(S), word_be32(S.part, 8), word_be32(S.part, 4))) { rd_final(S, r); break; }
+        if (S.total == S.stream_total0) { rd_final(S, FOURMC_IMG_OK); break; }     // an empty stream ends the file
+        rd_enter(S, RD_FHDR);
+    }
+    S.cpos = i; S.npieces = np; S.max_piece = uint32_t(maxp);
+    *st = S;
+}
+
+// The copy pieces of one walk: one wave per 64 KiB of a piece; blockIdx.x = piece, blockIdx.y = its 64 KiB step
+__global__ __launch_bounds__(64)
+void image_rd_gather_kernel(const fourmc_image_piece* __restrict__ pc)
+{
+    const fourmc_image_piece q = pc[blockIdx.x];
+    const uint64_t c0 = uint64_t(blockIdx.y) * kChunk;
+    if (c0 >= q.len) return;
+    wave_copy(reinterpret_cast<uint8_t*>(uintptr_t(q.dst)) + c0, reinterpret_cast<const uint8_t*>(uintptr_t(q.src)) + c0,
+              int(min(q.len - c0, uint64_t(kChunk))), int(threadIdx.x));
+}
+
+// image_reduce's rule across batches: the first failing block (in file order) and the decoded bytes before it; the batch empties
+__global__ __launch_bounds__(64)
+void image_rd_fold_kernel(const fourmc_block* __restrict__ desc, const uint64_t* __restrict__ at, uint32_t n,
+                          fourmc_image_rd_state* __restrict__ st)
+{
+    const uint64_t base = st->decoded;
+    if (st->first_reason == 0) {
+        uint64_t done = 0;
+        const uint32_t first = first_failing(desc, n, &done);
+        if (threadIdx.x == 0) {
+            st->done += done;
+            if (first < n) { st->first = uint32_t(base + first); st->first_at = at[first]; st->first_reason = block_reason(desc[first].result); }
+        }
+    }
+    if (threadIdx.x == 0) { st->decoded = base + n; st->batch_n = 0; }
+}
+
+// The checks that waited for bytes, decided with N; then the status image_decompress writes for the same bytes
+__global__ __launch_bounds__(64)
+void image_rd_finish_kernel(const fourmc_image_rd_state* __restrict__ st, uint64_t N, uint64_t dst_cap, fourmc_image_status* __restrict__ out)
+{
+    if (threadIdx.x != 0) return;
+    const fourmc_image_rd_state S = *st;
+    int32_t reason = S.reason;
+    if (!S.final_) {
+        switch (S.phase) {
+            case RD_FHDR:   reason = S.have == 0 ? FOURMC_IMG_OK : S.have < 4 ? FOURMC_IMG_MAGIC_UNREADABLE : FOURMC_IMG_HEADER_UNREADABLE; break;
+            case RD_BHDR:   reason = FOURMC_IMG_BLOCK_SIZE_UNREADABLE; break;
+            case RD_FSIZE:  reason = FOURMC_IMG_FOOTER_UNREADABLE; break;
+            case RD_FBODY:  reason = FOURMC_IMG_FOOTER_SHORT; break;
+            default:        reason = FOURMC_IMG_DATA_UNREADABLE; break;
+        }
+    }
+    fourmc_image_status r = {};
+    r.total_bytes = S.total; r.streams = S.streams;
+    if (S.total > dst_cap) {
+        r.reason = FOURMC_IMG_DST_SMALL; r.exit_code = fourmc_image_exit_code(FOURMC_IMG_DST_SMALL);
+    } else if (S.first_reason) {
+        r.decoded_bytes = S.done; r.blocks = S.first; r.reason = S.first_reason; r.exit_code = 4; r.fail_offset = S.first_at;
+    } else {
+        r.decoded_bytes = S.done; r.blocks = uint32_t(S.nblocks); r.reason = reason; r.exit_code = fourmc_image_exit_code(reason);
+        r.fail_offset = reason == FOURMC_IMG_OK ? N : S.at;
+    }
+    *out = r;
+}
+
 } // namespace
 
 extern "C" {
@@ -750,6 +982,36 @@ hipError_t fourmc_launch_image_read_reduce(const fourmc_image_entry* d_ent, four
 {
     if (!nranges) return hipSuccess;
     hipLaunchKernelGGL(image_read_reduce_kernel, dim3(nranges), dim3(64), 0, s, d_ent, d_ranges, d_rp, d_slot, d_desc, ndirect);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_image_rd_walk(const void* d_chunk, uint64_t bytes, uint64_t start, fourmc_image_rd_state* d_st,
+                                       uint32_t magic, uint64_t dst_cap, uint32_t batch, void* d_stage, fourmc_block* d_desc,
+                                       uint64_t* d_at, fourmc_image_piece* d_pc, hipStream_t s)
+{
+    hipLaunchKernelGGL(image_rd_walk_kernel, dim3(1), dim3(64), 0, s, static_cast<const uint8_t*>(d_chunk), bytes, start, d_st, magic,
+                       dst_cap, batch, static_cast<uint8_t*>(d_stage), d_desc, d_at, d_pc);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_image_rd_gather(const fourmc_image_piece* d_pc, uint32_t npieces, uint64_t max_piece, hipStream_t s)
+{
+    if (!npieces || !max_piece) return hipSuccess;
+    hipLaunchKernelGGL(image_rd_gather_kernel, dim3(npieces, uint32_t((max_piece + kChunk - 1) / kChunk)), dim3(64), 0, s, d_pc);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_image_rd_fold(const fourmc_block* d_desc, const uint64_t* d_at, uint32_t n, fourmc_image_rd_state* d_st,
+                                       hipStream_t s)
+{
+    hipLaunchKernelGGL(image_rd_fold_kernel, dim3(1), dim3(64), 0, s, d_desc, d_at, n, d_st);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_image_rd_finish(const fourmc_image_rd_state* d_st, uint64_t image_bytes, uint64_t dst_cap,
+                                         fourmc_image_status* d_status, hipStream_t s)
+{
+    hipLaunchKernelGGL(image_rd_finish_kernel, dim3(1), dim3(64), 0, s, d_st, image_bytes, dst_cap, d_status);
     return hipGetLastError();
 }
 

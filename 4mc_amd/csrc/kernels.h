@@ -155,6 +155,57 @@ hipError_t fourmc_launch_image_read_copy(const fourmc_image_entry* d_ent, const 
 hipError_t fourmc_launch_image_read_reduce(const fourmc_image_entry* d_ent, fourmc_image_range* d_ranges, uint32_t nranges,
                                            const fourmc_image_rplan* d_rp, const uint32_t* d_slot, const fourmc_block* d_desc,
                                            uint64_t ndirect, hipStream_t s);
+/* the streaming reader (fourmc_gpu_image_reader_*): the resumable walk's device state.  The first block is what the engine reads
+ * back after each walk launch. */
+typedef struct fourmc_image_rd_state {
+    /* read back after every walk */
+    uint64_t cpos;          /* where the walk stopped in the chunk */
+    uint32_t batch_n;       /* complete blocks in the current batch (staging slots 0 .. batch_n-1) */
+    uint32_t npieces;       /* copy pieces the walk emitted */
+    uint32_t max_piece;     /* the longest of them */
+    uint32_t final_;        /* the framing verdict is final: later bytes are not read */
+    /* the walk */
+    uint64_t pos;           /* image offset of the next byte to consume */
+    uint64_t at;            /* image offset of the unit in progress (file header, block header, footer): the fail offset */
+    uint64_t total;         /* sum of the usizes of the well-formed blocks */
+    uint64_t stream_total0; /* total when the current stream's header passed */
+    uint64_t nblocks;       /* well-formed blocks */
+    uint64_t got;           /* bytes of the current payload / footer received */
+    uint32_t phase, streams;
+    int32_t  reason;        /* the verdict once final_ */
+    uint32_t have;          /* header / size-field bytes in part */
+    uint32_t usize, csize, sum, slot;   /* the current block; slot ~0u: not decoded (it ends beyond dst_cap) */
+    uint32_t fsz, xbn;      /* the footer's size field; bytes in xbuf */
+    uint64_t part[2];       /* a header in progress, byte k at bits 8 (k % 8) of word k / 8; a footer keeps its size and version
+                             * at bytes 0..7 and its checksum at 8..11 */
+    uint32_t xv[4];         /* streaming XXH32 of a footer or of an oversized block's payload: lanes, length, partial stripe */
+    uint64_t xlen;
+    uint64_t xbuf[2];
+    /* the fold over the decoded batches */
+    uint64_t done;          /* decoded bytes before the first failing block */
+    uint64_t decoded;       /* blocks decoded so far (the global index of the next batch's first block) */
+    uint64_t first_at;      /* image offset of the first failing block's header */
+    uint32_t first;         /* its global index */
+    int32_t  first_reason;  /* 0: none yet, else FOURMC_IMG_BLOCK_CHECKSUM / FOURMC_IMG_CORRUPT */
+} fourmc_image_rd_state;
+/* one copy of payload bytes from a chunk into a staging slot */
+typedef struct fourmc_image_piece {
+    uint64_t src, dst;      /* device addresses */
+    uint64_t len;
+    uint64_t pad;
+} fourmc_image_piece;
+/* the walk over chunk[start, bytes): descriptors (src_off relative to the staging, dst_off to d_dst) and header offsets of the
+ * blocks it completes into slots batch_n.., copy pieces, until the chunk ends, the batch is full or the verdict is final */
+hipError_t fourmc_launch_image_rd_walk(const void* d_chunk, uint64_t bytes, uint64_t start, fourmc_image_rd_state* d_st,
+                                       uint32_t magic, uint64_t dst_cap, uint32_t batch, void* d_stage, fourmc_block* d_desc,
+                                       uint64_t* d_at, fourmc_image_piece* d_pc, hipStream_t s);
+hipError_t fourmc_launch_image_rd_gather(const fourmc_image_piece* d_pc, uint32_t npieces, uint64_t max_piece, hipStream_t s);
+/* after a batch of n blocks has decoded: image_reduce's rule carried across batches; the batch is emptied */
+hipError_t fourmc_launch_image_rd_fold(const fourmc_block* d_desc, const uint64_t* d_at, uint32_t n, fourmc_image_rd_state* d_st,
+                                       hipStream_t s);
+/* the deferred checks with N = image_bytes, the DST_SMALL rule and the fold into *d_status */
+hipError_t fourmc_launch_image_rd_finish(const fourmc_image_rd_state* d_st, uint64_t image_bytes, uint64_t dst_cap,
+                                         fourmc_image_status* d_status, hipStream_t s);
 #ifdef FOURMC_RESEARCH      /* the research side build exports these two: tools/zstd_timing.py and tools/k7x_prof.py size their read-backs with them */
 #pragma GCC visibility push(default)
 #endif

@@ -258,3 +258,72 @@ class ImageWriter:
                 self.abort()
             except Exception:
                 pass
+
+
+def _status_dict(st):
+    res = {name: int(getattr(st, name)) for name, _ in ImageStatus._fields_}
+    res["message"] = lib().fourmc_gpu_image_reason_text(st.reason).decode()
+    return res
+
+
+class ImageReader:
+    """Streaming reads of one .4mc / .4mz image into d_dst (fourmc_gpu_image_reader_*): append() chunks of the image in file order
+    as they arrive, finish() for the status.  The status and the bytes are the ones decompress_image gives for the concatenation of
+    the chunks.  Appends queue work on `stream` (default: the current stream); they synchronize it once per walk over the chunk.
+    As a context manager the reader is aborted when the block raises, or when it ends without finish()."""
+
+    def __init__(self, d_dst, magic=MAGIC_4MC, batch_blocks=0, stream=None):
+        ptr = _dev_ptr(d_dst, "ImageReader d_dst")
+        self._stream = torch.cuda.current_stream() if stream is None else stream
+        h = C.c_void_p(0)
+        check(lib().fourmc_gpu_image_reader_begin(C.byref(h), ptr, d_dst.numel(), magic, batch_blocks, _stream_ptr(self._stream)),
+              "fourmc_gpu_image_reader_begin")
+        self._h = h.value
+        self._dst = d_dst                         # the queued decodes write into it until finish
+
+    def _handle(self, what):
+        if not self._h:
+            raise EngineError(f"ImageReader.{what}: the reader is finished or aborted")
+        return self._h
+
+    def append(self, chunk):
+        """Queues the chunk (a contiguous uint8 CUDA tensor); the caching allocator keeps its memory until the stream has read it."""
+        h = self._handle("append")
+        ptr = _dev_ptr(chunk, "ImageReader.append chunk")
+        if chunk.numel():
+            chunk.record_stream(self._stream)
+        check(lib().fourmc_gpu_image_reader_append(h, ptr, chunk.numel()), "fourmc_gpu_image_reader_append")
+
+    def finish(self):
+        """Decodes the last batch and returns the status as decompress_image does (a dict with "message").  The reader is closed
+        whatever happens."""
+        h = self._handle("finish")
+        self._h = None
+        st = ImageStatus()
+        check(lib().fourmc_gpu_image_reader_finish(h, C.byref(st)), "fourmc_gpu_image_reader_finish")
+        return _status_dict(st)
+
+    def abort(self):
+        """Frees the reader without a status."""
+        h = self._handle("abort")
+        self._h = None
+        lib().fourmc_gpu_image_reader_abort(h)
+
+    @property
+    def closed(self):
+        return not self._h
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self._h:
+            self.abort()
+        return False
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                self.abort()
+            except Exception:
+                pass

@@ -236,6 +236,51 @@ const char* fourmc_gpu_image_reason_text(int reason);
  * file-order walk (everything the fast path does not prove: concatenations, damage, FOURMC_IMAGE_PARSE=walk). */
 void fourmc_gpu_image_parse_stats(unsigned long long* fast, unsigned long long* walk);
 
+/* ---- streaming reads of one image: append chunks of any size as they arrive, in file order ------------------------------------
+ * The one rule.  After finish, *status equals, field for field, what fourmc_gpu_image_decompress returns for the concatenation of
+ *   every appended chunk (N bytes in all) with the same d_dst, dst_cap and magic, and d_dst[0, decoded_bytes) holds the same bytes.
+ *   This holds for every way the image is cut: empty and 1-byte appends, cuts inside the file header, a block header, a payload,
+ *   the end mark, the footer's size field or its body, appends of many blocks, concatenated streams, trailing bytes and bytes
+ *   after the empty stream that ends a file.  The reader never writes outside [d_dst, d_dst + dst_cap).
+ *   - A check that needs bytes not yet appended waits ("magic unreadable", "cannot read next block size", "cannot read data
+ *     block", "unreadable footer", "footer short"): finish decides it with N.  fail_offset is an offset in the image, not in a
+ *     chunk; for an image that decodes cleanly it is N.
+ *   - FOURMC_IMG_DST_SMALL is decided as image_decompress decides it: the sum of the usizes of the well-formed blocks is compared
+ *     with dst_cap, and that check wins over a block that failed its checksum.  The one difference: the blocks that fit may
+ *     already have been written (a block that would end past dst_cap is never decoded).
+ *   - Once the verdict is final (a framing error, or the clean end after a stream whose blocks add up to 0 bytes), later appends
+ *     are accepted; they count toward N and cost nothing more.  A footer may claim any size up to 4 GiB: its XXH32 is a
+ *     streaming state carried across appends, and the footer is never buffered.
+ *   The block decode is fourmc_gpu_4mc_decode_blocks with the magic's codec (payload XXH32, then LZ4 or zstd), in batches of
+ *   batch_blocks from the reader's staging, so every setting it obeys (FOURMC_DECODE, FOURMC_ZDECODE) applies unchanged.
+ * Begin.  Checks the magic and the pointers, then allocates everything the reader owns in one piece: batch_blocks staging slots of
+ *   4 MiB (with the 64 bytes of slack the block decoders read past a payload), the descriptors and header offsets of one batch,
+ *   the copy pieces of one walk and the device state (the walk's position, phase, partial header bytes, running totals and
+ *   footer XXH32 state; the fold of the decoded batches).  A block cut by the end of a chunk waits in its own staging slot, so
+ *   there is no separate carry slot.  batch_blocks 0 means 512, the writer's and the mapped file path's batch.  FOURMC_EINVAL for a
+ *   bad magic or a NULL pointer (d_dst NULL included: there is no parse-only mode); FOURMC_ENODEV without a device; FOURMC_ENOMEM
+ *   when the allocation fails.  On any error *r is left NULL.
+ * Append.  Queues work on the reader's stream: the walk over the chunk, the copy of its payload bytes into staging, and the decode
+ *   of each batch it fills.  No hipMalloc / hipFree of its own (the engine's decode workspaces may grow, as in every decode call).
+ *   It synchronizes the stream once to read back what the walk found, plus once for each further batch the chunk fills.  The
+ *   reader never reads outside [d_chunk, d_chunk + bytes), so chunks cut from files and sockets need no slack, and the chunk may be
+ *   reused or freed once the stream has passed the append.
+ * Finish.  Decodes the last partial batch, decides the checks that waited with N, folds in the first failing block in file order,
+ *   writes *status and synchronizes the stream.  finish frees the reader whatever it returns.
+ * Failures.  An argument check (a NULL reader, a NULL chunk of nonzero length) fails the call and leaves the reader as it was.
+ *   After any other failure (FOURMC_ENOMEM from a decode workspace, FOURMC_EHIP, ...) the reader is poisoned: later appends
+ *   return that first error, and finish returns it and frees.
+ * Independence.  The reader owns its buffers and holds no per-stream workspace of the engine between calls, so other engine calls
+ *   on the same stream may run between appends, and several readers and writers may be open at once, on one stream or several.
+ *   fourmc_gpu_release_workspaces does not touch a reader's buffers.  A reader is used by one thread at a time.  abort frees the
+ *   reader without a status (it waits for the work queued on the stream first); abort(NULL) does nothing. */
+typedef struct fourmc_image_reader fourmc_image_reader;      /* opaque */
+int  fourmc_gpu_image_reader_begin(fourmc_image_reader** r, void* d_dst, uint64_t dst_cap, uint32_t magic,
+                                   uint32_t batch_blocks, void* stream);
+int  fourmc_gpu_image_reader_append(fourmc_image_reader* r, const void* d_chunk, uint64_t bytes);
+int  fourmc_gpu_image_reader_finish(fourmc_image_reader* r, fourmc_image_status* status);  /* frees r, whatever it returns */
+void fourmc_gpu_image_reader_abort(fourmc_image_reader* r);                                /* frees r; NULL is a no-op */
+
 /* ---- random access into single-stream images in device memory ---------------------------------------------------------------
  * The device twins of fourmc_file_block_count / fourmc_file_decode_blocks (include/fourmc.h): the image's footer index, the
  * decode of a block range, and reads of decoded byte ranges.  Every verdict is the one fourmc_file_decode_blocks reaches on the
