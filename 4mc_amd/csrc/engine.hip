@@ -141,41 +141,57 @@ extern "C" int fourmc_gpu_release_workspaces(void)
 }
 namespace {
 
+// A codec's per-block workspace, leased on its stream.  FOURMC_WS_FAIL_ABOVE=N (test aid, read once per process) makes every such
+// lease of more than N bytes fail the way hipMalloc does when the device is out of memory, so that the answers to it - the pieces
+// of in_pieces, the smaller batches and the exact walker of lease_lz4_decode - run on any device.  (The image calls' descriptor and
+// staging leases are not codec workspaces and are never refused.)
+int lease_codec_ws(WsLease& ws, hipStream_t s, size_t need, void** work)
+{
+    static const size_t fail_above = [] { const char* e = getenv("FOURMC_WS_FAIL_ABOVE"); return e ? size_t(strtoull(e, nullptr, 10)) : size_t(0); }();
+    if (fail_above && need > fail_above) {
+        snprintf(g_err, sizeof g_err, "workspace of %zu bytes refused (FOURMC_WS_FAIL_ABOVE)", need);
+        return FOURMC_ENOMEM;
+    }
+    return ws.get(s, need, work);
+}
+
 // The LZ4 decode workspace.  Path, piece size and bytes are resolved once (fourmc_lz4_decode_plan) and handed to the launcher; when
-// the device cannot give the workspace the pieces halve FOR THIS CALL (the launch is then cut into more of them), and an automatic
-// choice ends at the walk + window copier, which needs none.
+// the device cannot give the workspace the pieces halve FOR THIS CALL (the launch is then cut into more of them) until they are
+// below 64 blocks: there an automatic choice ends at the exact walker, which needs none, and an explicit tile / seg choice fails
+// with FOURMC_ENOMEM.
 int lease_lz4_decode(WsLease& ws, hipStream_t s, uint32_t n, void** work, fourmc_lz4_plan* plan)
 {
     fourmc_lz4_plan prev; prev.path = -1; prev.batch = 0; prev.work_bytes = 0; prev.ok = 0;
+    int r = FOURMC_ENOMEM;
     for (uint32_t shrink = 0;; shrink++) {
         *plan = fourmc_lz4_decode_plan(n, shrink);
         if (!plan->ok) { snprintf(g_err, sizeof g_err, "LZ4 decode workspace cannot be allocated"); return FOURMC_ENOMEM; }
         if (plan->work_bytes == 0) { *work = nullptr; return FOURMC_OK; }
-        const int r = ws.get(s, plan->work_bytes, work);
-        if (r == FOURMC_OK) return r;
-        // only "out of memory" is answered with smaller pieces: any other device error is the caller's to see; and a plan that did
-        // not change (a path without a shrinkable batch) cannot succeed on the next turn either (this loop spun forever)
-        if (r != FOURMC_ENOMEM) return r;
-        if (shrink && plan->path == prev.path && plan->batch == prev.batch && plan->work_bytes == prev.work_bytes) return r;
+        // An unchanged plan cannot succeed where the last one failed.  On the tile / seg paths (11..16) it only means the halved
+        // batch is still above n: the halving goes on until the plan changes or ends (path 2 or !ok).  Any other path has no batch
+        // to shrink (the research paths 1 / 3) and stops here (this loop spun forever; r6: it stopped on the first turn).
+        const bool same = shrink && plan->path == prev.path && plan->batch == prev.batch && plan->work_bytes == prev.work_bytes;
+        if (same && (plan->path < 11 || plan->path > 16)) return r;
         prev = *plan;
+        if (same) continue;
+        r = lease_codec_ws(ws, s, plan->work_bytes, work);
+        if (r == FOURMC_OK) return r;
+        // only "out of memory" is answered with smaller pieces: any other device error is the caller's to see
+        if (r != FOURMC_ENOMEM) return r;
     }
 }
 
 // A launch whose workspace grows with its blocks.  When the device cannot give the memory for all of them at once the launch is cut
 // into pieces, halved until the allocation succeeds: the blocks are independent, so the results are the same and only the chip is
 // filled less well (a 512-block batch of level-12 tables is 25 GiB; nothing retried with a smaller batch).
-// `cap`: the most blocks a piece may have (0: no limit).  FOURMC_WS_FAIL_ABOVE=N makes leases of more than N bytes fail (test aid).
+// `cap`: the most blocks a piece may have (0: no limit).  The lease honours FOURMC_WS_FAIL_ABOVE (lease_codec_ws).
 template <class Bytes, class Launch>
 int in_pieces(hipStream_t s, uint32_t n, uint32_t cap, Bytes bytes, Launch launch)
 {
-    static const size_t fail_above = [] { const char* e = getenv("FOURMC_WS_FAIL_ABOVE"); return e ? size_t(strtoull(e, nullptr, 10)) : size_t(0); }();
     uint32_t piece = cap && cap < n ? cap : n;
     WsLease ws; void* work = nullptr;
     for (;;) {
-        const size_t need = bytes(piece);
-        int r = FOURMC_OK;
-        if (fail_above && need > fail_above) { snprintf(g_err, sizeof g_err, "workspace of %zu bytes refused (FOURMC_WS_FAIL_ABOVE)", need); r = FOURMC_ENOMEM; }
-        else r = ws.get(s, need, &work);
+        const int r = lease_codec_ws(ws, s, bytes(piece), &work);
         if (r == FOURMC_OK) break;
         if (r != FOURMC_ENOMEM || piece <= 1) return r;
         piece = (piece + 1) / 2;

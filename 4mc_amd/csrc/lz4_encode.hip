@@ -607,7 +607,7 @@ void lz4_encode_fast_kernel(const uint8_t* __restrict__ src_base, uint8_t* dst_b
     uint8_t* dst = dst_base + blk.dst_off;
     uint4* rec = reinterpret_cast<uint4*>(work + lz4rec_count_bytes(nblocks) + size_t(b) * lz4rec_area_bytes(reccap));
     const int n = int(blk.src_len);
-    const int cap = container_mode ? n - 1 : int(blk.dst_cap);
+    const int cap = container_mode ? (n > 0 ? n - 1 : 0) : int(blk.dst_cap);     // (an empty block: 0, not -1; as every encoder)
     const int lane = threadIdx.x;
     int r;
     uint32_t nrec = 0;

@@ -344,7 +344,7 @@ void lz4_par_stitch_kernel(const uint8_t* __restrict__ src_base, uint8_t* __rest
     const uint8_t* in = src_base + blk.src_off;
     uint8_t* dst = dst_base + blk.dst_off;
     const uint32_t n = blk.src_len;
-    const int64_t cap = container_mode ? int64_t(n) - 1 : int64_t(blk.dst_cap);
+    const int64_t cap = container_mode ? (n ? int64_t(n) - 1 : 0) : int64_t(blk.dst_cap);     // (an empty block: 0, not -1; as every encoder)
     if (n > 0x7E000000u) { if (k == 0 && lane == 0) blocks[b].result = 0; return; }        // lz4.c:1324
 
     // lane j <-> segment j of the block

@@ -597,7 +597,7 @@ void lz4hc_encode_kernel(const uint8_t* __restrict__ src_base, uint8_t* dst_base
         return;
     }
     uint8_t* dst = dst_base + blk.dst_off;
-    const int cap = container_mode ? n - 1 : int(blk.dst_cap);
+    const int cap = container_mode ? (n > 0 ? n - 1 : 0) : int(blk.dst_cap);     // (an empty block: 0, not -1 = no limit; as every encoder)
     int r = lz4hc_encode_block(src, dst, n, cap, attempts, work, wins, &sync, lane);
     if (lane == 0) st_rel(&sync.done, 1u);
     if (container_mode && r <= 0) { copy_bytes(dst, src, uint32_t(n), lane); r = n; }

@@ -279,7 +279,7 @@ void lz4hc_opt_encode_kernel(const uint8_t* __restrict__ src_base, uint8_t* dst_
     uint8_t* work = work_base + size_t(b) * kWorkBytes;
     HO c;
     c.src = src_base + blk.src_off; c.dst = dst_base + blk.dst_off; c.n = n;
-    c.cap = container_mode ? int64_t(n) - 1 : int64_t(blk.dst_cap);
+    c.cap = container_mode ? (n ? int64_t(n) - 1 : 0) : int64_t(blk.dst_cap);     // (an empty block: 0, not -1; as every encoder)
     c.limited = c.cap < int64_t(n) + n / 255 + 16;              // LZ4_compressBound (lz4hc.c:945)
     c.chain = chain; c.score = score; c.lane = lane;
     c.heads = reinterpret_cast<uint32_t*>(work);

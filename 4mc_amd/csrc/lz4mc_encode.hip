@@ -162,7 +162,7 @@ void lz4mc_encode_kernel(const uint8_t* __restrict__ src_base, uint8_t* dst_base
     const uint8_t* src = src_base + blk.src_off;
     uint8_t* dst = dst_base + blk.dst_off;
     const int n = int(blk.src_len);
-    const int cap = container_mode ? n - 1 : (blk.dst_cap == 0xFFFFFFFFu ? -1 : int(blk.dst_cap));
+    const int cap = container_mode ? (n > 0 ? n - 1 : 0) : (blk.dst_cap == 0xFFFFFFFFu ? -1 : int(blk.dst_cap));   // (an empty block: 0, not -1 = LZ4_compressMC; as every encoder)
     int r = lz4mc_encode_block(src, dst, n, cap, work_base + size_t(b) * kWorkBytes, threadIdx.x);
     if (container_mode && r <= 0) { copy_bytes(dst, src, uint32_t(n), threadIdx.x); r = n; }
     if (threadIdx.x == 0) blocks[b].result = r;
