@@ -91,6 +91,11 @@ for name, d in zin.items():
         zf[name]["frames"][str(lvl)] = out[:r].tobytes().hex()
 json.dump(zf, open(os.path.join(HERE, "zstd_frames.json"), "w"))
 
+# zstd frames of the shapes ZSTD_compress at levels 1..12 does not write (tests/zstd_shapes.py): for every ledger key of REQUIRED
+# the smallest frame that reaches it, with the length and SHA-256 of its output
+import zstd_shapes  # noqa: E402
+json.dump(zstd_shapes.fixture_select(zstd_shapes.frames()), open(zstd_shapes.FIXTURE, "w"), indent=0)
+
 # the reference's shipped JNI library through the mock JNIEnv driver: stdout, size + SHA-256 of every payload, stream sizes
 from test_jni_reference_artifact import REF_SO, RUNS, run_driver  # noqa: E402
 assert os.path.exists(REF_SO), REF_SO

@@ -70,6 +70,14 @@ def oracle():
     return _cache["oracle"]
 
 
+class ZstdInBuffer(C.Structure):          # ZSTD_inBuffer (zstd.h)
+    _fields_ = [("src", C.c_void_p), ("size", C.c_size_t), ("pos", C.c_size_t)]
+
+
+class ZstdOutBuffer(C.Structure):         # ZSTD_outBuffer
+    _fields_ = [("dst", C.c_void_p), ("size", C.c_size_t), ("pos", C.c_size_t)]
+
+
 def ref():
     """The reference's own codec sources compiled by oracle/Makefile; None when not built."""
     if "ref" not in _cache:
@@ -84,6 +92,15 @@ def ref():
             L.ZSTD_compress.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int]; L.ZSTD_compress.restype = C.c_size_t
             L.ZSTD_decompress.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]; L.ZSTD_decompress.restype = C.c_size_t
             L.ZSTD_isError.argtypes = [C.c_size_t]; L.ZSTD_isError.restype = C.c_uint
+            # the advanced API (tests/zstd_shapes.py): parameters, streaming with flushes, explicit sequences
+            L.ZSTD_createCCtx.argtypes = []; L.ZSTD_createCCtx.restype = C.c_void_p
+            L.ZSTD_freeCCtx.argtypes = [C.c_void_p]; L.ZSTD_freeCCtx.restype = C.c_size_t
+            L.ZSTD_CCtx_setParameter.argtypes = [C.c_void_p, C.c_int, C.c_int]; L.ZSTD_CCtx_setParameter.restype = C.c_size_t
+            L.ZSTD_compress2.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]; L.ZSTD_compress2.restype = C.c_size_t
+            L.ZSTD_compressStream2.argtypes = [C.c_void_p, C.POINTER(ZstdOutBuffer), C.POINTER(ZstdInBuffer), C.c_int]
+            L.ZSTD_compressStream2.restype = C.c_size_t
+            L.ZSTD_compressSequences.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+            L.ZSTD_compressSequences.restype = C.c_size_t
         _cache["ref"] = L
     return _cache["ref"]
 

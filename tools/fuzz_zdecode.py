@@ -13,6 +13,12 @@ rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 data = helpers.corpus(12 * B)
 lib = p.lib()
+import zstd_shapes
+# base frames of every shape the reference writes (tests/zstd_shapes.py) next to the level 1/3/6 frames of corpus pieces: the
+# generated set when oracle/_ref is built, else the committed subset; at most 1 MiB of output each (48 destinations per round)
+shaped = ([(f, len(e)) for _, f, e in zstd_shapes.frames()] if helpers.ref() is not None
+          else [(f, n) for _, f, n, _ in zstd_shapes.fixture_frames()])
+shaped = [(f, n) for f, n in shaped if 0 < n <= (1 << 20) and len(f) > 8 and not zstd_shapes.rejected_by_design(f)]
 
 def decode(frames, caps):
     offs, pos = [], 3
@@ -36,9 +42,13 @@ for rd in range(rounds):
         b = int(rng.integers(0, 12)); n = int(rng.choice([3000, 40000, 200000, 700000, 1 << 20]))
         at = int(rng.integers(0, B - n)); src = data[b * B + at: b * B + at + n]
         level = int(rng.choice([1, 3, 6]))
-        r, comp = helpers.orc_zstd_compress(src, level, n + 1024)
-        if r <= 0: continue
-        m = np.array(comp[:r], dtype=np.uint8)
+        if k % 2:
+            f, n = shaped[int(rng.integers(0, len(shaped)))]
+            m = np.frombuffer(f, np.uint8).copy()
+        else:
+            r, comp = helpers.orc_zstd_compress(src, level, n + 1024)
+            if r <= 0: continue
+            m = np.array(comp[:r], dtype=np.uint8)
         for _ in range(int(rng.integers(1, 3))):
             kind = int(rng.integers(0, 5)) if rng.integers(0, 3) == 0 else 0
             if kind == 0: m[rng.integers(0, len(m))] ^= 1 << rng.integers(0, 8)
