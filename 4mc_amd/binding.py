@@ -42,6 +42,18 @@ class ImageRange(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("length", C.c_uint64), ("dst_off", C.c_uint64), ("result", C.c_int64)]
 
 
+# struct fourmc_image_slice / fourmc_image_records (include/fourmc_gpu.h: the line records of a split)
+class ImageSlice(C.Structure):
+    _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("split_start", C.c_uint64), ("split_end", C.c_uint64),
+                ("first_block", C.c_uint32), ("block_count", C.c_uint32), ("result", C.c_int64)]
+
+
+class ImageRecords(C.Structure):
+    _fields_ = [("result", C.c_int64), ("base", C.c_uint64), ("data_off", C.c_uint64), ("data_bytes", C.c_uint64),
+                ("reserved", C.c_uint64)]
+
+
+assert C.sizeof(ImageSlice) == 48 and C.sizeof(ImageRecords) == 40
 IMAGE_ENTRY_DTYPE = np.dtype([("image_off", "<u8"), ("data_off", "<u8"), ("usize", "<u4"), ("csize", "<u4"),
                               ("xxh32", "<u4"), ("pad", "<u4")])
 assert C.sizeof(ImageEntry) == 32 and C.sizeof(ImageRange) == 32 and C.sizeof(ImageIndexInfo) == 32
@@ -69,7 +81,8 @@ def cli_path():
 _lib = None
 _product_lib = None
 # declared by include/fourmc_gpu.h under FOURMC_RESEARCH only: the product library does not export them
-_RESEARCH_ONLY = ("fourmc_gpu_debug_read_workspace", "fourmc_gpu_debug_zstd_exec_counts", "fourmc_gpu_debug_lz4_parse", "fourmc_debug_one_block_counters")
+_RESEARCH_ONLY = ("fourmc_gpu_debug_read_workspace", "fourmc_gpu_debug_zstd_exec_counts", "fourmc_gpu_debug_lz4_parse", "fourmc_debug_one_block_counters",
+                  "fourmc_gpu_debug_records_scan")
 
 # every symbol include/fourmc_gpu.h and include/fourmc.h declare
 _GPU_API = {
@@ -107,6 +120,10 @@ _GPU_API = {
     "fourmc_gpu_image_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_decode_blocks": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_read": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "fourmc_gpu_image_align_slices": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "fourmc_gpu_image_read_records": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint8, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                C.c_uint64, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_debug_records_scan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint8, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_writer_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_image_writer_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "fourmc_gpu_image_writer_finish": (C.c_int, [C.c_void_p, C.c_void_p]),

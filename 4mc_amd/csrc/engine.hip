@@ -1091,6 +1091,159 @@ int fourmc_gpu_image_read(const void* d_image, uint64_t image_bytes, fourmc_imag
     return FOURMC_OK;
 }
 
+// ------------------------------------------------------------------------ the line records of a split (records.hip)
+// Two read-backs: the summary, then the aligned slices.  An image without blocks leaves every slice as it came (getSplits'
+// "leave the default split for empty block index").
+int fourmc_gpu_image_align_slices(const void* d_image, uint64_t image_bytes, fourmc_image_slice* slices, uint32_t nslices, void* stream)
+{
+    if (nslices && !slices) { snprintf(g_err, sizeof g_err, "image_align_slices: null slices"); return FOURMC_EINVAL; }
+    if (!d_image) { snprintf(g_err, sizeof g_err, "image_align_slices: null image"); return FOURMC_EINVAL; }
+    if (int r = ensure_device()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    WsLease ws(&g_img_ws);
+    fourmc_image_index_dev idx;
+    if (int r = image_index_count(ws, s, d_image, image_bytes, &idx)) return r;
+    const int64_t code = idx.info.nblocks < 0 ? idx.info.nblocks : idx.info.framing;
+    if (code != 0 || idx.info.nblocks == 0) {
+        for (uint32_t i = 0; i < nslices; i++) {
+            slices[i].split_start = slices[i].start; slices[i].split_end = slices[i].end;
+            slices[i].first_block = slices[i].block_count = 0;
+            slices[i].result = code != 0 ? code : 1;
+        }
+        return FOURMC_OK;
+    }
+    if (!nslices) return FOURMC_OK;
+    const uint32_t n = uint32_t(idx.info.nblocks);
+    const size_t o_ent = kIdxBytes, o_sl = o_ent + align256(size_t(n) * sizeof(fourmc_image_entry));
+    void* w = nullptr;
+    if (int r = ws.get(s, o_sl + size_t(nslices) * sizeof(fourmc_image_slice), &w)) return r;
+    char* base = static_cast<char*>(w);
+    auto* d_idx = reinterpret_cast<fourmc_image_index_dev*>(base);
+    auto* d_ent = reinterpret_cast<fourmc_image_entry*>(base + o_ent);
+    auto* d_sl = reinterpret_cast<fourmc_image_slice*>(base + o_sl);
+    HIP_TRY(hipMemcpyAsync(d_sl, slices, size_t(nslices) * sizeof(fourmc_image_slice), hipMemcpyHostToDevice, s));
+    HIP_TRY(fourmc_launch_image_index(d_image, image_bytes, d_idx, d_ent, n, s));
+    HIP_TRY(fourmc_launch_image_align(d_ent, n, image_bytes, d_sl, nslices, s));
+    std::vector<fourmc_image_slice> back(nslices);
+    HIP_TRY(hipMemcpyAsync(back.data(), d_sl, size_t(nslices) * sizeof(fourmc_image_slice), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    memcpy(slices, back.data(), size_t(nslices) * sizeof(fourmc_image_slice));
+    return FOURMC_OK;
+}
+
+namespace {
+// The delimiter scan over d[0, len), count - finish - write; d_cnt holds fourmc_records_tiles(d, len) words.
+int records_scan(const void* d, uint64_t len, uint8_t delim, uint64_t* d_cnt, const fourmc_block* d_desc, uint32_t ndesc,
+                 int first_split, uint64_t ds, uint64_t body, uint64_t* d_starts, uint64_t starts_cap, fourmc_records_state* d_st,
+                 hipStream_t s)
+{
+    const uint64_t ntiles = fourmc_records_tiles(d, len);
+    if (ntiles > 0x7FFFFFFFull) { snprintf(g_err, sizeof g_err, "image_read_records: %llu bytes in one split", (unsigned long long)len); return FOURMC_EUNSUP; }
+    HIP_TRY(fourmc_launch_records_count(d, len, delim, d_cnt, ntiles, s));
+    HIP_TRY(fourmc_launch_records_finish(d, len, delim, d_cnt, ntiles, d_desc, ndesc, first_split, ds, body, d_starts, starts_cap, d_st, s));
+    if (d_starts) HIP_TRY(fourmc_launch_records_write(d, len, delim, d_cnt, ntiles, d_st, d_starts, s));
+    return FOURMC_OK;
+}
+// tile counts of any destination of `len` bytes (its address may add one chunk)
+size_t records_cnt_bytes(uint64_t len) { return size_t((len + 16) / FOURMC_RECORDS_TILE + 2) * sizeof(uint64_t); }
+} // namespace
+
+// Read-backs: the summary; the plan (the split's blocks and decoded offsets); one per tail block staged in search of hi; the
+// result.  Between the last two: the body's descriptors, ONE container decode straight into d_dst, the copy of the last tail
+// block's prefix out of staging, and the scan.
+int fourmc_gpu_image_read_records(const void* d_image, uint64_t image_bytes, uint64_t split_start, uint64_t split_end, uint8_t delim,
+                                  void* d_dst, uint64_t dst_cap, uint64_t* d_starts, uint64_t starts_cap,
+                                  fourmc_image_records* out, void* stream)
+{
+    if (!out) { snprintf(g_err, sizeof g_err, "image_read_records: null result"); return FOURMC_EINVAL; }
+    if (!d_image) { snprintf(g_err, sizeof g_err, "image_read_records: null image"); return FOURMC_EINVAL; }
+    if (!d_dst) { snprintf(g_err, sizeof g_err, "image_read_records: null destination"); return FOURMC_EINVAL; }
+    if (int r = ensure_device()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    memset(out, 0, sizeof *out);
+    WsLease ws(&g_img_ws);
+    fourmc_image_index_dev idx;
+    if (int r = image_index_count(ws, s, d_image, image_bytes, &idx)) return r;
+    const int64_t code = idx.info.nblocks < 0 ? idx.info.nblocks : idx.info.framing;
+    if (code != 0) { out->result = code; return FOURMC_OK; }
+    const uint32_t n = uint32_t(idx.info.nblocks);
+    const size_t o_plan = kIdxBytes, o_tail = o_plan + 256, o_st = o_tail + 256, o_ent = o_st + 256;
+    const size_t o_desc = o_ent + align256(size_t(n) * sizeof(fourmc_image_entry));
+    const size_t o_cnt = o_desc + align256((size_t(n) + 1) * sizeof(fourmc_block));
+    void* w = nullptr;
+    if (int r = ws.get(s, o_cnt + records_cnt_bytes(std::min(dst_cap, idx.info.total_bytes)), &w)) return r;
+    char* base = static_cast<char*>(w);
+    auto* d_idx = reinterpret_cast<fourmc_image_index_dev*>(base);
+    auto* d_plan = reinterpret_cast<fourmc_records_plan*>(base + o_plan);
+    auto* d_tail = reinterpret_cast<fourmc_records_tail*>(base + o_tail);
+    auto* d_st = reinterpret_cast<fourmc_records_state*>(base + o_st);
+    auto* d_ent = reinterpret_cast<fourmc_image_entry*>(base + o_ent);
+    auto* d_desc = reinterpret_cast<fourmc_block*>(base + o_desc);
+    auto* d_cnt = reinterpret_cast<uint64_t*>(base + o_cnt);
+    HIP_TRY(fourmc_launch_image_index(d_image, image_bytes, d_idx, d_ent, n, s));
+    HIP_TRY(fourmc_launch_records_plan(d_ent, n, d_idx, split_start, split_end, d_plan, s));
+    fourmc_records_plan plan;
+    HIP_TRY(hipMemcpyAsync(&plan, d_plan, sizeof plan, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (plan.code != 0) { out->result = plan.code; return FOURMC_OK; }
+    out->base = plan.ds;
+    // hi: behind the first delimiter at or after de.  The blocks from b1 on go through the staging slot one at a time until one
+    // shows a delimiter; bt is that block (n: the content ends first) and its prefix is still in the slot afterwards.
+    uint64_t hi = plan.total;
+    uint32_t bt = n;
+    fourmc_records_tail tail = {};
+    char* d_stage = nullptr;
+    WsLease ws2(&g_img_stage);
+    if (plan.b1 < n) {
+        void* w2 = nullptr;
+        if (int r = ws2.get(s, size_t(FOURMC_BLOCKSIZE) + 64, &w2)) return r;
+        d_stage = static_cast<char*>(w2);
+    }
+    for (uint32_t b = plan.b1; b < n; b++) {
+        HIP_TRY(fourmc_launch_records_desc(d_ent, b, 1, 0, 1, d_desc, s));
+        if (int r = fourmc_gpu_4mc_decode_blocks(d_image, d_stage, d_desc, 1, image_codec(idx), s)) return r;
+        HIP_TRY(fourmc_launch_records_tail_find(d_stage, d_desc, d_ent, b, delim, d_tail, s));
+        HIP_TRY(hipMemcpyAsync(&tail, d_tail, sizeof tail, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (tail.code != 0) { out->result = tail.code; return FOURMC_OK; }
+        if (tail.found) { bt = b; hi = tail.hi; break; }
+    }
+    const uint64_t len = hi - plan.ds;
+    if (len > dst_cap) { out->result = -5; out->data_bytes = len; return FOURMC_OK; }
+    const uint32_t count = bt - plan.b0;
+    if (count) {
+        HIP_TRY(fourmc_launch_records_desc(d_ent, plan.b0, count, plan.ds, 0, d_desc, s));
+        if (int r = fourmc_gpu_4mc_decode_blocks(d_image, d_dst, d_desc, count, image_codec(idx), s)) return r;
+    }
+    if (bt < n && hi > tail.data_off)
+        HIP_TRY(hipMemcpyAsync(static_cast<char*>(d_dst) + (tail.data_off - plan.ds), d_stage, hi - tail.data_off, hipMemcpyDeviceToDevice, s));
+    if (int r = records_scan(d_dst, len, delim, d_cnt, d_desc, count, split_start == 0, plan.ds, plan.de - plan.ds, d_starts, starts_cap, d_st, s)) return r;
+    fourmc_records_state st;
+    HIP_TRY(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = st.r;
+    return FOURMC_OK;
+}
+
+#ifdef FOURMC_RESEARCH
+int fourmc_gpu_debug_records_scan(const void* d, uint64_t len, uint8_t delim, uint64_t* d_starts, uint64_t starts_cap,
+                                  int64_t* records, void* stream)
+{
+    if (!records || (len && !d)) { snprintf(g_err, sizeof g_err, "debug_records_scan: null pointer"); return FOURMC_EINVAL; }
+    if (int r = ensure_device()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    WsLease ws(&g_img_ws); void* w = nullptr;
+    if (int r = ws.get(s, 256 + records_cnt_bytes(len), &w)) return r;
+    auto* d_st = static_cast<fourmc_records_state*>(w);
+    if (int r = records_scan(d, len, delim, reinterpret_cast<uint64_t*>(static_cast<char*>(w) + 256), nullptr, 0, 1, 0, len, d_starts, starts_cap, d_st, s)) return r;
+    fourmc_records_state st;
+    HIP_TRY(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *records = st.r.result;
+    return FOURMC_OK;
+}
+#endif
+
 // ------------------------------------------------------------------------ host-buffer API
 int fourmc_LZ4_compressBound(int n) { return (unsigned)n > 0x7E000000u ? 0 : n + n / 255 + 16; }
 

@@ -206,6 +206,46 @@ hipError_t fourmc_launch_image_rd_fold(const fourmc_block* d_desc, const uint64_
 /* the deferred checks with N = image_bytes, the DST_SMALL rule and the fold into *d_status */
 hipError_t fourmc_launch_image_rd_finish(const fourmc_image_rd_state* d_st, uint64_t image_bytes, uint64_t dst_cap,
                                          fourmc_image_status* d_status, hipStream_t s);
+/* the line records of a split (records.hip): what the split's offsets resolve to, read back before anything is decoded */
+typedef struct fourmc_records_plan {
+    int64_t  code;          /* 0, or -3: a split offset that is neither 0 / a block header nor at or past the end mark */
+    uint64_t ds, de;        /* decoded offsets of the blocks at split_start and split_end (0 / total_bytes when there is none) */
+    uint64_t total;         /* total decoded size */
+    uint32_t b0, b1;        /* the split's blocks are [b0, b1); b1 == nblocks when split_end is no block header */
+} fourmc_records_plan;
+/* one staged tail block, read back after its scan */
+typedef struct fourmc_records_tail {
+    int64_t  code;          /* 0, or -4: the block failed its XXH32 or its decode, or decoded to another size than its usize */
+    uint64_t data_off;      /* decoded offset of the block's first byte */
+    uint64_t hi;            /* found: decoded offset just behind the block's first delimiter */
+    uint32_t found, pad;
+} fourmc_records_tail;
+/* the call's result on the device, and what the finish kernel tells the write kernel */
+typedef struct fourmc_records_state {
+    fourmc_image_records r;
+    uint32_t write;         /* 1: the starts are to be written */
+    uint32_t shift;         /* index of the start behind the first delimiter: 1 when the split starts the file, else 0 */
+} fourmc_records_state;
+#define FOURMC_RECORDS_TILE (16u * 1024u)       /* bytes one wave scans: one count per tile */
+hipError_t fourmc_launch_image_align(const fourmc_image_entry* d_ent, uint32_t n, uint64_t image_bytes,
+                                     fourmc_image_slice* d_slices, uint32_t nslices, hipStream_t s);
+hipError_t fourmc_launch_records_plan(const fourmc_image_entry* d_ent, uint32_t n, const fourmc_image_index_dev* d_idx,
+                                      uint64_t split_start, uint64_t split_end, fourmc_records_plan* d_plan, hipStream_t s);
+/* descriptors of blocks [first, first + count) with block i at data_off[i] - ds of the decode's destination (to_stage: at 0) */
+hipError_t fourmc_launch_records_desc(const fourmc_image_entry* d_ent, uint32_t first, uint32_t count, uint64_t ds, int to_stage,
+                                      fourmc_block* d_desc, hipStream_t s);
+/* after block b has been decoded to d_stage through *d_desc: its verdict and its first delimiter */
+hipError_t fourmc_launch_records_tail_find(const void* d_stage, const fourmc_block* d_desc, const fourmc_image_entry* d_ent,
+                                           uint32_t b, uint8_t delim, fourmc_records_tail* d_tail, hipStream_t s);
+/* tiles of d[0, len): FOURMC_RECORDS_TILE bytes each, counted from d rounded down to 16 bytes */
+uint64_t   fourmc_records_tiles(const void* d, uint64_t len);
+hipError_t fourmc_launch_records_count(const void* d, uint64_t len, uint8_t delim, uint64_t* d_cnt, uint64_t ntiles, hipStream_t s);
+/* the counts into their exclusive prefix (in place), the body blocks' verdict, the ownership rule: *d_st */
+hipError_t fourmc_launch_records_finish(const void* d, uint64_t len, uint8_t delim, uint64_t* d_cnt, uint64_t ntiles,
+                                        const fourmc_block* d_desc, uint32_t ndesc, int first_split, uint64_t ds, uint64_t body,
+                                        uint64_t* d_starts, uint64_t starts_cap, fourmc_records_state* d_st, hipStream_t s);
+hipError_t fourmc_launch_records_write(const void* d, uint64_t len, uint8_t delim, const uint64_t* d_cnt, uint64_t ntiles,
+                                       const fourmc_records_state* d_st, uint64_t* d_starts, hipStream_t s);
 #ifdef FOURMC_RESEARCH      /* the research side build exports these two: tools/zstd_timing.py and tools/k7x_prof.py size their read-backs with them */
 #pragma GCC visibility push(default)
 #endif

@@ -1,0 +1,371 @@
+// 4mc_amd/csrc/records.hip — the line records of a Hadoop split (fourmc_gpu_image_align_slices / _image_read_records).
+//
+// Alignment and planning are index work, one lane per slice or one lane in all: binary searches over the footer index
+// (FourMcBlockIndex.java:92-173).  The hot path is the delimiter scan over the decoded bytes of a split, count - scan - write:
+//   count   one wave per 16 KiB tile: 16 bytes per lane and step, a 16-bit match mask per lane, popcounts summed over the wave;
+//   finish  one workgroup: the tile counts into their 64-bit exclusive prefix in place, the first delimiter (which a split that
+//           does not start the file drops), the body blocks' verdict, and the ownership rule into the call's result;
+//   write   the count kernel's walk again; a wave prefix of the popcounts (DPP) puts each lane's starts behind the tile's base.
+// The data is read twice and every start written once.  A single pass with decoupled look-back would read it once, but its
+// workgroups spin on their predecessors' flags; two plain launches need no forward-progress assumption, and the second read of
+// a split costs far less than its decode did ("Line records").
+// The bytes are addressed in 16-byte chunks from the destination rounded DOWN to 16: aligned loads never leave the pages the
+// destination's own bytes lie in, and the bytes of the first and last chunk that are not the destination's are masked out.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "fourmc_gpu.h"
+#include "kernels.h"
+
+namespace {
+
+constexpr uint32_t kTileChunks = FOURMC_RECORDS_TILE / 16;     // 16-byte chunks of one wave's tile
+constexpr uint32_t kSteps = kTileChunks / 64;                  // steps of 64 lanes x 16 bytes
+constexpr uint32_t kWaves = 4;                                 // tiles per workgroup
+
+// wave64 inclusive prefix sum (image.hip: scan_add)
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ uint32_t dpp0(uint32_t v)
+{ return uint32_t(__builtin_amdgcn_update_dpp(0, int(v), CTRL, ROWMASK, 0xf, false)); }
+__device__ __forceinline__ uint32_t scan_add(uint32_t v)
+{
+    v += dpp0<0x111, 0xf>(v); v += dpp0<0x112, 0xf>(v); v += dpp0<0x114, 0xf>(v); v += dpp0<0x118, 0xf>(v);
+    v += dpp0<0x142, 0xa>(v);
+    v += dpp0<0x143, 0xc>(v);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_total(uint32_t incl) { return uint32_t(__builtin_amdgcn_readlane(int(incl), 63)); }
+
+// bit k: byte k of the word equals the pattern's byte.  x = w ^ pat has a zero byte there; bit 7 of each byte of t says "not
+// zero" without a carry between bytes; the multiply gathers bits 0, 8, 16, 24 into bits 24..27 (no two products share a bit).
+__device__ __forceinline__ uint32_t match4(uint32_t w, uint32_t pat)
+{
+    const uint32_t x = w ^ pat;
+    const uint32_t t = ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x;
+    return (((~t & 0x80808080u) >> 7) * 0x01020408u) >> 24;
+}
+__device__ __forceinline__ uint32_t match16(const uint4& v, uint32_t pat)
+{ return match4(v.x, pat) | (match4(v.y, pat) << 4) | (match4(v.z, pat) << 8) | (match4(v.w, pat) << 12); }
+
+// d[0, len) as chunks: chunk c holds the bytes [16 c - head, 16 c - head + 16) of d
+struct Span {
+    const uint4* base;
+    uint32_t head;          // bytes of chunk 0 before d[0]
+    uint64_t end;           // head + len
+    uint64_t nchunks;
+    __host__ __device__ Span(const void* d, uint64_t len)
+    {
+        const uintptr_t p = reinterpret_cast<uintptr_t>(d);
+        head = uint32_t(p & 15); base = reinterpret_cast<const uint4*>(p - head);
+        end = head + len; nchunks = (end + 15) / 16;
+    }
+    // the bytes of chunk c < nchunks that are d's
+    __device__ __forceinline__ uint32_t valid(uint64_t c) const
+    {
+        const uint64_t a = 16 * c;
+        uint32_t m = 0xffffu;
+        if (a < head) m = (m << (head - a)) & 0xffffu;
+        if (end - a < 16) m &= 0xffffu >> (16 - (end - a));
+        return m;
+    }
+    // a tile whose every chunk lies wholly inside d
+    __device__ __forceinline__ bool inner(uint64_t tile) const
+    { return (tile > 0 || head == 0) && (tile + 1) * uint64_t(FOURMC_RECORDS_TILE) <= end; }
+    __device__ __forceinline__ uint32_t mask(uint64_t c, uint32_t pat) const
+    { return c < nchunks ? match16(base[c], pat) & valid(c) : 0u; }
+};
+
+__device__ __forceinline__ uint32_t pattern(uint8_t delim) { return uint32_t(delim) * 0x01010101u; }
+
+// ------------------------------------------------------------------------------------------------------------- index work
+// first block whose header offset is >= pos; n if none (findNextPosition, FourMcBlockIndex.java:87-104)
+__device__ uint32_t next_block(const fourmc_image_entry* ent, uint32_t n, uint64_t pos)
+{
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (ent[mid].image_off >= pos) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// one lane per slice: alignSliceStartToIndex / alignSliceEndToIndex (FourMcBlockIndex.java:142-173), fileSize = image_bytes
+__global__ __launch_bounds__(256)
+void image_align_kernel(const fourmc_image_entry* __restrict__ ent, uint32_t n, uint64_t image_bytes,
+                        fourmc_image_slice* __restrict__ slices, uint32_t nslices)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nslices) return;
+    fourmc_image_slice q = slices[i];
+    const uint32_t j = next_block(ent, n, q.end);
+    q.split_end = j < n ? ent[j].image_off : image_bytes;
+    uint32_t first = 0;
+    bool kept = true;
+    q.split_start = 0;
+    if (q.start != 0) {
+        first = next_block(ent, n, q.start);
+        kept = first < n && ent[first].image_off < q.end;
+        q.split_start = kept ? ent[first].image_off : ~uint64_t(0);
+    }
+    q.first_block = kept ? first : 0;
+    q.block_count = kept ? j - first : 0;
+    q.result = kept ? 1 : 0;
+    slices[i] = q;
+}
+
+// one lane: the split's offsets into blocks and decoded offsets
+__global__ __launch_bounds__(64)
+void records_plan_kernel(const fourmc_image_entry* __restrict__ ent, uint32_t n, const fourmc_image_index_dev* __restrict__ idx,
+                         uint64_t split_start, uint64_t split_end, fourmc_records_plan* __restrict__ plan)
+{
+    if (threadIdx.x != 0) return;
+    fourmc_records_plan p = {};
+    p.total = idx->info.total_bytes;
+    p.de = p.total; p.b1 = n;
+    if (split_start != 0) {
+        const uint32_t b = next_block(ent, n, split_start);
+        if (b < n && ent[b].image_off == split_start) { p.b0 = b; p.ds = ent[b].data_off; }
+        else p.code = -3;
+    }
+    if (split_end < idx->data_end) {
+        const uint32_t b = next_block(ent, n, split_end);
+        if (b < n && ent[b].image_off == split_end && split_end >= split_start) { p.b1 = b; p.de = ent[b].data_off; }
+        else p.code = -3;
+    }
+    *plan = p;
+}
+
+__global__ __launch_bounds__(256)
+void records_desc_kernel(const fourmc_image_entry* __restrict__ ent, uint32_t first, uint32_t count, uint64_t ds, int to_stage,
+                         fourmc_block* __restrict__ desc)
+{
+    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= count) return;
+    const fourmc_image_entry e = ent[first + b];
+    fourmc_block d;
+    d.src_off = e.image_off + 12; d.dst_off = to_stage ? 0 : e.data_off - ds; d.src_len = e.csize; d.dst_cap = e.usize; d.result = 0; d.xxh32 = e.xxh32;
+    desc[b] = d;
+}
+
+__device__ __forceinline__ bool block_bad(const fourmc_block& d) { return d.result < 0 || uint32_t(d.result) != d.dst_cap; }
+
+// One workgroup over a staged block (16-byte aligned): its verdict, and its first delimiter, 16 KiB per step until one shows.
+__global__ __launch_bounds__(1024)
+void records_tail_find_kernel(const uint8_t* __restrict__ stage, const fourmc_block* __restrict__ desc,
+                              const fourmc_image_entry* __restrict__ ent, uint32_t b, uint8_t delim, fourmc_records_tail* __restrict__ out)
+{
+    __shared__ uint32_t first;
+    const fourmc_block d = *desc;
+    const fourmc_image_entry e = ent[b];
+    fourmc_records_tail r = {};
+    r.data_off = e.data_off;
+    if (block_bad(d)) {
+        r.code = -4;
+        if (threadIdx.x == 0) *out = r;
+        return;
+    }
+    const Span sp(stage, e.usize);
+    const uint32_t pat = pattern(delim);
+    if (threadIdx.x == 0) first = ~0u;
+    __syncthreads();
+    for (uint64_t c0 = 0; c0 < sp.nchunks; c0 += 1024) {
+        const uint64_t c = c0 + threadIdx.x;
+        const uint32_t m = sp.mask(c, pat);
+        if (m) atomicMin(&first, uint32_t(16 * c) + uint32_t(__builtin_ctz(m)));
+        if (__syncthreads_or(m != 0)) break;
+    }
+    if (threadIdx.x == 0) {
+        if (first != ~0u) { r.found = 1; r.hi = e.data_off + first + 1; }
+        *out = r;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------- the scan
+// one wave per tile: the delimiters of its 16 KiB
+__global__ __launch_bounds__(64 * kWaves)
+void records_count_kernel(const uint8_t* __restrict__ d, uint64_t len, uint32_t pat, uint64_t* __restrict__ cnt, uint64_t ntiles)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t tile = uint64_t(blockIdx.x) * kWaves + (threadIdx.x >> 6);
+    if (tile >= ntiles) return;
+    const Span sp(d, len);
+    const uint64_t c0 = tile * kTileChunks + lane;
+    uint32_t k = 0;
+    if (sp.inner(tile)) {
+        for (uint32_t i = 0; i < kSteps; i += 4) {                 // 4 KiB of the wave in flight
+            const uint4 v0 = sp.base[c0 + 64 * i], v1 = sp.base[c0 + 64 * (i + 1)];
+            const uint4 v2 = sp.base[c0 + 64 * (i + 2)], v3 = sp.base[c0 + 64 * (i + 3)];
+            k += __popc(match16(v0, pat)) + __popc(match16(v1, pat)) + __popc(match16(v2, pat)) + __popc(match16(v3, pat));
+        }
+    } else {
+        for (uint32_t i = 0; i < kSteps; i++) k += __popc(sp.mask(c0 + 64 * i, pat));
+    }
+    for (int o = 32; o; o >>= 1) k += uint32_t(__shfl_xor(int(k), o));
+    if (lane == 0) cnt[tile] = k;
+}
+
+// One workgroup.  cnt[0, ntiles) becomes its exclusive prefix; then the ownership rule on the total, the first delimiter's
+// position and the last byte (fourmc_gpu.h).  `body` = de - ds: a split that does not start the file owns something only when
+// its first delimiter lies below it.  The start before the first record of a file and the end behind an unterminated last
+// record have no delimiter in front of them: they are written here.
+__global__ __launch_bounds__(1024)
+void records_finish_kernel(const uint8_t* __restrict__ d, uint64_t len, uint32_t pat, uint64_t* __restrict__ cnt, uint64_t ntiles,
+                           const fourmc_block* __restrict__ desc, uint32_t ndesc, int first_split, uint64_t ds, uint64_t body,
+                           uint64_t* __restrict__ starts, uint64_t starts_cap, fourmc_records_state* __restrict__ st)
+{
+    __shared__ uint64_t wsum[16];
+    __shared__ unsigned long long tile0;
+    __shared__ uint32_t in_tile;
+    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+    if (t == 0) { tile0 = ~0ull; in_tile = ~0u; }
+    bool bad = false;
+    for (uint32_t i = t; i < ndesc; i += 1024) bad |= block_bad(desc[i]);
+    const int any_bad = __syncthreads_or(bad);
+    // each thread a contiguous run of tiles; a 64-bit wave scan and the 16 wave totals order the runs
+    const uint64_t per = (ntiles + 1023) / 1024, a = min(ntiles, t * per), z = min(ntiles, a + per);
+    uint64_t mine = 0, nz = ~0ull;
+    for (uint64_t i = a; i < z; i++) { const uint64_t c = cnt[i]; if (c && nz == ~0ull) nz = i; mine += c; }
+    if (nz != ~0ull) atomicMin(&tile0, (unsigned long long)nz);
+    uint64_t incl = mine;
+    for (int o = 1; o < 64; o <<= 1) { const uint64_t v = uint64_t(__shfl_up((unsigned long long)incl, o)); if (int(lane) >= o) incl += v; }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    uint64_t run = 0, total = 0;
+    for (uint32_t j = 0; j < 16; j++) { if (j < w) run += wsum[j]; total += wsum[j]; }
+    run += incl - mine;
+    for (uint64_t i = a; i < z; i++) { const uint64_t c = cnt[i]; cnt[i] = run; run += c; }
+    // the first delimiter: in the first tile that counted one
+    const Span sp(d, len);
+    if (total) {
+        const uint32_t m = sp.mask(uint64_t(tile0) * kTileChunks + t, pat);
+        if (m) atomicMin(&in_tile, 16 * t + uint32_t(__builtin_ctz(m)));
+    }
+    __syncthreads();
+    if (t != 0) return;
+    fourmc_records_state s = {};
+    s.r.base = ds;
+    if (any_bad) { s.r.result = -4; *st = s; return; }
+    const bool open_end = len > 0 && d[len - 1] != uint8_t(pat);         // an unterminated last record
+    uint64_t lo = 0, records = 0;
+    if (first_split) records = total + (open_end ? 1 : 0);
+    else if (total) {
+        const uint64_t p0 = uint64_t(tile0) * FOURMC_RECORDS_TILE + in_tile - sp.head;
+        if (p0 < body) { lo = p0 + 1; records = total - 1 + (open_end ? 1 : 0); }
+    }
+    if (starts && records + 1 > starts_cap) {
+        s.r.result = -5; s.r.data_off = records ? lo : 0; s.r.data_bytes = len; s.r.reserved = records;
+    } else if (records == 0) {
+        if (starts) starts[0] = 0;
+    } else {
+        s.r.result = int64_t(records); s.r.data_off = lo; s.r.data_bytes = len;
+        if (starts) {
+            s.write = 1; s.shift = first_split ? 1 : 0;
+            if (first_split) starts[0] = 0;
+            if (open_end) starts[records] = len;
+        }
+    }
+    *st = s;
+}
+
+// the count kernel's walk; the start behind delimiter number r of d goes to starts[shift + r]
+__global__ __launch_bounds__(64 * kWaves)
+void records_write_kernel(const uint8_t* __restrict__ d, uint64_t len, uint32_t pat, const uint64_t* __restrict__ base, uint64_t ntiles,
+                          const fourmc_records_state* __restrict__ st, uint64_t* __restrict__ starts)
+{
+    if (!st->write) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t tile = uint64_t(blockIdx.x) * kWaves + (threadIdx.x >> 6);
+    if (tile >= ntiles) return;
+    const Span sp(d, len);
+    const uint64_t c0 = tile * kTileChunks + lane;
+    uint64_t run = base[tile] + st->shift;
+    const bool inner = sp.inner(tile);
+    for (uint32_t i0 = 0; i0 < kSteps; i0 += 4) {
+        uint32_t m[4];
+        if (inner) {
+            const uint4 v0 = sp.base[c0 + 64 * i0], v1 = sp.base[c0 + 64 * (i0 + 1)];
+            const uint4 v2 = sp.base[c0 + 64 * (i0 + 2)], v3 = sp.base[c0 + 64 * (i0 + 3)];
+            m[0] = match16(v0, pat); m[1] = match16(v1, pat); m[2] = match16(v2, pat); m[3] = match16(v3, pat);
+        } else {
+            for (uint32_t j = 0; j < 4; j++) m[j] = sp.mask(c0 + 64 * (i0 + j), pat);
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            const uint32_t k = __popc(m[j]);
+            const uint32_t incl = scan_add(k);
+            uint64_t o = run + (incl - k);
+            const uint64_t at = 16 * (c0 + 64 * (i0 + j)) + 1 - sp.head;      // the start behind byte 0 of the chunk
+            for (uint32_t mm = m[j]; mm; mm &= mm - 1) starts[o++] = at + uint32_t(__builtin_ctz(mm));
+            run += wave_total(incl);
+        }
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+hipError_t fourmc_launch_image_align(const fourmc_image_entry* d_ent, uint32_t n, uint64_t image_bytes,
+                                     fourmc_image_slice* d_slices, uint32_t nslices, hipStream_t s)
+{
+    if (!nslices) return hipSuccess;
+    hipLaunchKernelGGL(image_align_kernel, dim3((nslices + 255) / 256), dim3(256), 0, s, d_ent, n, image_bytes, d_slices, nslices);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_records_plan(const fourmc_image_entry* d_ent, uint32_t n, const fourmc_image_index_dev* d_idx,
+                                      uint64_t split_start, uint64_t split_end, fourmc_records_plan* d_plan, hipStream_t s)
+{
+    hipLaunchKernelGGL(records_plan_kernel, dim3(1), dim3(64), 0, s, d_ent, n, d_idx, split_start, split_end, d_plan);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_records_desc(const fourmc_image_entry* d_ent, uint32_t first, uint32_t count, uint64_t ds, int to_stage,
+                                      fourmc_block* d_desc, hipStream_t s)
+{
+    if (!count) return hipSuccess;
+    hipLaunchKernelGGL(records_desc_kernel, dim3((count + 255) / 256), dim3(256), 0, s, d_ent, first, count, ds, to_stage, d_desc);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_records_tail_find(const void* d_stage, const fourmc_block* d_desc, const fourmc_image_entry* d_ent,
+                                           uint32_t b, uint8_t delim, fourmc_records_tail* d_tail, hipStream_t s)
+{
+    hipLaunchKernelGGL(records_tail_find_kernel, dim3(1), dim3(1024), 0, s, static_cast<const uint8_t*>(d_stage), d_desc, d_ent, b,
+                       delim, d_tail);
+    return hipGetLastError();
+}
+
+uint64_t fourmc_records_tiles(const void* d, uint64_t len)
+{
+    if (!len) return 0;
+    const Span sp(d, len);
+    return (sp.nchunks + kTileChunks - 1) / kTileChunks;
+}
+
+hipError_t fourmc_launch_records_count(const void* d, uint64_t len, uint8_t delim, uint64_t* d_cnt, uint64_t ntiles, hipStream_t s)
+{
+    if (!ntiles) return hipSuccess;
+    hipLaunchKernelGGL(records_count_kernel, dim3(uint32_t((ntiles + kWaves - 1) / kWaves)), dim3(64 * kWaves), 0, s,
+                       static_cast<const uint8_t*>(d), len, uint32_t(delim) * 0x01010101u, d_cnt, ntiles);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_records_finish(const void* d, uint64_t len, uint8_t delim, uint64_t* d_cnt, uint64_t ntiles,
+                                        const fourmc_block* d_desc, uint32_t ndesc, int first_split, uint64_t ds, uint64_t body,
+                                        uint64_t* d_starts, uint64_t starts_cap, fourmc_records_state* d_st, hipStream_t s)
+{
+    hipLaunchKernelGGL(records_finish_kernel, dim3(1), dim3(1024), 0, s, static_cast<const uint8_t*>(d), len,
+                       uint32_t(delim) * 0x01010101u, d_cnt, ntiles, d_desc, ndesc, first_split, ds, body, d_starts, starts_cap, d_st);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_records_write(const void* d, uint64_t len, uint8_t delim, const uint64_t* d_cnt, uint64_t ntiles,
+                                       const fourmc_records_state* d_st, uint64_t* d_starts, hipStream_t s)
+{
+    if (!ntiles) return hipSuccess;
+    hipLaunchKernelGGL(records_write_kernel, dim3(uint32_t((ntiles + kWaves - 1) / kWaves)), dim3(64 * kWaves), 0, s,
+                       static_cast<const uint8_t*>(d), len, uint32_t(delim) * 0x01010101u, d_cnt, ntiles, d_st, d_starts);
+    return hipGetLastError();
+}
+
+} // extern "C"

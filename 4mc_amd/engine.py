@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from .binding import (BLOCK_DTYPE, CODEC_LZ4_FAST, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageIndexInfo, ImageRange,
-                      ImageStatus, check, lib)
+                      ImageRecords, ImageSlice, ImageStatus, check, lib)
 
 
 def _stream_ptr(stream):
@@ -196,6 +196,39 @@ def image_read(d_image, ranges, d_dst, image_bytes=None, stream=None):
         arr[i].offset, arr[i].length, arr[i].dst_off, arr[i].result = o, ln, d, 0
     check(lib().fourmc_gpu_image_read(ptr, n, C.cast(arr, C.c_void_p), len(q), dst, d_dst.numel(), _stream_ptr(stream)), "fourmc_gpu_image_read")
     return np.array([arr[i].result for i in range(len(q))], dtype=np.int64)
+
+
+def image_align_slices(d_image, slices, image_bytes=None, stream=None):
+    """Raw byte slices [(start, end), ...] of the image file, as FileInputFormat cuts them, aligned to block headers on the device
+    (FourMcInputFormat.getSplits' inner step).  Returns one dict per slice: start, end, split_start, split_end, first_block,
+    block_count and result (1 kept, 0 dropped, or the index code of an image that cannot be indexed)."""
+    ptr = _dev_ptr(d_image, "image_align_slices d_image")
+    n = _image_len(d_image, image_bytes, "image_align_slices")
+    q = np.asarray(slices, dtype=np.uint64).reshape(-1, 2)
+    arr = (ImageSlice * len(q))()
+    for i, (a, z) in enumerate(q.tolist()):
+        arr[i].start, arr[i].end = a, z
+    check(lib().fourmc_gpu_image_align_slices(ptr, n, C.cast(arr, C.c_void_p), len(q), _stream_ptr(stream)), "fourmc_gpu_image_align_slices")
+    return [{name: int(getattr(arr[i], name)) for name, _ in ImageSlice._fields_} for i in range(len(q))]
+
+
+def image_read_records(d_image, split_start, split_end, d_dst, starts=None, delim=10, image_bytes=None, stream=None):
+    """The records (lines ending with the byte `delim`) that the split [split_start, split_end) of the image owns by the line
+    reader's rule: d_dst[:data_bytes] receives the decoded content from the split's first block on, `starts` (an int64 CUDA tensor,
+    or None to count only) the offset in d_dst of each record and, behind the last, data_bytes.  Returns the ImageRecords struct
+    (result: the records owned, or a negative code; include/fourmc_gpu.h)."""
+    ptr = _dev_ptr(d_image, "image_read_records d_image")
+    dst = _dev_ptr(d_dst, "image_read_records d_dst")
+    n = _image_len(d_image, image_bytes, "image_read_records")
+    sp, cap = 0, 0
+    if starts is not None:
+        if not (isinstance(starts, torch.Tensor) and starts.is_cuda and starts.is_contiguous() and starts.dtype == torch.int64):
+            raise EngineError("image_read_records starts: a contiguous int64 CUDA tensor is required")
+        sp, cap = int(starts.data_ptr()), starts.numel()
+    out = ImageRecords()
+    check(lib().fourmc_gpu_image_read_records(ptr, n, int(split_start), int(split_end), int(delim) & 0xFF, dst, d_dst.numel(), sp, cap,
+                                              C.byref(out), _stream_ptr(stream)), "fourmc_gpu_image_read_records")
+    return out
 
 
 class ImageWriter:

@@ -326,6 +326,62 @@ typedef struct fourmc_image_range { uint64_t offset, length, dst_off; int64_t re
 int fourmc_gpu_image_read(const void* d_image, uint64_t image_bytes, fourmc_image_range* ranges, uint32_t nranges,
                           void* d_dst, uint64_t dst_cap, void* stream);
 
+/* ---- the line records of a Hadoop split, from a single-stream image in device memory -----------------------------------------
+ * What FourMcInputFormat.getSplits and FourMcLineRecordReader do between them (java/hadoop-4mc: mapreduce/FourMcInputFormat.java:
+ * 159-168, mapreduce/FourMcLineRecordReader.java): a raw byte slice of the file is aligned to block headers, and the reader of the
+ * aligned split skips its first line unless it starts the file, then reads lines while its position is <= the split's end - so
+ * every line has exactly one owner.  Both calls obey the settings image_read obeys (FOURMC_DECODE, FOURMC_ZDECODE); no per-block
+ * data crosses to the host.  Synchronizations of `stream`: image_align_slices 2 (1 for an image without blocks); image_read_records
+ * 3 + one per staged tail block (usually 1; 0 when split_end is at or past the end mark; more only while a line longer than a
+ * block has shown no delimiter), less when a check ends the call early.
+ * Not reproduced: Hadoop's default LineReader also ends a line at a lone CR and strips CR LF; here the delimiter is ONE byte, a
+ * record includes it, and CR handling is the caller's.  There is no max.line.length truncation, and multi-stream images are refused
+ * as in the random-access group (the index code). */
+typedef struct fourmc_image_slice {       /* 48 bytes */
+    uint64_t start, end;                  /* in : raw byte slice [start, end) of the image, as FileInputFormat cuts it */
+    uint64_t split_start, split_end;      /* out: aligned as FourMcBlockIndex.java:142-173 with fileSize = image_bytes: what
+                                           *      fourmc_index_align_start / _align_end return (split_start ~0 when dropped) */
+    uint32_t first_block, block_count;    /* out: blocks whose headers lie in [split_start, split_end) (0, 0 when dropped) */
+    int64_t  result;                      /* out: 1 kept, 0 dropped (start found no block before end),
+                                           *      or info.nblocks / info.framing when the image cannot be indexed */
+} fourmc_image_slice;
+/* start == 0 stays 0, so [0, e) with e <= 12 is kept with zero blocks.  An image with an empty index (zero blocks) returns each
+ * slice unchanged with result = 1: the reference's "leave the default split". */
+int fourmc_gpu_image_align_slices(const void* d_image, uint64_t image_bytes, fourmc_image_slice* slices /*host*/, uint32_t n,
+                                  void* stream);
+/* The records of the split [split_start, split_end).  split_start must be 0 or the offset of a block header; split_end a block
+ * header's offset not below split_start, or any value at or past the end mark.  T: the total decoded size; ds: the decoded offset
+ * of the block at split_start (0 for 0); de: that of the block at split_end (T when it is no block header).  A record is a maximal
+ * run of bytes ending with `delim`, inclusive; the content's final unterminated run, if not empty, is a record too.  The split owns
+ * the records whose first byte s has s <= de and (split_start == 0 or s > ds):
+ *   lo = 0 when split_start == 0, else 1 + the position of the first delimiter in [ds, de) (none: the split owns nothing);
+ *   hi = 1 + the position of the first delimiter at or after de (none: T);  the owned records are the records of [lo, hi).
+ * Output: d_dst[0, hi - ds) = the content from ds, each block decoded where it belongs; d_starts[i] = offset in d_dst of record i,
+ * d_starts[records] = data_bytes.  d_starts NULL: count only.  Nothing owned: result 0, data_off = data_bytes = 0, d_starts[0] = 0.
+ * The blocks from split_end on that the last record reaches into are decoded one at a time into a staging slot kept with the
+ * stream, until one shows a delimiter, and never into d_dst beyond hi: of the last one only the prefix is copied.
+ * result, in order of precedence:
+ *   info.nblocks if < 0, else info.framing if != 0   the image cannot be indexed;
+ *   -3   a bad split offset;
+ *   -4   a block from split_end on, decoded in search of hi, failed its XXH32, failed to decode or decoded to a size other
+ *        than its usize (hi is then unknown);
+ *   -5   hi - ds > dst_cap: data_bytes = hi - ds, the smallest dst_cap that works, and nothing is written to d_dst;
+ *   -4   a block of [ds, hi) failed in one of those ways;
+ *   -5   records + 1 > starts_cap with d_starts not NULL: reserved = records, and nothing is written to d_starts;
+ *   the records owned (>= 0).
+ * The call never writes outside [d_dst, d_dst + dst_cap) or d_starts[0, starts_cap); bytes of d_dst from data_bytes on are
+ * unspecified. */
+typedef struct fourmc_image_records {     /* 40 bytes */
+    int64_t  result;      /* records owned (>= 0), or a negative code                               */
+    uint64_t base;        /* decoded offset of d_dst[0] = ds (0 for the index codes and -3)         */
+    uint64_t data_off;    /* offset in d_dst of the first owned record = lo - ds                    */
+    uint64_t data_bytes;  /* d_dst[0, data_bytes) = decoded content [ds, hi)                        */
+    uint64_t reserved;    /* the record count when result is the -5 of starts_cap, else 0           */
+} fourmc_image_records;
+int fourmc_gpu_image_read_records(const void* d_image, uint64_t image_bytes, uint64_t split_start, uint64_t split_end, uint8_t delim,
+                                  void* d_dst, uint64_t dst_cap, uint64_t* d_starts, uint64_t starts_cap,
+                                  fourmc_image_records* out /*host*/, void* stream);
+
 /* ---- host-buffer conveniences with the reference's per-block signatures ------------------- */
 /* These stage one block through HBM (H2D, one launch, D2H).  They exist so the JNI entry points
  * keep their exact one-call-one-block contract (SURVEY.md §8(b) "Batching constraint").        */
@@ -368,6 +424,11 @@ int  fourmc_gpu_debug_zstd_exec_counts(unsigned long long* executed, unsigned lo
  * descriptor offset, token offset. */
 int fourmc_gpu_debug_lz4_parse(const void* d_src, const void* d_dst, fourmc_block* d_blocks, uint32_t n, int container_mode,
                                void* host, size_t bytes, size_t* layout);
+/* Timing aid (tools/records_scan.py): the delimiter scan and compaction of fourmc_gpu_image_read_records alone, over bytes already
+ * decoded: d[0, len) as the content of a split that starts the file; *records (host) = the records, d_starts as there (NULL: count
+ * only; -5 in *records when starts_cap is too small).  Synchronizes once. */
+int fourmc_gpu_debug_records_scan(const void* d, uint64_t len, uint8_t delim, uint64_t* d_starts, uint64_t starts_cap,
+                                  int64_t* records, void* stream);
 /* one-block host calls (LZ4_* / ZSTD_* twins, JNI) made so far, and the launches that served them (concurrent calls share one) */
 void fourmc_debug_one_block_counters(unsigned long long* calls, unsigned long long* launches);
 
