@@ -53,7 +53,11 @@ class ImageRecords(C.Structure):
                 ("reserved", C.c_uint64)]
 
 
-assert C.sizeof(ImageSlice) == 48 and C.sizeof(ImageRecords) == 40
+class ImageLines(C.Structure):         # struct fourmc_image_lines: as ImageRecords, result = the lines owned
+    _fields_ = list(ImageRecords._fields_)
+
+
+assert C.sizeof(ImageSlice) == 48 and C.sizeof(ImageRecords) == 40 and C.sizeof(ImageLines) == 40
 IMAGE_ENTRY_DTYPE = np.dtype([("image_off", "<u8"), ("data_off", "<u8"), ("usize", "<u4"), ("csize", "<u4"),
                               ("xxh32", "<u4"), ("pad", "<u4")])
 assert C.sizeof(ImageEntry) == 32 and C.sizeof(ImageRange) == 32 and C.sizeof(ImageIndexInfo) == 32
@@ -82,7 +86,7 @@ _lib = None
 _product_lib = None
 # declared by include/fourmc_gpu.h under FOURMC_RESEARCH only: the product library does not export them
 _RESEARCH_ONLY = ("fourmc_gpu_debug_read_workspace", "fourmc_gpu_debug_zstd_exec_counts", "fourmc_gpu_debug_lz4_parse", "fourmc_debug_one_block_counters",
-                  "fourmc_gpu_debug_records_scan")
+                  "fourmc_gpu_debug_records_scan", "fourmc_gpu_debug_lines_scan")
 
 # every symbol include/fourmc_gpu.h and include/fourmc.h declare
 _GPU_API = {
@@ -123,6 +127,9 @@ _GPU_API = {
     "fourmc_gpu_image_align_slices": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_image_read_records": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint8, C.c_void_p, C.c_uint64, C.c_void_p,
                                                 C.c_uint64, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_image_read_lines": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                              C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_debug_lines_scan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_debug_records_scan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint8, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_writer_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_image_writer_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),

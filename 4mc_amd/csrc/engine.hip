@@ -1144,6 +1144,18 @@ int records_scan(const void* d, uint64_t len, uint8_t delim, uint64_t* d_cnt, co
     if (d_starts) HIP_TRY(fourmc_launch_records_write(d, len, delim, d_cnt, ntiles, d_st, d_starts, s));
     return FOURMC_OK;
 }
+// The line-end scan over d[0, len): the same passes by the line rule, and the text lengths behind them.
+int lines_scan(const void* d, uint64_t len, uint32_t max_line_len, uint64_t* d_cnt, const fourmc_block* d_desc, uint32_t ndesc,
+               int first_split, uint64_t ds, uint64_t body, uint64_t* d_starts, uint32_t* d_text_len, uint64_t lines_cap,
+               fourmc_records_state* d_st, hipStream_t s)
+{
+    const uint64_t ntiles = fourmc_records_tiles(d, len);
+    if (ntiles > 0x7FFFFFFFull) { snprintf(g_err, sizeof g_err, "image_read_lines: %llu bytes in one split", (unsigned long long)len); return FOURMC_EUNSUP; }
+    HIP_TRY(fourmc_launch_lines_count(d, len, d_cnt, ntiles, s));
+    HIP_TRY(fourmc_launch_lines_finish(d, len, d_cnt, ntiles, d_desc, ndesc, first_split, ds, body, d_starts, lines_cap, d_text_len, d_st, s));
+    if (d_starts) HIP_TRY(fourmc_launch_lines_write(d, len, max_line_len, d_cnt, ntiles, d_st, d_starts, d_text_len, s));
+    return FOURMC_OK;
+}
 // tile counts of any destination of `len` bytes (its address may add one chunk)
 size_t records_cnt_bytes(uint64_t len) { return size_t((len + 16) / FOURMC_RECORDS_TILE + 2) * sizeof(uint64_t); }
 } // namespace
@@ -1225,7 +1237,106 @@ int fourmc_gpu_image_read_records(const void* d_image, uint64_t image_bytes, uin
     return FOURMC_OK;
 }
 
+// image_read_records with the line rule.  Read-backs: as there, and one more when a staged tail block ends with a CR: whether
+// that CR ends the line is the next block's first byte, so that block is staged too.  The block with the CR then lies wholly
+// inside [ds, hi) and is decoded with the body; of the block behind it at most the LF leaves the staging slot.
+int fourmc_gpu_image_read_lines(const void* d_image, uint64_t image_bytes, uint64_t split_start, uint64_t split_end, uint32_t max_line_len,
+                                void* d_dst, uint64_t dst_cap, uint64_t* d_starts, uint32_t* d_text_len, uint64_t lines_cap,
+                                fourmc_image_lines* out, void* stream)
+{
+    if (!out) { snprintf(g_err, sizeof g_err, "image_read_lines: null result"); return FOURMC_EINVAL; }
+    if (!d_image) { snprintf(g_err, sizeof g_err, "image_read_lines: null image"); return FOURMC_EINVAL; }
+    if (!d_dst) { snprintf(g_err, sizeof g_err, "image_read_lines: null destination"); return FOURMC_EINVAL; }
+    if (!d_starts != !d_text_len) { snprintf(g_err, sizeof g_err, "image_read_lines: d_starts and d_text_len go together (both NULL: count only)"); return FOURMC_EINVAL; }
+    if (max_line_len > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "image_read_lines: max_line_len %u above 0x7FFFFFFF", max_line_len); return FOURMC_EINVAL; }
+    if (int r = ensure_device()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    memset(out, 0, sizeof *out);
+    WsLease ws(&g_img_ws);
+    fourmc_image_index_dev idx;
+    if (int r = image_index_count(ws, s, d_image, image_bytes, &idx)) return r;
+    const int64_t code = idx.info.nblocks < 0 ? idx.info.nblocks : idx.info.framing;
+    if (code != 0) { out->result = code; return FOURMC_OK; }
+    const uint32_t n = uint32_t(idx.info.nblocks);
+    const size_t o_plan = kIdxBytes, o_tail = o_plan + 256, o_st = o_tail + 256, o_ent = o_st + 256;
+    const size_t o_desc = o_ent + align256(size_t(n) * sizeof(fourmc_image_entry));
+    const size_t o_cnt = o_desc + align256((size_t(n) + 1) * sizeof(fourmc_block));
+    void* w = nullptr;
+    if (int r = ws.get(s, o_cnt + records_cnt_bytes(std::min(dst_cap, idx.info.total_bytes)), &w)) return r;
+    char* base = static_cast<char*>(w);
+    auto* d_idx = reinterpret_cast<fourmc_image_index_dev*>(base);
+    auto* d_plan = reinterpret_cast<fourmc_records_plan*>(base + o_plan);
+    auto* d_tail = reinterpret_cast<fourmc_records_tail*>(base + o_tail);
+    auto* d_st = reinterpret_cast<fourmc_records_state*>(base + o_st);
+    auto* d_ent = reinterpret_cast<fourmc_image_entry*>(base + o_ent);
+    auto* d_desc = reinterpret_cast<fourmc_block*>(base + o_desc);
+    auto* d_cnt = reinterpret_cast<uint64_t*>(base + o_cnt);
+    HIP_TRY(fourmc_launch_image_index(d_image, image_bytes, d_idx, d_ent, n, s));
+    HIP_TRY(fourmc_launch_records_plan(d_ent, n, d_idx, split_start, split_end, d_plan, s));
+    fourmc_records_plan plan;
+    HIP_TRY(hipMemcpyAsync(&plan, d_plan, sizeof plan, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (plan.code != 0) { out->result = plan.code; return FOURMC_OK; }
+    out->base = plan.ds;
+    // hi: behind the first line end at or after de.  As in image_read_records the blocks from b1 on are staged one at a time; bt
+    // is the first block the body decode leaves out (n: none), and [tail.data_off, hi) comes out of the slot.  `pending`: the
+    // block staged last ended with a CR and is not the last one, hi so far is behind that CR.
+    uint64_t hi = plan.total;
+    uint32_t bt = n;
+    bool pending = false;
+    fourmc_records_tail tail = {};
+    char* d_stage = nullptr;
+    WsLease ws2(&g_img_stage);
+    if (plan.b1 < n) {
+        void* w2 = nullptr;
+        if (int r = ws2.get(s, size_t(FOURMC_BLOCKSIZE) + 64, &w2)) return r;
+        d_stage = static_cast<char*>(w2);
+    }
+    for (uint32_t b = plan.b1; b < n; b++) {
+        HIP_TRY(fourmc_launch_records_desc(d_ent, b, 1, 0, 1, d_desc, s));
+        if (int r = fourmc_gpu_4mc_decode_blocks(d_image, d_stage, d_desc, 1, image_codec(idx), s)) return r;
+        HIP_TRY(fourmc_launch_lines_tail_find(d_stage, d_desc, d_ent, b, b + 1 == n, pending, d_tail, s));
+        HIP_TRY(hipMemcpyAsync(&tail, d_tail, sizeof tail, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (tail.code != 0) { out->result = tail.code; return FOURMC_OK; }
+        if (tail.found == 1) { bt = b; hi = tail.hi; break; }
+        if (tail.found == 2) { pending = true; hi = tail.hi; }
+    }
+    const uint64_t len = hi - plan.ds;
+    if (len > dst_cap) { out->result = -5; out->data_bytes = len; return FOURMC_OK; }
+    const uint32_t count = bt - plan.b0;
+    if (count) {
+        HIP_TRY(fourmc_launch_records_desc(d_ent, plan.b0, count, plan.ds, 0, d_desc, s));
+        if (int r = fourmc_gpu_4mc_decode_blocks(d_image, d_dst, d_desc, count, image_codec(idx), s)) return r;
+    }
+    if (bt < n && hi > tail.data_off)
+        HIP_TRY(hipMemcpyAsync(static_cast<char*>(d_dst) + (tail.data_off - plan.ds), d_stage, hi - tail.data_off, hipMemcpyDeviceToDevice, s));
+    if (int r = lines_scan(d_dst, len, max_line_len, d_cnt, d_desc, count, split_start == 0, plan.ds, plan.de - plan.ds, d_starts, d_text_len, lines_cap, d_st, s)) return r;
+    fourmc_records_state st;
+    HIP_TRY(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    memcpy(out, &st.r, sizeof *out);
+    return FOURMC_OK;
+}
+
 #ifdef FOURMC_RESEARCH
+int fourmc_gpu_debug_lines_scan(const void* d, uint64_t len, uint32_t max_line_len, uint64_t* d_starts, uint32_t* d_text_len,
+                                uint64_t lines_cap, int64_t* lines, void* stream)
+{
+    if (!lines || (len && !d) || !d_starts != !d_text_len || max_line_len > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "debug_lines_scan: bad argument"); return FOURMC_EINVAL; }
+    if (int r = ensure_device()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    WsLease ws(&g_img_ws); void* w = nullptr;
+    if (int r = ws.get(s, 256 + records_cnt_bytes(len), &w)) return r;
+    auto* d_st = static_cast<fourmc_records_state*>(w);
+    if (int r = lines_scan(d, len, max_line_len, reinterpret_cast<uint64_t*>(static_cast<char*>(w) + 256), nullptr, 0, 1, 0, len, d_starts, d_text_len, lines_cap, d_st, s)) return r;
+    fourmc_records_state st;
+    HIP_TRY(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *lines = st.r.result;
+    return FOURMC_OK;
+}
+
 int fourmc_gpu_debug_records_scan(const void* d, uint64_t len, uint8_t delim, uint64_t* d_starts, uint64_t starts_cap,
                                   int64_t* records, void* stream)
 {

@@ -246,6 +246,17 @@ hipError_t fourmc_launch_records_finish(const void* d, uint64_t len, uint8_t del
                                         uint64_t* d_starts, uint64_t starts_cap, fourmc_records_state* d_st, hipStream_t s);
 hipError_t fourmc_launch_records_write(const void* d, uint64_t len, uint8_t delim, const uint64_t* d_cnt, uint64_t ntiles,
                                        const fourmc_records_state* d_st, uint64_t* d_starts, hipStream_t s);
+/* The same by Hadoop's default line rule (LF, lone CR, CR LF; fourmc_gpu_image_read_lines).  tail_find: found = 2 says that the
+ * block ends with a CR whose fate the next block's first byte decides; the block behind it is then asked with `pending`. */
+hipError_t fourmc_launch_lines_tail_find(const void* d_stage, const fourmc_block* d_desc, const fourmc_image_entry* d_ent,
+                                         uint32_t b, int last_block, int pending, fourmc_records_tail* d_tail, hipStream_t s);
+hipError_t fourmc_launch_lines_count(const void* d, uint64_t len, uint64_t* d_cnt, uint64_t ntiles, hipStream_t s);
+hipError_t fourmc_launch_lines_finish(const void* d, uint64_t len, uint64_t* d_cnt, uint64_t ntiles, const fourmc_block* d_desc,
+                                      uint32_t ndesc, int first_split, uint64_t ds, uint64_t body, uint64_t* d_starts,
+                                      uint64_t starts_cap, uint32_t* d_tlen, fourmc_records_state* d_st, hipStream_t s);
+/* the starts and each line's terminator length, then the pass that turns d_tlen into text lengths cut at max_line_len */
+hipError_t fourmc_launch_lines_write(const void* d, uint64_t len, uint32_t max_line_len, const uint64_t* d_cnt, uint64_t ntiles,
+                                     const fourmc_records_state* d_st, uint64_t* d_starts, uint32_t* d_tlen, hipStream_t s);
 #ifdef FOURMC_RESEARCH      /* the research side build exports these two: tools/zstd_timing.py and tools/k7x_prof.py size their read-backs with them */
 #pragma GCC visibility push(default)
 #endif

@@ -11,6 +11,10 @@
 // a split costs far less than its decode did ("Line records").
 // The bytes are addressed in 16-byte chunks from the destination rounded DOWN to 16: aligned loads never leave the pages the
 // destination's own bytes lie in, and the bytes of the first and last chunk that are not the destination's are masked out.
+//
+// fourmc_gpu_image_read_lines cuts the same bytes by Hadoop's default LineReader rule (LF, lone CR, CR LF) with sibling kernels
+// below "the scan, by lines": the same two passes over another mask, a terminator length per line from the write pass, and a
+// third small pass over the table that turns it into the text length.  The one-byte kernels are as they were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fourmc_gpu.h"
@@ -75,6 +79,58 @@ struct Span {
 };
 
 __device__ __forceinline__ uint32_t pattern(uint8_t delim) { return uint32_t(delim) * 0x01010101u; }
+
+// ---- line ends by Hadoop's default rule: LF | (CR & ~(LF one byte further)) ------------------------------------------------
+constexpr uint32_t kLF4 = 0x0a0a0a0au, kCR4 = 0x0d0d0d0du;
+// bit 7 of byte k: byte k of x is zero (match4's test, before its gather)
+__device__ __forceinline__ uint32_t zero_flags(uint32_t x)
+{ return ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u; }
+__device__ __forceinline__ uint32_t gather4(uint32_t z) { return ((z >> 7) * 0x01020408u) >> 24; }
+__device__ __forceinline__ uint32_t gather16(uint32_t z0, uint32_t z1, uint32_t z2, uint32_t z3)
+{ return gather4(z0) | (gather4(z1) << 4) | (gather4(z2) << 8) | (gather4(z3) << 12); }
+// what a chunk shows its neighbours: bit 7 = its byte 0 is LF (the chunk below needs it for a CR in its byte 15) ...
+__device__ __forceinline__ uint32_t lf_first(const uint4& v) { return zero_flags(v.x ^ kLF4) & 0x80u; }
+// ... and bit 7 = its byte 15 is CR (the chunk above needs it for the terminator length of an LF in its byte 0)
+__device__ __forceinline__ uint32_t cr_last(const uint4& v) { return zero_flags(v.w ^ kCR4) >> 24; }
+// The line ends of one chunk, bit k for byte k.  The flags of LF and CR are combined per 32-bit word BEFORE the gather: a CR's
+// flag is cleared by the LF flag one byte up, which for byte 3 of a word is byte 0 of the next word and for byte 15 is `nx`
+// (bit 7: byte 0 of the next chunk is LF).  WITH_T: also `two`, the ends that are the LF of a CR LF (terminator length 2); an LF
+// in byte 0 asks `pv` (bit 7: byte 15 of the chunk before is CR).  Count and write call this one function, so they cannot differ.
+template <bool WITH_T>
+__device__ __forceinline__ uint32_t ends16(const uint4& v, uint32_t nx, uint32_t pv, uint32_t& two)
+{
+    const uint32_t l0 = zero_flags(v.x ^ kLF4), l1 = zero_flags(v.y ^ kLF4), l2 = zero_flags(v.z ^ kLF4), l3 = zero_flags(v.w ^ kLF4);
+    const uint32_t c0 = zero_flags(v.x ^ kCR4), c1 = zero_flags(v.y ^ kCR4), c2 = zero_flags(v.z ^ kCR4), c3 = zero_flags(v.w ^ kCR4);
+    const uint32_t e0 = l0 | (c0 & ~((l0 >> 8) | (l1 << 24))), e1 = l1 | (c1 & ~((l1 >> 8) | (l2 << 24)));
+    const uint32_t e2 = l2 | (c2 & ~((l2 >> 8) | (l3 << 24))), e3 = l3 | (c3 & ~((l3 >> 8) | (nx << 24)));
+    if (WITH_T)
+        two = gather16(l0 & ((c0 << 8) | pv), l1 & ((c1 << 8) | (c0 >> 24)), l2 & ((c2 << 8) | (c1 >> 24)), l3 & ((c3 << 8) | (c2 >> 24)));
+    return gather16(e0, e1, e2, e3);
+}
+// bytes of a word whose bit in the low 4 bits of `m` is clear become 0, which is neither CR nor LF
+__device__ __forceinline__ uint32_t keep4(uint32_t w, uint32_t m) { return w & ((((m & 15u) * 0x00204081u) & 0x01010101u) * 0xffu); }
+// chunk c with the bytes that are not d's zeroed; all zero from nchunks on
+__device__ __forceinline__ uint4 clean_chunk(const Span& sp, uint64_t c)
+{
+    uint4 v = {0, 0, 0, 0};
+    if (c < sp.nchunks) {
+        const uint32_t m = sp.valid(c);
+        v = sp.base[c];
+        v.x = keep4(v.x, m); v.y = keep4(v.y, m >> 4); v.z = keep4(v.z, m >> 8); v.w = keep4(v.w, m >> 12);
+    }
+    return v;
+}
+// One byte of d by its chunk position, 0 outside d.  The byte behind d's last byte is never read: a CR in the last position ends
+// a line, which is what the caller's choice of the span's end (hi, or the content's end) says.
+__device__ __forceinline__ uint32_t span_byte(const Span& sp, uint64_t at)
+{ return at >= sp.head && at < sp.end ? uint32_t(reinterpret_cast<const uint8_t*>(sp.base)[at]) : 0u; }
+// the line ends of chunk c, for one thread by itself (finish, tail find)
+__device__ __forceinline__ uint32_t ends_of(const Span& sp, uint64_t c)
+{
+    if (c >= sp.nchunks) return 0u;
+    uint32_t two;
+    return ends16<false>(clean_chunk(sp, c), span_byte(sp, 16 * (c + 1)) == 10u ? 0x80u : 0u, 0u, two);
+}
 
 // ------------------------------------------------------------------------------------------------------------- index work
 // first block whose header offset is >= pos; n if none (findNextPosition, FourMcBlockIndex.java:87-104)
@@ -207,10 +263,13 @@ void records_count_kernel(const uint8_t* __restrict__ d, uint64_t len, uint32_t 
 // position and the last byte (fourmc_gpu.h).  `body` = de - ds: a split that does not start the file owns something only when
 // its first delimiter lies below it.  The start before the first record of a file and the end behind an unterminated last
 // record have no delimiter in front of them: they are written here.
-__global__ __launch_bounds__(1024)
-void records_finish_kernel(const uint8_t* __restrict__ d, uint64_t len, uint32_t pat, uint64_t* __restrict__ cnt, uint64_t ntiles,
-                           const fourmc_block* __restrict__ desc, uint32_t ndesc, int first_split, uint64_t ds, uint64_t body,
-                           uint64_t* __restrict__ starts, uint64_t starts_cap, fourmc_records_state* __restrict__ st)
+// LINES: the delimiters are the line ends of ends16 (pat unused), and the unterminated last line's terminator length, 0, goes
+// to tlen; the one-byte kernel is the instantiation without, to the instruction what it was before the rule had a sibling.
+template <bool LINES>
+__device__ __forceinline__
+void finish_body(const uint8_t* __restrict__ d, uint64_t len, uint32_t pat, uint64_t* __restrict__ cnt, uint64_t ntiles,
+                 const fourmc_block* __restrict__ desc, uint32_t ndesc, int first_split, uint64_t ds, uint64_t body,
+                 uint64_t* __restrict__ starts, uint64_t starts_cap, uint32_t* __restrict__ tlen, fourmc_records_state* __restrict__ st)
 {
     __shared__ uint64_t wsum[16];
     __shared__ unsigned long long tile0;
@@ -236,7 +295,8 @@ void records_finish_kernel(const uint8_t* __restrict__ d, uint64_t len, uint32_t
     // the first delimiter: in the first tile that counted one
     const Span sp(d, len);
     if (total) {
-        const uint32_t m = sp.mask(uint64_t(tile0) * kTileChunks + t, pat);
+        const uint64_t c = uint64_t(tile0) * kTileChunks + t;
+        const uint32_t m = LINES ? ends_of(sp, c) : sp.mask(c, pat);
         if (m) atomicMin(&in_tile, 16 * t + uint32_t(__builtin_ctz(m)));
     }
     __syncthreads();
@@ -244,7 +304,7 @@ void records_finish_kernel(const uint8_t* __restrict__ d, uint64_t len, uint32_t
     fourmc_records_state s = {};
     s.r.base = ds;
     if (any_bad) { s.r.result = -4; *st = s; return; }
-    const bool open_end = len > 0 && d[len - 1] != uint8_t(pat);         // an unterminated last record
+    const bool open_end = len > 0 && (LINES ? d[len - 1] != 10 && d[len - 1] != 13 : d[len - 1] != uint8_t(pat));   // an unterminated last record
     uint64_t lo = 0, records = 0;
     if (first_split) records = total + (open_end ? 1 : 0);
     else if (total) {
@@ -260,11 +320,17 @@ void records_finish_kernel(const uint8_t* __restrict__ d, uint64_t len, uint32_t
         if (starts) {
             s.write = 1; s.shift = first_split ? 1 : 0;
             if (first_split) starts[0] = 0;
-            if (open_end) starts[records] = len;
+            if (open_end) { starts[records] = len; if (LINES) tlen[records - 1] = 0; }
         }
     }
     *st = s;
 }
+
+__global__ __launch_bounds__(1024)
+void records_finish_kernel(const uint8_t* __restrict__ d, uint64_t len, uint32_t pat, uint64_t* __restrict__ cnt, uint64_t ntiles,
+                           const fourmc_block* __restrict__ desc, uint32_t ndesc, int first_split, uint64_t ds, uint64_t body,
+                           uint64_t* __restrict__ starts, uint64_t starts_cap, fourmc_records_state* __restrict__ st)
+{ finish_body<false>(d, len, pat, cnt, ntiles, desc, ndesc, first_split, ds, body, starts, starts_cap, nullptr, st); }
 
 // the count kernel's walk; the start behind delimiter number r of d goes to starts[shift + r]
 __global__ __launch_bounds__(64 * kWaves)
@@ -297,6 +363,154 @@ void records_write_kernel(const uint8_t* __restrict__ d, uint64_t len, uint32_t 
             for (uint32_t mm = m[j]; mm; mm &= mm - 1) starts[o++] = at + uint32_t(__builtin_ctz(mm));
             run += wave_total(incl);
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------ the scan, by lines
+// One wave step of the walk both passes make: lane l holds chunk c in `v` (the caller loads it as it lies in an inner tile and
+// through clean_chunk in an edge tile; that is all the two differ in) and gets the LF flag of chunk c + 1's byte 0 from lane l + 1's registers.  Lane 63's neighbour is lane 0 of the next step, of the
+// next tile or of another workgroup: it loads that one byte itself, so every seam is the same seam.  WITH_T: the CR flag of
+// chunk c - 1's byte 15 comes up the same way, and lane 0 loads its byte.
+template <bool WITH_T>
+__device__ __forceinline__ uint32_t step_ends(const Span& sp, uint64_t c, const uint4& v, uint32_t lane, uint32_t& two)
+{
+    uint32_t nx = uint32_t(__shfl_down(int(lf_first(v)), 1)), pv = 0;
+    if (lane == 63) nx = span_byte(sp, 16 * (c + 1)) == 10u ? 0x80u : 0u;
+    if (WITH_T) {
+        pv = uint32_t(__shfl_up(int(cr_last(v)), 1));
+        if (lane == 0) pv = c && span_byte(sp, 16 * c - 1) == 13u ? 0x80u : 0u;
+    }
+    return ends16<WITH_T>(v, nx, pv, two);
+}
+
+// one wave per tile: the line ends of its 16 KiB
+__global__ __launch_bounds__(64 * kWaves)
+void lines_count_kernel(const uint8_t* __restrict__ d, uint64_t len, uint64_t* __restrict__ cnt, uint64_t ntiles)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t tile = uint64_t(blockIdx.x) * kWaves + (threadIdx.x >> 6);
+    if (tile >= ntiles) return;
+    const Span sp(d, len);
+    const uint64_t c0 = tile * kTileChunks + lane;
+    uint32_t k = 0, two;
+    if (sp.inner(tile)) {
+        for (uint32_t i = 0; i < kSteps; i += 4) {                 // 4 KiB of the wave in flight
+            const uint4 v0 = sp.base[c0 + 64 * i], v1 = sp.base[c0 + 64 * (i + 1)];
+            const uint4 v2 = sp.base[c0 + 64 * (i + 2)], v3 = sp.base[c0 + 64 * (i + 3)];
+            k += __popc(step_ends<false>(sp, c0 + 64 * i, v0, lane, two)) + __popc(step_ends<false>(sp, c0 + 64 * (i + 1), v1, lane, two))
+               + __popc(step_ends<false>(sp, c0 + 64 * (i + 2), v2, lane, two)) + __popc(step_ends<false>(sp, c0 + 64 * (i + 3), v3, lane, two));
+        }
+    } else {
+        for (uint32_t i = 0; i < kSteps; i++) k += __popc(step_ends<false>(sp, c0 + 64 * i, clean_chunk(sp, c0 + 64 * i), lane, two));
+    }
+    for (int o = 32; o; o >>= 1) k += uint32_t(__shfl_xor(int(k), o));
+    if (lane == 0) cnt[tile] = k;
+}
+
+__global__ __launch_bounds__(1024)
+void lines_finish_kernel(const uint8_t* __restrict__ d, uint64_t len, uint64_t* __restrict__ cnt, uint64_t ntiles,
+                         const fourmc_block* __restrict__ desc, uint32_t ndesc, int first_split, uint64_t ds, uint64_t body,
+                         uint64_t* __restrict__ starts, uint64_t starts_cap, uint32_t* __restrict__ tlen, fourmc_records_state* __restrict__ st)
+{ finish_body<true>(d, len, 0, cnt, ntiles, desc, ndesc, first_split, ds, body, starts, starts_cap, tlen, st); }
+
+// The count kernel's walk.  Line end number r of d closes line shift + r - 1 and opens line shift + r: the start behind it goes
+// to starts[shift + r] and its terminator's length (2 for the LF of a CR LF, else 1) to tlen[shift + r - 1]; the end a split that
+// does not start the file drops (shift 0, r 0) closes a line the split does not own.
+__global__ __launch_bounds__(64 * kWaves)
+void lines_write_kernel(const uint8_t* __restrict__ d, uint64_t len, const uint64_t* __restrict__ base, uint64_t ntiles,
+                        const fourmc_records_state* __restrict__ st, uint64_t* __restrict__ starts, uint32_t* __restrict__ tlen)
+{
+    if (!st->write) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t tile = uint64_t(blockIdx.x) * kWaves + (threadIdx.x >> 6);
+    if (tile >= ntiles) return;
+    const Span sp(d, len);
+    const uint64_t c0 = tile * kTileChunks + lane;
+    uint64_t run = base[tile] + st->shift;
+    const bool inner = sp.inner(tile);
+    for (uint32_t i0 = 0; i0 < kSteps; i0 += 4) {
+        uint32_t m[4], two[4];
+        if (inner) {
+            const uint4 v0 = sp.base[c0 + 64 * i0], v1 = sp.base[c0 + 64 * (i0 + 1)];
+            const uint4 v2 = sp.base[c0 + 64 * (i0 + 2)], v3 = sp.base[c0 + 64 * (i0 + 3)];
+            m[0] = step_ends<true>(sp, c0 + 64 * i0, v0, lane, two[0]); m[1] = step_ends<true>(sp, c0 + 64 * (i0 + 1), v1, lane, two[1]);
+            m[2] = step_ends<true>(sp, c0 + 64 * (i0 + 2), v2, lane, two[2]); m[3] = step_ends<true>(sp, c0 + 64 * (i0 + 3), v3, lane, two[3]);
+        } else {
+            for (uint32_t j = 0; j < 4; j++) m[j] = step_ends<true>(sp, c0 + 64 * (i0 + j), clean_chunk(sp, c0 + 64 * (i0 + j)), lane, two[j]);
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            const uint32_t k = __popc(m[j]);
+            const uint32_t incl = scan_add(k);
+            uint64_t o = run + (incl - k);
+            const uint64_t at = 16 * (c0 + 64 * (i0 + j)) + 1 - sp.head;      // the start behind byte 0 of the chunk
+            for (uint32_t mm = m[j]; mm; mm &= mm - 1) {
+                const uint32_t bit = uint32_t(__builtin_ctz(mm));
+                starts[o] = at + bit;
+                if (o) tlen[o - 1] = 1 + ((two[j] >> bit) & 1u);
+                o++;
+            }
+            run += wave_total(incl);
+        }
+    }
+}
+
+// tlen[i], the terminator's length of line i, into the length of its text, cut at max_len.  The line count is on the device
+// only, so a fixed grid strides over it.
+__global__ __launch_bounds__(256)
+void lines_len_kernel(const fourmc_records_state* __restrict__ st, const uint64_t* __restrict__ starts, uint32_t* __restrict__ tlen,
+                      uint32_t max_len)
+{
+    if (!st->write) return;
+    const uint64_t n = uint64_t(st->r.result), step = uint64_t(gridDim.x) * 256;
+    for (uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += step) {
+        const uint64_t text = starts[i + 1] - starts[i] - tlen[i];
+        tlen[i] = uint32_t(text < max_len ? text : max_len);
+    }
+}
+
+// records_tail_find_kernel by lines: the first line end of a staged block.  A CR in the block's last byte ends a line only if
+// the next block does not open with LF, which this block cannot say unless it is the last (found = 2, hi behind the block).
+// `pending`: the block BEHIND such a CR; its first byte decides (hi behind the LF, or still behind the CR), an empty block
+// leaves the question open.
+__global__ __launch_bounds__(1024)
+void lines_tail_find_kernel(const uint8_t* __restrict__ stage, const fourmc_block* __restrict__ desc,
+                            const fourmc_image_entry* __restrict__ ent, uint32_t b, int last_block, int pending,
+                            fourmc_records_tail* __restrict__ out)
+{
+    __shared__ uint32_t first;
+    const fourmc_block d = *desc;
+    const fourmc_image_entry e = ent[b];
+    fourmc_records_tail r = {};
+    r.data_off = e.data_off;
+    if (block_bad(d)) {
+        r.code = -4;
+        if (threadIdx.x == 0) *out = r;
+        return;
+    }
+    if (pending) {
+        if (threadIdx.x == 0) {
+            if (e.usize == 0) { r.found = 2; r.hi = e.data_off; }
+            else { r.found = 1; r.hi = e.data_off + (stage[0] == 10 ? 1 : 0); }
+            *out = r;
+        }
+        return;
+    }
+    const Span sp(stage, e.usize);
+    if (threadIdx.x == 0) first = ~0u;
+    __syncthreads();
+    for (uint64_t c0 = 0; c0 < sp.nchunks; c0 += 1024) {
+        const uint64_t c = c0 + threadIdx.x;
+        const uint32_t m = ends_of(sp, c);
+        if (m) atomicMin(&first, uint32_t(16 * c) + uint32_t(__builtin_ctz(m)));
+        if (__syncthreads_or(m != 0)) break;
+    }
+    if (threadIdx.x == 0) {
+        if (first != ~0u) {
+            const bool open = !last_block && first == e.usize - 1 && stage[first] == 13;
+            r.found = open ? 2 : 1; r.hi = e.data_off + first + 1;
+        }
+        *out = r;
     }
 }
 
@@ -365,6 +579,45 @@ hipError_t fourmc_launch_records_write(const void* d, uint64_t len, uint8_t deli
     if (!ntiles) return hipSuccess;
     hipLaunchKernelGGL(records_write_kernel, dim3(uint32_t((ntiles + kWaves - 1) / kWaves)), dim3(64 * kWaves), 0, s,
                        static_cast<const uint8_t*>(d), len, uint32_t(delim) * 0x01010101u, d_cnt, ntiles, d_st, d_starts);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_lines_tail_find(const void* d_stage, const fourmc_block* d_desc, const fourmc_image_entry* d_ent,
+                                         uint32_t b, int last_block, int pending, fourmc_records_tail* d_tail, hipStream_t s)
+{
+    hipLaunchKernelGGL(lines_tail_find_kernel, dim3(1), dim3(1024), 0, s, static_cast<const uint8_t*>(d_stage), d_desc, d_ent, b,
+                       last_block, pending, d_tail);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_lines_count(const void* d, uint64_t len, uint64_t* d_cnt, uint64_t ntiles, hipStream_t s)
+{
+    if (!ntiles) return hipSuccess;
+    hipLaunchKernelGGL(lines_count_kernel, dim3(uint32_t((ntiles + kWaves - 1) / kWaves)), dim3(64 * kWaves), 0, s,
+                       static_cast<const uint8_t*>(d), len, d_cnt, ntiles);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_lines_finish(const void* d, uint64_t len, uint64_t* d_cnt, uint64_t ntiles, const fourmc_block* d_desc,
+                                      uint32_t ndesc, int first_split, uint64_t ds, uint64_t body, uint64_t* d_starts,
+                                      uint64_t starts_cap, uint32_t* d_tlen, fourmc_records_state* d_st, hipStream_t s)
+{
+    hipLaunchKernelGGL(lines_finish_kernel, dim3(1), dim3(1024), 0, s, static_cast<const uint8_t*>(d), len, d_cnt, ntiles, d_desc,
+                       ndesc, first_split, ds, body, d_starts, starts_cap, d_tlen, d_st);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_lines_write(const void* d, uint64_t len, uint32_t max_line_len, const uint64_t* d_cnt, uint64_t ntiles,
+                                     const fourmc_records_state* d_st, uint64_t* d_starts, uint32_t* d_tlen, hipStream_t s)
+{
+    if (ntiles) {
+        hipLaunchKernelGGL(lines_write_kernel, dim3(uint32_t((ntiles + kWaves - 1) / kWaves)), dim3(64 * kWaves), 0, s,
+                           static_cast<const uint8_t*>(d), len, d_cnt, ntiles, d_st, d_starts, d_tlen);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    // one thread per line up to 2048 workgroups (a line of text per ~100 bytes: the grid is full from ~50 MB on), strides above
+    const uint64_t most = len / 256 + 1;
+    hipLaunchKernelGGL(lines_len_kernel, dim3(uint32_t(most < 2048 ? most : 2048)), dim3(256), 0, s, d_st, d_starts, d_tlen, max_line_len);
     return hipGetLastError();
 }
 

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .binding import (BLOCK_DTYPE, CODEC_LZ4_FAST, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageIndexInfo, ImageRange,
+from .binding import (BLOCK_DTYPE, CODEC_LZ4_FAST, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageIndexInfo, ImageLines, ImageRange,
                       ImageRecords, ImageSlice, ImageStatus, check, lib)
 
 
@@ -228,6 +228,36 @@ def image_read_records(d_image, split_start, split_end, d_dst, starts=None, deli
     out = ImageRecords()
     check(lib().fourmc_gpu_image_read_records(ptr, n, int(split_start), int(split_end), int(delim) & 0xFF, dst, d_dst.numel(), sp, cap,
                                               C.byref(out), _stream_ptr(stream)), "fourmc_gpu_image_read_records")
+    return out
+
+
+def image_read_lines(d_image, split_start, split_end, d_dst, starts=None, text_len=None, max_line_len=0x7FFFFFFF, image_bytes=None,
+                     stream=None):
+    """The lines that the split [split_start, split_end) of the image owns, cut as Hadoop's default LineReader cuts them: LF, a
+    lone CR and CR LF end a line.  d_dst[:data_bytes] receives the decoded content from the split's first block on, `starts` (an
+    int64 CUDA tensor) the offset in d_dst of each line and, behind the last, data_bytes, `text_len` (an int32 or uint32 CUDA
+    tensor) each line's length without its terminator, cut at max_line_len.  Both tables or neither (count only); `starts` needs
+    one entry more than there are lines, `text_len` one per line.  Returns the ImageLines struct (result: the lines owned, or a
+    negative code; include/fourmc_gpu.h)."""
+    ptr = _dev_ptr(d_image, "image_read_lines d_image")
+    dst = _dev_ptr(d_dst, "image_read_lines d_dst")
+    n = _image_len(d_image, image_bytes, "image_read_lines")
+    if (starts is None) != (text_len is None):
+        raise EngineError("image_read_lines: starts and text_len go together (both None: count only)")
+    if not 0 <= int(max_line_len) <= 0x7FFFFFFF:
+        raise EngineError("image_read_lines max_line_len: 0 .. 0x7FFFFFFF")
+    sp, tp, cap = 0, 0, 0
+    if starts is not None:
+        if not (isinstance(starts, torch.Tensor) and starts.is_cuda and starts.is_contiguous() and starts.dtype == torch.int64):
+            raise EngineError("image_read_lines starts: a contiguous int64 CUDA tensor is required")
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if not (isinstance(text_len, torch.Tensor) and text_len.is_cuda and text_len.is_contiguous() and text_len.dtype in words):
+            raise EngineError("image_read_lines text_len: a contiguous int32 or uint32 CUDA tensor is required")
+        # the call writes text_len[0, lines) only, so a table of one entry per line serves lines_cap = its size + 1
+        sp, tp, cap = int(starts.data_ptr()), int(text_len.data_ptr()), min(starts.numel(), text_len.numel() + 1)
+    out = ImageLines()
+    check(lib().fourmc_gpu_image_read_lines(ptr, n, int(split_start), int(split_end), int(max_line_len), dst, d_dst.numel(), sp, tp, cap,
+                                            C.byref(out), _stream_ptr(stream)), "fourmc_gpu_image_read_lines")
     return out
 
 

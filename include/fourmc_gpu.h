@@ -333,10 +333,11 @@ int fourmc_gpu_image_read(const void* d_image, uint64_t image_bytes, fourmc_imag
  * every line has exactly one owner.  Both calls obey the settings image_read obeys (FOURMC_DECODE, FOURMC_ZDECODE); no per-block
  * data crosses to the host.  Synchronizations of `stream`: image_align_slices 2 (1 for an image without blocks); image_read_records
  * 3 + one per staged tail block (usually 1; 0 when split_end is at or past the end mark; more only while a line longer than a
- * block has shown no delimiter), less when a check ends the call early.
- * Not reproduced: Hadoop's default LineReader also ends a line at a lone CR and strips CR LF; here the delimiter is ONE byte, a
- * record includes it, and CR handling is the caller's.  There is no max.line.length truncation, and multi-stream images are refused
- * as in the random-access group (the index code). */
+ * block has shown no delimiter), less when a check ends the call early; image_read_lines the same, plus one when a staged tail
+ * block ends with a CR and is not the last block (the next block's first byte says whether that CR ends the line).
+ * image_read_records cuts at ONE caller-chosen byte and a record includes it; the lines Hadoop's default LineReader hands to a
+ * mapper (LF, lone CR and CR LF end a line, the terminator stripped, the text cut at max.line.length) are image_read_lines'.
+ * Not reproduced by either: multi-stream images are refused as in the random-access group (the index code). */
 typedef struct fourmc_image_slice {       /* 48 bytes */
     uint64_t start, end;                  /* in : raw byte slice [start, end) of the image, as FileInputFormat cuts it */
     uint64_t split_start, split_end;      /* out: aligned as FourMcBlockIndex.java:142-173 with fileSize = image_bytes: what
@@ -381,6 +382,34 @@ typedef struct fourmc_image_records {     /* 40 bytes */
 int fourmc_gpu_image_read_records(const void* d_image, uint64_t image_bytes, uint64_t split_start, uint64_t split_end, uint8_t delim,
                                   void* d_dst, uint64_t dst_cap, uint64_t* d_starts, uint64_t starts_cap,
                                   fourmc_image_records* out /*host*/, void* stream);
+
+/* The lines of the split by Hadoop's default rule, which is the reference reader's: it is built as new LineReader(stream, job)
+ * and calls readLine(value, maxLineLen) (FourMcLineRecordReader.java:122,135,154), so no custom delimiter is ever read.  With D[0, T)
+ * the decoded content, position p ENDS A LINE when D[p] == LF, or D[p] == CR and (p + 1 == T or D[p+1] != LF); a CR followed by LF
+ * ends nothing by itself.  Lines start at 0 and behind every end; a final unterminated run is a line if not empty.  Line [s, s')
+ * has a terminator of t = 2 (CR LF), 1 (LF, lone CR) or 0 bytes, and its TEXT is D[s, s + min(s' - s - t, max_line_len)): the whole
+ * line is consumed however long it is, as readLine with maxBytesToConsume = Integer.MAX_VALUE does.
+ * Ownership, split offsets, ds / de / lo / hi, d_dst[0, hi - ds), base, data_off, data_bytes, d_starts[0 .. lines] with
+ * d_starts[lines] = data_bytes, and the result codes with their precedence are image_read_records' word for word, with "line end"
+ * for "delimiter".  New: d_text_len[i] = the length of line i's text, so line i's text is d_dst[d_starts[i], d_starts[i] +
+ * d_text_len[i]).  The call needs lines + 1 <= lines_cap (else the -5 with reserved = lines, and neither table is written);
+ * d_starts[0 .. lines] and d_text_len[0, lines) are written, so d_text_len may hold one entry less than d_starts.  Both tables
+ * NULL: count only; one without the other: FOURMC_EINVAL.  max_line_len: Hadoop's default is 0x7FFFFFFF; larger: FOURMC_EINVAL;
+ * 0: every text is empty.  Nothing is written outside [d_dst, d_dst + dst_cap), d_starts[0, lines_cap) or d_text_len[0, lines_cap).
+ * One deviation from the reference, by reading it (no JVM ran it): when the last decoded byte before split_end is a CR and the byte
+ * behind it is not LF, the reference's LineReader must fill its buffer to look behind the CR, which pulls the whole next block
+ * through FourMcInputStream and moves the file position past the split's end; its reader stops, the next split's reader skips its
+ * first line as always, and the line that starts at de is read by nobody.  Here that line belongs to the earlier split: the rule
+ * above is the contract, and every line has exactly one owner.
+ * Not reproduced: the reference's IOException("Too many bytes before newline") for a line of 2 GiB or more; the key (the raw file
+ * position after the last block read); multi-byte delimiters (textinputformat.record.delimiter, which the reference never reads);
+ * batching of splits; multi-stream images (the index code). */
+typedef struct fourmc_image_lines { int64_t result; uint64_t base, data_off, data_bytes, reserved; } fourmc_image_lines; /* as fourmc_image_records */
+int fourmc_gpu_image_read_lines(const void* d_image, uint64_t image_bytes, uint64_t split_start, uint64_t split_end,
+                                uint32_t max_line_len,               /* Hadoop's default: 0x7FFFFFFF; larger: FOURMC_EINVAL; 0: every text empty */
+                                void* d_dst, uint64_t dst_cap,
+                                uint64_t* d_starts, uint32_t* d_text_len, uint64_t lines_cap,
+                                fourmc_image_lines* out /*host*/, void* stream);
 
 /* ---- host-buffer conveniences with the reference's per-block signatures ------------------- */
 /* These stage one block through HBM (H2D, one launch, D2H).  They exist so the JNI entry points
@@ -429,6 +458,9 @@ int fourmc_gpu_debug_lz4_parse(const void* d_src, const void* d_dst, fourmc_bloc
  * only; -5 in *records when starts_cap is too small).  Synchronizes once. */
 int fourmc_gpu_debug_records_scan(const void* d, uint64_t len, uint8_t delim, uint64_t* d_starts, uint64_t starts_cap,
                                   int64_t* records, void* stream);
+/* The same for fourmc_gpu_image_read_lines: count, finish, write and the length pass; *lines (host) = the lines. */
+int fourmc_gpu_debug_lines_scan(const void* d, uint64_t len, uint32_t max_line_len, uint64_t* d_starts, uint32_t* d_text_len,
+                                uint64_t lines_cap, int64_t* lines, void* stream);
 /* one-block host calls (LZ4_* / ZSTD_* twins, JNI) made so far, and the launches that served them (concurrent calls share one) */
 void fourmc_debug_one_block_counters(unsigned long long* calls, unsigned long long* launches);
 
