@@ -92,6 +92,7 @@ public:
     explicit WsLease(std::map<hipStream_t, StreamWs*>* reg) : reg_(reg) {}
     WsLease(const WsLease&) = delete;
     ~WsLease() { if (w_) w_->mu.unlock(); }
+    size_t cap() const { return w_ ? w_->cap : 0; }          // changes exactly when get() had to grow the buffer
     int get(hipStream_t s, size_t need, void** out)
     {
         if (!w_) {
@@ -937,6 +938,90 @@ int fourmc_gpu_image_decompress(const void* d_image, uint64_t image_bytes, void*
     HIP_TRY(fourmc_launch_image_reduce(d_blk, n, d_ps, d_st, s));
     HIP_TRY(hipMemcpyAsync(status, d_st, sizeof *status, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return FOURMC_OK;
+}
+
+// Many images with one call.  Workspace (g_img_ws): the summary, the items, one parse and one first-descriptor number per image,
+// the statuses, then - sized after the first read-back - the descriptors of every image.  When that grows the buffer its contents
+// are gone: the items go up again and the count parse and the plan run again before the fill.
+int fourmc_gpu_images_decompress(const void* d_images, uint64_t images_bytes, void* d_dst, uint64_t dst_bytes,
+                                 uint32_t magic, fourmc_image_item* items, uint32_t n, void* stream)
+{
+    if (magic != FOURMC_MAGIC_4MC && magic != FOURMC_MAGIC_4MZ) { snprintf(g_err, sizeof g_err, "magic 0x%08x is neither 4mc nor 4mz", magic); return FOURMC_EINVAL; }
+    if (n == 0) return FOURMC_OK;
+    if (!items) { snprintf(g_err, sizeof g_err, "images_decompress: null items"); return FOURMC_EINVAL; }
+    {
+        std::vector<std::pair<uint64_t, uint64_t>> d;
+        if (d_dst) d.reserve(n);
+        for (uint32_t i = 0; i < n; i++) {
+            const fourmc_image_item& it = items[i];
+            if (it.image_bytes && !d_images) { snprintf(g_err, sizeof g_err, "images_decompress: null images"); return FOURMC_EINVAL; }
+            if (it.image_off > images_bytes || it.image_bytes > images_bytes - it.image_off) {
+                snprintf(g_err, sizeof g_err, "images_decompress: image %u lies beyond the %llu bytes of images", i, (unsigned long long)images_bytes);
+                return FOURMC_EINVAL;
+            }
+            if (!d_dst) continue;                             // the size query looks at no destination
+            if (it.dst_off > dst_bytes || it.dst_cap > dst_bytes - it.dst_off) {
+                snprintf(g_err, sizeof g_err, "images_decompress: the output region of image %u lies beyond the %llu bytes of the destination", i,
+                         (unsigned long long)dst_bytes);
+                return FOURMC_EINVAL;
+            }
+            if (it.dst_cap) d.emplace_back(it.dst_off, it.dst_off + it.dst_cap);
+        }
+        std::sort(d.begin(), d.end());
+        for (size_t i = 1; i < d.size(); i++)
+            if (d[i].first < d[i - 1].second) {
+                snprintf(g_err, sizeof g_err, "images_decompress: output regions overlap at %llu", (unsigned long long)d[i].first);
+                return FOURMC_EINVAL;
+            }
+    }
+    if (int r = ensure_device()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool query = !d_dst;
+    const size_t o_items = align256(sizeof(fourmc_images_summary)), o_ps = o_items + align256(size_t(n) * sizeof(fourmc_image_item));
+    const size_t o_first = o_ps + align256(size_t(n) * sizeof(fourmc_image_parse)), o_st = o_first + align256(size_t(n) * 8);
+    const size_t o_blk = o_st + align256(size_t(n) * sizeof(fourmc_image_status));
+    WsLease ws(&g_img_ws); void* w = nullptr;
+    if (int r = ws.get(s, o_blk, &w)) return r;
+    char* base = static_cast<char*>(w);
+    const bool try_fast = !image_walk_forced();
+    // the items, the count parse and the plan; again after the buffer has grown
+    auto count_and_plan = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(base + o_items, items, size_t(n) * sizeof(fourmc_image_item), hipMemcpyHostToDevice, s));
+        HIP_TRY(fourmc_launch_images_parse(d_images, reinterpret_cast<fourmc_image_item*>(base + o_items), n, magic, try_fast,
+                                           reinterpret_cast<fourmc_image_parse*>(base + o_ps), nullptr, nullptr, s));
+        HIP_TRY(fourmc_launch_images_plan(reinterpret_cast<fourmc_image_item*>(base + o_items), n, reinterpret_cast<fourmc_image_parse*>(base + o_ps),
+                                          query, reinterpret_cast<uint64_t*>(base + o_first), reinterpret_cast<fourmc_images_summary*>(base),
+                                          reinterpret_cast<fourmc_image_status*>(base + o_st), s));
+        return FOURMC_OK;
+    };
+    if (int r = count_and_plan()) return r;
+    fourmc_images_summary sum;
+    std::vector<fourmc_image_status> back(n);
+    HIP_TRY(hipMemcpyAsync(&sum, base, sizeof sum, hipMemcpyDeviceToHost, s));
+    if (query) HIP_TRY(hipMemcpyAsync(back.data(), base + o_st, size_t(n) * sizeof(fourmc_image_status), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    g_img_fast += sum.fast; g_img_walk += sum.walk;
+    if (sum.nblocks > 0x7FFFFFFFull) { snprintf(g_err, sizeof g_err, "images_decompress: %llu blocks", (unsigned long long)sum.nblocks); return FOURMC_EUNSUP; }
+    if (!query) {
+        const uint32_t nb = uint32_t(sum.nblocks);
+        const size_t had = ws.cap();
+        if (int r = ws.get(s, o_blk + size_t(nb) * sizeof(fourmc_block), &w)) return r;
+        base = static_cast<char*>(w);
+        if (ws.cap() != had) if (int r = count_and_plan()) return r;
+        auto* d_items = reinterpret_cast<fourmc_image_item*>(base + o_items);
+        auto* d_ps = reinterpret_cast<fourmc_image_parse*>(base + o_ps);
+        auto* d_first = reinterpret_cast<uint64_t*>(base + o_first);
+        auto* d_blk = reinterpret_cast<fourmc_block*>(base + o_blk);
+        if (nb) {
+            HIP_TRY(fourmc_launch_images_parse(d_images, d_items, n, magic, try_fast, d_ps, d_first, d_blk, s));
+            if (int r = fourmc_gpu_4mc_decode_blocks(d_images, d_dst, d_blk, nb, magic == FOURMC_MAGIC_4MZ ? FOURMC_CODEC_ZSTD : FOURMC_CODEC_LZ4_FAST, s)) return r;
+        }
+        HIP_TRY(fourmc_launch_images_reduce(d_items, n, d_ps, d_first, d_blk, reinterpret_cast<fourmc_image_status*>(base + o_st), s));
+        HIP_TRY(hipMemcpyAsync(back.data(), base + o_st, size_t(n) * sizeof(fourmc_image_status), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    for (uint32_t i = 0; i < n; i++) items[i].status = back[i];
     return FOURMC_OK;
 }
 

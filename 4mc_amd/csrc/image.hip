@@ -13,6 +13,8 @@
 // count it read back, the same descriptors.  Header fields are big-endian u32 at any byte offset.
 // Streaming writes reuse the encode half: a batch's descriptors may start inside a chunk or in the writer's carry slot, and its scan
 // runs on from the offset the previous batch left in the writer's device index.
+// Many images (fourmc_gpu_images_decompress): the same parsers and reduction, one wave per image of one buffer, and a plan that
+// gives every image its slice of one descriptor table.
 // Random access (second half): the footer index of a single stream, block-range decodes and byte-range reads, each with the
 // verdict fourmc_file_decode_blocks (fourmc_file.c) reaches on the same bytes as a file.
 // Streaming reads (last part): the walk restated to stop at the end of each appended chunk and resume at the next, the gather of
@@ -155,9 +157,10 @@ void image_enc_tail_kernel(uint8_t* __restrict__ image, const uint64_t* __restri
 
 // ------------------------------------------------------------------------------------------------------------- decode
 // The fast path, one wave.  `blocks` NULL: check only (summary); else write the descriptors of the image it accepted.
-__global__ __launch_bounds__(64)
-void image_parse_fast_kernel(const uint8_t* __restrict__ img, uint64_t N, uint32_t magic, fourmc_image_parse* ps,
-                             fourmc_block* __restrict__ blocks)
+// The three bases place one image among many (images_parse_kernel): the image starts at src_base of the buffer the block decode
+// reads from, its output at dst_base of the buffer it writes to, its descriptors at blocks + desc_base.  A single image has zeros.
+__device__ __forceinline__ void parse_fast(const uint8_t* __restrict__ img, uint64_t N, uint32_t magic, fourmc_image_parse* ps,
+                                           fourmc_block* __restrict__ blocks, uint64_t src_base, uint64_t dst_base, uint64_t desc_base)
 {
     const int lane = threadIdx.x;
     // the footer at the end: [size][version 1][k deltas][size][magic][xxh32]
@@ -199,9 +202,9 @@ void image_parse_fast_kernel(const uint8_t* __restrict__ img, uint64_t N, uint32
         const uint32_t uincl = scan_add(have ? usize : 0u);
         if (ok && blocks && have) {
             fourmc_block d;
-            d.src_off = at + 12; d.dst_off = ucarry + (uincl - usize);
+            d.src_off = src_base + at + 12; d.dst_off = dst_base + ucarry + (uincl - usize);
             d.src_len = csize; d.dst_cap = usize; d.result = 0; d.xxh32 = sum;
-            blocks[i] = d;
+            blocks[desc_base + i] = d;
         }
         carry += dtot; ucarry += wave_total(uincl);
     }
@@ -212,6 +215,10 @@ void image_parse_fast_kernel(const uint8_t* __restrict__ img, uint64_t N, uint32
         ps->fast = 1;
     }
 }
+__global__ __launch_bounds__(64)
+void image_parse_fast_kernel(const uint8_t* __restrict__ img, uint64_t N, uint32_t magic, fourmc_image_parse* ps,
+                             fourmc_block* __restrict__ blocks)
+{ parse_fast(img, N, magic, ps, blocks, 0, 0, 0); }
 
 // decode_stream's per-field checks (fourmc_file.c:473-592), shared by the whole-image walk and the streaming reader's walk.  Each
 // one is decided once the bytes it reads are there; the checks of "unreadable" kinds (N - p < k) are the callers'.
@@ -239,10 +246,9 @@ __device__ __forceinline__ int32_t footer_verdict(uint32_t computed, uint32_t st
 // The walk: decode_stream (fourmc_file.c:473-592) and decompress_file's loop over concatenated streams on one lane, the checks in
 // their order.  That loop (`do got = decode_stream(..); while (got)`, fourmc_file.c:606-609, native/4mc.c:908-912) ends after a
 // stream that decoded 0 bytes, whatever follows it: the walk ends cleanly after a stream whose blocks add up to 0 usize.  count mode (blocks NULL): nothing to do when the fast path has accepted the image; else the summary.  fill mode:
-// the same walk, writing the descriptors of the blocks it counted.
-__global__ __launch_bounds__(64)
-void image_parse_walk_kernel(const uint8_t* __restrict__ img, uint64_t N, uint32_t magic, fourmc_image_parse* ps,
-                             fourmc_block* __restrict__ blocks)
+// the same walk, writing the descriptors of the blocks it counted.  The bases: as parse_fast's.
+__device__ __forceinline__ void parse_walk(const uint8_t* __restrict__ img, uint64_t N, uint32_t magic, fourmc_image_parse* ps,
+                                           fourmc_block* __restrict__ blocks, uint64_t src_base, uint64_t dst_base, uint64_t desc_base)
 {
     if (threadIdx.x != 0) return;
     if (!blocks && ps->fast) return;
@@ -270,8 +276,8 @@ void image_parse_walk_kernel(const uint8_t* __restrict__ img, uint64_t N, uint32
             if (usize_beyond(usize, csize)) { reason = usize_verdict(xxh32_lane(img + p, csize, 0), sum); break; }
             if (blocks) {
                 fourmc_block d;
-                d.src_off = p; d.dst_off = total; d.src_len = csize; d.dst_cap = usize; d.result = 0; d.xxh32 = sum;
-                blocks[nb] = d;
+                d.src_off = src_base + p; d.dst_off = dst_base + total; d.src_len = csize; d.dst_cap = usize; d.result = 0; d.xxh32 = sum;
+                blocks[desc_base + nb] = d;
             }
             nb++; total += usize; p += csize;
         }
@@ -289,6 +295,10 @@ void image_parse_walk_kernel(const uint8_t* __restrict__ img, uint64_t N, uint32
         ps->fail_offset = reason == FOURMC_IMG_OK ? N : at;
     }
 }
+__global__ __launch_bounds__(64)
+void image_parse_walk_kernel(const uint8_t* __restrict__ img, uint64_t N, uint32_t magic, fourmc_image_parse* ps,
+                             fourmc_block* __restrict__ blocks)
+{ parse_walk(img, N, magic, ps, blocks, 0, 0, 0); }
 
 // image_reduce's scan, one wave: the index of the first block whose result is negative (n if none) and *done, the sum of the
 // positive results before it
@@ -319,8 +329,9 @@ __device__ __forceinline__ int32_t block_reason(int32_t result)
 
 // The verdict: the first block that failed its checksum or its decode ends decoding there (file order puts it before any
 // framing error, which the parsers only ever report behind the last block they counted); otherwise the parser's verdict.
-__global__ __launch_bounds__(64)
-void image_reduce_kernel(const fourmc_block* __restrict__ blocks, uint32_t n, const fourmc_image_parse* ps, fourmc_image_status* st)
+// `blocks` is the image's own slice of the descriptors; src_base: where the image starts in the buffer their src_off count from.
+__device__ __forceinline__ void reduce_verdict(const fourmc_block* __restrict__ blocks, uint32_t n, const fourmc_image_parse* ps,
+                                               fourmc_image_status* st, uint64_t src_base)
 {
     uint64_t done = 0;
     const uint32_t first = first_failing(blocks, n, &done);
@@ -332,12 +343,107 @@ void image_reduce_kernel(const fourmc_block* __restrict__ blocks, uint32_t n, co
     if (first < n) {
         st->reason = block_reason(blocks[first].result);
         st->exit_code = 4;
-        st->fail_offset = blocks[first].src_off - 12;
+        st->fail_offset = blocks[first].src_off - 12 - src_base;
     } else {
         st->reason = ps->reason;
         st->exit_code = fourmc_image_exit_code(ps->reason);
         st->fail_offset = ps->fail_offset;
     }
+}
+__global__ __launch_bounds__(64)
+void image_reduce_kernel(const fourmc_block* __restrict__ blocks, uint32_t n, const fourmc_image_parse* ps, fourmc_image_status* st)
+{ reduce_verdict(blocks, n, ps, st, 0); }
+
+// ------------------------------------------------------------------------------------------------------------- many images
+// fourmc_gpu_images_decompress: the three steps above for n images of one buffer at once, so that ONE descriptor table with offsets
+// relative to two base pointers describes every block of every image and one container decode serves them all.
+// Parse, one wave per image.  Count mode (desc NULL): the fast path, then - in the same launch - the walk when it did not accept
+// the image; ps[i] is the image's summary.  Fill mode: the parser that accepted the image writes its descriptors at
+// desc + first[i]; an image that ends FOURMC_IMG_DST_SMALL has none (what fourmc_gpu_image_decompress' host code decides).
+__device__ __forceinline__ bool dst_small(const fourmc_image_parse& s, const fourmc_image_item& it) { return s.total > it.dst_cap; }
+
+__global__ __launch_bounds__(64)
+void images_parse_kernel(const uint8_t* __restrict__ images, const fourmc_image_item* __restrict__ items, uint32_t magic, int fast,
+                         fourmc_image_parse* ps, const uint64_t* __restrict__ first, fourmc_block* __restrict__ desc)
+{
+    const uint32_t i = blockIdx.x;
+    const fourmc_image_item it = items[i];
+    const uint8_t* img = images + it.image_off;
+    if (!desc) {
+        if (threadIdx.x == 0) ps[i] = fourmc_image_parse{};
+        if (fast) parse_fast(img, it.image_bytes, magic, ps + i, nullptr, 0, 0, 0);
+        parse_walk(img, it.image_bytes, magic, ps + i, nullptr, 0, 0, 0);    // lane 0 reads what lane 0 wrote: ps[i].fast
+        return;
+    }
+    const fourmc_image_parse s = ps[i];
+    if (dst_small(s, it) || s.nblocks == 0) return;
+    if (s.fast) parse_fast(img, it.image_bytes, magic, ps + i, desc, it.image_off, it.dst_off, first[i]);
+    else parse_walk(img, it.image_bytes, magic, ps + i, desc, it.image_off, it.dst_off, first[i]);
+}
+
+// Plan, one workgroup: first[i] = the exclusive prefix of the images' descriptor counts (none for FOURMC_IMG_DST_SMALL), the total
+// and the parsers' counts for the engine's first read-back; for the size query (every well-formed block counts, no destination is
+// looked at) the final statuses too.  A plain pass in chunks of kPlanThreads images with a carry, not decoupled look-back: its
+// workgroups would spin on their predecessors' flags (records.hip), and n images are a few KiB of counts.
+constexpr uint32_t kPlanThreads = 256;
+__global__ __launch_bounds__(kPlanThreads)
+void images_plan_kernel(const fourmc_image_item* __restrict__ items, uint32_t n, const fourmc_image_parse* __restrict__ ps, int query,
+                        uint64_t* __restrict__ first, fourmc_images_summary* __restrict__ sum, fourmc_image_status* __restrict__ status)
+{
+    __shared__ uint64_t wsum[kPlanThreads / 64];
+    __shared__ uint32_t taken[2];
+    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+    if (t < 2) taken[t] = 0;
+    uint64_t carry = 0;
+    uint32_t nfast = 0, nwalk = 0;
+    for (uint64_t i0 = 0; i0 < n; i0 += kPlanThreads) {
+        const uint64_t i = i0 + t;
+        uint64_t c = 0;
+        if (i < n) {
+            const fourmc_image_parse s = ps[i];
+            if (s.fast) nfast++; else nwalk++;
+            if (query) {
+                c = s.nblocks;
+                fourmc_image_status r = {};
+                r.total_bytes = s.total; r.streams = s.streams; r.blocks = uint32_t(s.nblocks);
+                r.reason = s.reason; r.exit_code = fourmc_image_exit_code(s.reason); r.fail_offset = s.fail_offset;
+                status[i] = r;
+            } else c = dst_small(s, items[i]) ? 0 : s.nblocks;
+        }
+        uint64_t incl = c;
+        for (int o = 1; o < 64; o <<= 1) { const uint64_t v = uint64_t(__shfl_up((unsigned long long)incl, o)); if (int(lane) >= o) incl += v; }
+        __syncthreads();                                   // the previous chunk's totals have been read
+        if (lane == 63) wsum[w] = incl;
+        __syncthreads();
+        uint64_t base = 0, total = 0;
+        for (uint32_t j = 0; j < kPlanThreads / 64; j++) { if (j < w) base += wsum[j]; total += wsum[j]; }
+        if (i < n) first[i] = carry + base + (incl - c);
+        carry += total;
+    }
+    if (nfast) atomicAdd(&taken[0], nfast);
+    if (nwalk) atomicAdd(&taken[1], nwalk);
+    __syncthreads();
+    if (t == 0) { sum->nblocks = carry; sum->fast = taken[0]; sum->walk = taken[1]; }
+}
+
+// Reduce, one wave per image over its slice of the descriptors: image_reduce_kernel's verdict with the fail offset counted from
+// the image's start, or the FOURMC_IMG_DST_SMALL status fourmc_gpu_image_decompress builds on the host.
+__global__ __launch_bounds__(64)
+void images_reduce_kernel(const fourmc_image_item* __restrict__ items, const fourmc_image_parse* __restrict__ ps,
+                          const uint64_t* __restrict__ first, const fourmc_block* __restrict__ desc, fourmc_image_status* __restrict__ status)
+{
+    const uint32_t i = blockIdx.x;
+    const fourmc_image_item it = items[i];
+    const fourmc_image_parse s = ps[i];
+    if (dst_small(s, it)) {
+        if (threadIdx.x) return;
+        fourmc_image_status r = {};
+        r.total_bytes = s.total; r.streams = s.streams;
+        r.reason = FOURMC_IMG_DST_SMALL; r.exit_code = fourmc_image_exit_code(FOURMC_IMG_DST_SMALL);
+        status[i] = r;
+        return;
+    }
+    reduce_verdict(desc + first[i], uint32_t(s.nblocks), ps + i, status + i, it.image_off);
 }
 
 // ------------------------------------------------------------------------------------------------------------- random access
@@ -917,6 +1023,28 @@ hipError_t fourmc_launch_image_reduce(const fourmc_block* d_blocks, uint32_t n, 
                                       fourmc_image_status* d_status, hipStream_t s)
 {
     hipLaunchKernelGGL(image_reduce_kernel, dim3(1), dim3(64), 0, s, d_blocks, n, d_ps, d_status);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_images_parse(const void* d_images, const fourmc_image_item* d_items, uint32_t n, uint32_t magic, int fast,
+                                      fourmc_image_parse* d_ps, const uint64_t* d_first, fourmc_block* d_desc, hipStream_t s)
+{
+    hipLaunchKernelGGL(images_parse_kernel, dim3(n), dim3(64), 0, s, static_cast<const uint8_t*>(d_images), d_items, magic, fast, d_ps,
+                       d_first, d_desc);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_images_plan(const fourmc_image_item* d_items, uint32_t n, const fourmc_image_parse* d_ps, int query,
+                                     uint64_t* d_first, fourmc_images_summary* d_sum, fourmc_image_status* d_status, hipStream_t s)
+{
+    hipLaunchKernelGGL(images_plan_kernel, dim3(1), dim3(kPlanThreads), 0, s, d_items, n, d_ps, query, d_first, d_sum, d_status);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_images_reduce(const fourmc_image_item* d_items, uint32_t n, const fourmc_image_parse* d_ps,
+                                       const uint64_t* d_first, const fourmc_block* d_desc, fourmc_image_status* d_status, hipStream_t s)
+{
+    hipLaunchKernelGGL(images_reduce_kernel, dim3(n), dim3(64), 0, s, d_items, d_ps, d_first, d_desc, d_status);
     return hipGetLastError();
 }
 

@@ -107,6 +107,20 @@ hipError_t fourmc_launch_image_parse(const void* d_image, uint64_t image_bytes, 
                                      fourmc_image_parse* d_ps, fourmc_block* d_blocks, hipStream_t s);
 hipError_t fourmc_launch_image_reduce(const fourmc_block* d_blocks, uint32_t n, const fourmc_image_parse* d_ps,
                                       fourmc_image_status* d_status, hipStream_t s);
+/* many images in one call (fourmc_gpu_images_decompress): what the plan leaves for the engine's first read-back */
+typedef struct fourmc_images_summary {
+    uint64_t nblocks;       /* descriptors of all images together (size query: every well-formed block) */
+    uint32_t fast, walk;    /* images the fast path / the walk accepted */
+} fourmc_images_summary;
+/* d_desc NULL: count every image into d_ps[i] (fast: try the footer-driven parser first); else fill the descriptors of the parse
+ * d_ps[i] holds at d_desc + d_first[i], offsets relative to d_images and to the items' common destination */
+hipError_t fourmc_launch_images_parse(const void* d_images, const fourmc_image_item* d_items, uint32_t n, uint32_t magic, int fast,
+                                      fourmc_image_parse* d_ps, const uint64_t* d_first, fourmc_block* d_desc, hipStream_t s);
+/* d_first[i] = descriptors before image i (none for an image that ends FOURMC_IMG_DST_SMALL), *d_sum; query: the parse-only statuses */
+hipError_t fourmc_launch_images_plan(const fourmc_image_item* d_items, uint32_t n, const fourmc_image_parse* d_ps, int query,
+                                     uint64_t* d_first, fourmc_images_summary* d_sum, fourmc_image_status* d_status, hipStream_t s);
+hipError_t fourmc_launch_images_reduce(const fourmc_image_item* d_items, uint32_t n, const fourmc_image_parse* d_ps,
+                                       const uint64_t* d_first, const fourmc_block* d_desc, fourmc_image_status* d_status, hipStream_t s);
 /* random access (image.hip, second half): the index summary plus where the last block must end (read_index's data_end) */
 typedef struct fourmc_image_index_dev {
     fourmc_image_index_info info;

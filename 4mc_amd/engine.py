@@ -8,8 +8,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .binding import (BLOCK_DTYPE, CODEC_LZ4_FAST, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageIndexInfo, ImageLines, ImageRange,
-                      ImageRecords, ImageSlice, ImageStatus, check, lib)
+from .binding import (BLOCK_DTYPE, CODEC_LZ4_FAST, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageIndexInfo, ImageItem, ImageLines,
+                      ImageRange, ImageRecords, ImageSlice, ImageStatus, check, lib)
 
 
 def _stream_ptr(stream):
@@ -144,6 +144,31 @@ def decompress_image(d_image, d_dst, magic=MAGIC_4MC, image_bytes=None, stream=N
     res = {name: int(getattr(st, name)) for name, _ in ImageStatus._fields_}
     res["message"] = lib().fourmc_gpu_image_reason_text(st.reason).decode()
     return res
+
+
+def decompress_images(d_images, items, d_dst, magic=MAGIC_4MC, images_bytes=None, stream=None):
+    """Decode many file images of one buffer with one call (fourmc_gpu_images_decompress).  `items` is a sequence of
+    (image_off, image_bytes, dst_off, dst_cap): image i is d_images[image_off:image_off + image_bytes] and its output region
+    d_dst[dst_off:dst_off + dst_cap].  d_dst None: the size query (dst_off and dst_cap are ignored).  Returns one status dict per
+    item, each what decompress_image returns for that image alone."""
+    ptr = _dev_ptr(d_images, "decompress_images d_images")
+    n = _image_len(d_images, images_bytes, "decompress_images")
+    dst, cap = (0, 0) if d_dst is None else (_dev_ptr(d_dst, "decompress_images d_dst"), d_dst.numel())
+    q = [tuple(int(v) for v in it) for it in items]
+    arr = (ImageItem * len(q))()
+    for i, (io, ib, do, dc) in enumerate(q):
+        arr[i].image_off, arr[i].image_bytes, arr[i].dst_off, arr[i].dst_cap = io, ib, do, dc
+    if d_dst is not None and dst == 0:          # an empty tensor has no address, and to the library NULL is the size query
+        raise EngineError("decompress_images: d_dst is empty (None asks for the sizes)")
+    check(lib().fourmc_gpu_images_decompress(ptr, n, dst, cap, magic, C.cast(arr, C.c_void_p), len(q), _stream_ptr(stream)),
+          "fourmc_gpu_images_decompress")
+    out = []
+    for i in range(len(q)):
+        st = arr[i].status
+        res = {name: int(getattr(st, name)) for name, _ in ImageStatus._fields_}
+        res["message"] = lib().fourmc_gpu_image_reason_text(st.reason).decode()
+        out.append(res)
+    return out
 
 
 def _image_len(d_image, image_bytes, what):

@@ -140,9 +140,9 @@ int fourmc_gpu_4mc_pack_image(const void* d_staging, void* d_image, const fourmc
                               const uint64_t* d_image_off, uint32_t n, void* stream);
 
 /* ---- whole file images in device memory ------------------------------------------------------------------------------------
- * "device image in -> device bytes out", with the result the CLI gives for the same bytes as a file.  Both calls synchronize
- * `stream`: the encode once (the image size), the decode twice (the block count its workspace is sized by, then the status).
- * No per-block data crosses to the host. */
+ * "device image in -> device bytes out", with the result the CLI gives for the same bytes as a file.  The calls synchronize
+ * `stream`: the encode once (the image size), the decode twice (the block count its workspace is sized by, then the status),
+ * the decode of many images twice as well.  No per-block data crosses to the host. */
 /* worst-case image size for src_bytes of input: header + 12 per block + src_bytes + end mark + footer */
 uint64_t fourmc_gpu_image_bound(uint64_t src_bytes);
 /* d_src[0, src_bytes) -> a complete .4mc (magic FOURMC_MAGIC_4MC) or .4mz (FOURMC_MAGIC_4MZ) file image at d_image, byte-identical
@@ -230,6 +230,36 @@ typedef struct fourmc_image_status {
  * payload, as with fourmc_gpu_4mc_decode_blocks.  env FOURMC_IMAGE_PARSE=walk forces the file-order walk (test knob). */
 int fourmc_gpu_image_decompress(const void* d_image, uint64_t image_bytes, void* d_dst, uint64_t dst_cap,
                                 uint32_t magic, fourmc_image_status* status, void* stream);
+/* Many images with one call: a Hadoop dataset is a directory of part files of a few blocks each, and one call per image leaves
+ * most of the chip idle for a launch latency per file.  All images lie in ONE device buffer and all outputs go to ONE device
+ * buffer, so a single descriptor table describes every block of every image and one block decode serves them all.
+ * The one rule.  After the call, items[i].status equals, field for field, what the single-image decompress call above returns
+ *   for d_images + image_off, image_bytes, d_dst + dst_off, dst_cap and the same magic, and d_dst[dst_off, dst_off +
+ *   decoded_bytes) holds the same bytes: for clean images, framing damage of every kind, a block that fails its XXH32 or its
+ *   decode, concatenated streams, trailing bytes, the empty stream that ends a file, and FOURMC_IMG_DST_SMALL when the image's
+ *   total_bytes exceeds its own dst_cap (nothing written for that image).  fail_offset is an offset in the image, not in the
+ *   buffer.  A damaged image changes nothing about its neighbours.  Two items may name the same image bytes.
+ * Size query.  d_dst NULL: the parse-only statuses of every item; dst_off, dst_cap and dst_bytes are ignored.
+ * Writes.  Nothing outside the items' output regions; for an item, nothing outside [dst_off, dst_off + total_bytes).
+ * Arguments.  Checked on the host before any device is looked for; each of these returns FOURMC_EINVAL with `items` untouched: a
+ *   magic that is neither 4mc nor 4mz; items NULL with n > 0; d_images NULL with a nonzero image_bytes; an image that does not
+ *   lie inside [0, images_bytes); with d_dst not NULL, an output region that does not lie inside [0, dst_bytes), or two output
+ *   regions of nonzero dst_cap that overlap.  n == 0 returns FOURMC_OK and does nothing.  More than 0x7FFFFFFF blocks in all:
+ *   FOURMC_EUNSUP.  No device: FOURMC_ENODEV.  On every failure `items` is left as it came.
+ * Slack.  The decoders may read up to 64 bytes past a payload: inside the buffer that is the next image; behind the last image
+ *   the caller keeps slack, as with the single call.
+ * Settings.  FOURMC_IMAGE_PARSE=walk, FOURMC_DECODE, FOURMC_ZDECODE and the batch limits of the block decode apply as they do to
+ *   the single call; the parse statistics below count each image once, under the parser that accepted it.
+ * Synchronizations of `stream`: two, however many images there are (the block count the workspace is sized by, then the
+ *   statuses); the size query takes one.  `items` crosses to the device once and the statuses come back once.
+ * Not reproduced: a batched encode, .4mc and .4mz in one call, images at unrelated device pointers. */
+typedef struct fourmc_image_item {      /* 72 bytes */
+    uint64_t image_off, image_bytes;    /* in : the image is d_images[image_off, image_off + image_bytes)           */
+    uint64_t dst_off, dst_cap;          /* in : its output region is d_dst[dst_off, dst_off + dst_cap)              */
+    fourmc_image_status status;         /* out                                                                       */
+} fourmc_image_item;
+int fourmc_gpu_images_decompress(const void* d_images, uint64_t images_bytes, void* d_dst, uint64_t dst_bytes,
+                                 uint32_t magic, fourmc_image_item* items /*host*/, uint32_t n, void* stream);
 /* the exact text fourmc_file.c prints for a FOURMC_IMG_* verdict ("" for FOURMC_IMG_OK) */
 const char* fourmc_gpu_image_reason_text(int reason);
 /* Statistics (read-only): images fourmc_gpu_image_decompress has parsed so far with the footer-driven fast path and with the
