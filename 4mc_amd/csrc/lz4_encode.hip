@@ -14,7 +14,8 @@
 //     2048-block launch needs (a 16 KiB variant that tagged the table in the sparse batch too
 //     measured 11 % slower and was not kept);
 //   * "dense window": lane l takes position sp+l whatever role the walk will give it, prepares
-//     candidate / 4-byte test / match extents against the table as it stands; lanes sharing a
+//     candidate / 4-byte test / match extents against the table as it stands (its own bytes come from an LDS ring
+//     that runs a KiB ahead of the cursor - 32-bit table only, in the scoreboard's memory); lanes sharing a
 //     slot are found on the table itself (lane tags, atomic max); a scalar walk of one readlane
 //     per sequence chooses the hit lanes; sizes and output positions of the chosen sequences are
 //     then computed by all lanes at once and their records (lz4emit.h) written in one store, and the
@@ -43,6 +44,11 @@ constexpr int      kSmallLim  = 65536 + 11;  // lz4.c:689 LZ4_64Klimit
 constexpr uint32_t kMaxDist   = 65535;       // lz4.h:633
 constexpr int      kMfLimit   = 12, kLastLit = 5, kMinLen = 13;
 constexpr int      kScore     = 1024;        // entries of the same-slot scoreboard
+// Input ring of the 32-bit-table instance (it lives in the scoreboard's memory, which that instance's dense windows do not
+// use): the stream around the cursor in pieces of kPiece bytes, 16-byte aligned in memory; piece k sits at (k & 1) * kPiece
+// and an even piece once more behind the odd one, so that the 64 bytes a lane reads never wrap.
+constexpr uint32_t kPiece     = 1024, kPieceLog = 10, kRing = 2 * kPiece;
+static_assert(kRing + kPiece <= kScore * 4, "the ring and its mirrored piece share the scoreboard");
 
 template <bool U32TAB> __device__ __forceinline__ uint32_t hash_at(const uint8_t* p)
 {
@@ -59,6 +65,7 @@ __device__ __forceinline__ uint32_t probe_offset(uint32_t K)
     return 1 + T + 32 * m * (m - 1) + m * r;
 }
 
+__device__ __forceinline__ uint32_t VG(uint32_t v) { asm("" : "+v"(v)); return v; }                                // keep in a VGPR
 __device__ __forceinline__ uint32_t U(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }   // pin to an SGPR
 
 // 16 bytes at p, any alignment, as four dwords (one global_load_dwordx4)
@@ -66,6 +73,16 @@ struct Q16 { uint32_t d0, d1, d2, d3; };
 __device__ __forceinline__ Q16 ld16(const uint8_t* p) { const U16B t = *reinterpret_cast<const U16B*>(p); return Q16{uint32_t(t.a), uint32_t(t.a >> 32), uint32_t(t.b), uint32_t(t.b >> 32)}; }
 __device__ __forceinline__ uint64_t u64(uint32_t lo, uint32_t hi) { return (uint64_t(hi) << 32) | lo; }
 __device__ __forceinline__ uint32_t rl(uint32_t v, int l) { return uint32_t(__builtin_amdgcn_readlane(int(v), l)); }
+__device__ __forceinline__ uint32_t lds_addr(const void* p) { return uint32_t(uintptr_t((const __attribute__((address_space(3))) void*)p)); }
+// 32 bytes at LDS address a, any alignment (ds_read_b128 takes every byte alignment on gfx950): both reads and their wait as
+// one piece.  (The compiler emits a ds_read_b128 for a packed 16-byte LDS read as well; this form is the one that was measured.)
+__device__ __forceinline__ void lds_ld32(uint32_t a, Q16& x, Q16& y)
+{
+    typedef uint32_t v4 __attribute__((ext_vector_type(4)));
+    v4 u, v;
+    asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)" : "=&v"(u), "=&v"(v) : "v"(a) : "memory");
+    x = Q16{u.x, u.y, u.z, u.w}; y = Q16{v.x, v.y, v.z, v.w};
+}
 
 // wave64 inclusive prefix sum on the DPP network (row shifts, then row broadcasts)
 template <int CTRL, int ROWMASK>
@@ -90,7 +107,7 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
 {
     uint16_t* tab16 = reinterpret_cast<uint16_t*>(tab32);
 #ifdef K2_PROF   // one-off phase profile (tools/k2_phases.py builds a side library with -DK2_PROF): cycles per phase
-    uint64_t pt_search = 0, pt_ext = 0, pt_match = 0, pt_cur = 0, pt_tab = 0, pt_gather = 0, pt_emit = 0, pt_nwin = 0, pt_nseq = 0, pt_nslow = 0, pt_none = 0, pt_cross = 0, pt_dcut = 0, pt_scut = 0, pt_prep = 0, pt_gen = 0, pt_nit = 0, pt0 = __builtin_readcyclecounter(), pt1;
+    uint64_t pt_search = 0, pt_ext = 0, pt_match = 0, pt_cur = 0, pt_tab = 0, pt_gather = 0, pt_emit = 0, pt_nwin = 0, pt_nseq = 0, pt_nslow = 0, pt_none = 0, pt_cross = 0, pt_dcut = 0, pt_scut = 0, pt_prep = 0, pt_gen = 0, pt_nit = 0, pt_nrel = 0, pt_nrot = 0, pt_nrst = 0, pt_ring = 0, pt0 = __builtin_readcyclecounter(), pt1;
 #define K2PH(acc) do { __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_sched_barrier(0); pt1 = __builtin_readcyclecounter(); acc += pt1 - pt0; pt0 = pt1; __builtin_amdgcn_sched_barrier(0); } while (0)
 #define K2CNT(c) do { c++; } while (0)
 #else
@@ -115,6 +132,39 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
     auto enc = [&](uint32_t pos, uint32_t ck) -> uint32_t { return U32TAB ? (pos << cbits) | ck : pos; };
     auto tab_get = [&](uint32_t h) -> uint32_t { return U32TAB ? tab32[h] : uint32_t(tab16[h]); };
     auto tab_put = [&](uint32_t h, uint32_t pos, uint32_t ck) { if (U32TAB) tab32[h] = enc(pos, ck); else tab16[h] = uint16_t(pos); };
+
+    // Input ring (32-bit table only; kPiece above).  The bytes of the stream do not depend on the parse: they come in with
+    // aligned 16-byte loads, a piece ahead of the cursor, and a dense window reads its 32 (64) bytes per lane from LDS - so its
+    // first round trip is an LDS one and does not queue behind the previous window's record store.  State: pieces rend-2 and
+    // rend-1 are in LDS and piece rend is on its way in `rnext`; rend 0 = no ring, the scoreboard is all ones.  The coordinate
+    // of position p is p + ralign, which makes every piece load aligned in memory.
+    auto ralign_now = [&]() -> uint32_t {                               // (taken from src where it is used: not one more scalar kept across the walk)
+        uint32_t a;
+        asm volatile("s_and_b32 %0, %1, 15" : "=s"(a) : "s"(uint32_t(reinterpret_cast<uintptr_t>(src))) : "scc");
+        return a;
+    };
+    uint8_t* const ring = reinterpret_cast<uint8_t*>(score);
+    uint32_t rend = VG(0);
+    Q16 rnext{0, 0, 0, 0};
+    auto piece_load = [&](uint32_t k) -> Q16 {
+        const int p = int(k * kPiece + 16u * uint32_t(lane)) - int(ralign_now());
+        Q16 v{0, 0, 0, 0};
+        if (p >= 0 && p + 16 <= n) { const uint4 t = *reinterpret_cast<const uint4*>(src + p); v = Q16{t.x, t.y, t.z, t.w}; }
+        else if (p + 16 > 0 && p < n) {
+            // the two ends of the block: only bytes of [src, src + n) are read - the nearest 16 of them, moved to their place
+            const int pc = min(max(p, 0), n - 16);
+            const U16B t = *reinterpret_cast<const U16B*>(src + pc);
+            unsigned __int128 w = (static_cast<unsigned __int128>(t.b) << 64) | t.a;
+            w = p > pc ? w >> (8 * (p - pc)) : w << (8 * (pc - p));
+            v = Q16{uint32_t(w), uint32_t(w >> 32), uint32_t(w >> 64), uint32_t(w >> 96)};
+        }
+        return v;
+    };
+    auto piece_store = [&](uint32_t k, const Q16& v) {
+        const uint32_t o = ((k & 1u) << kPieceLog) + 16u * uint32_t(lane);
+        *reinterpret_cast<uint4*>(ring + o) = make_uint4(v.d0, v.d1, v.d2, v.d3);
+        if (!(k & 1u)) *reinterpret_cast<uint4*>(ring + kRing + o) = make_uint4(v.d0, v.d1, v.d2, v.d3);
+    };
 
     if (n >= kMinLen) {
         const uint32_t un = uint32_t(n);
@@ -196,7 +246,6 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
         // whose ip-2 refill and immediate re-test (lz4.c:1207-1259) are still owed and whose search starts at sp+1;
         // otherwise it is probe number k0 of the running search.
         uint32_t sp = 1, k0 = 0; bool retest = false;
-        uint32_t pw_sp = 0xFFFFFFFFu;                                   // previous dense window: start
         for (;;) {
             if (rc > reccap - kRecSlack) {
                 // the record area is full (only a block above FOURMC_BLOCKSIZE gets here): its bytes go out now
@@ -217,7 +266,29 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 // ("dirty") cannot trust its candidate: when the walk reaches it as a probe the window ends there.
                 const uint32_t sp0 = sp;
                 const uint32_t pos = sp0 + uint32_t(lane);
-                const Q16 q0 = ld16(src + pos - 4), q1 = ld16(src + pos + 12);          // [pos-4, pos+28)
+                Q16 q0, q1;                                                              // [pos-4, pos+28)
+                uint32_t rpos = 0;                                                       // where they are in the ring
+                if (U32TAB) {
+                    // The window reads [sp0-4, sp0+124): at most two pieces.  When it reaches piece `rend` the ring moves on by
+                    // the piece in `rnext` (loaded a piece ago: no wait); after a jump past that, or after a sparse batch, it
+                    // starts again at the window (a trip to memory, as every window paid before) - and the next piece is asked for
+                    const uint32_t a0 = sp0 + ralign_now() - 4;
+                    const uint32_t c_lo = a0 >> kPieceLog, c_hi = (a0 + 127) >> kPieceLog;
+                    if (c_hi >= rend) {
+                        bool have = rend != 0 && c_hi == rend;          // `rnext` is piece k
+                        uint32_t k = have ? rend : c_lo - 1u;
+                        if (have) K2CNT(pt_nrot); else K2CNT(pt_nrel);
+                        do {
+                            if (have) piece_store(k, rnext);
+                            have = true; k++;
+                            rnext = piece_load(k);
+                        } while (k <= c_hi);
+                        rend = VG(k);
+                    }
+                    K2PH(pt_ring);
+                    rpos = lds_addr(ring) + ((a0 + uint32_t(lane)) & (kRing - 1));
+                    lds_ld32(rpos, q0, q1);
+                } else { q0 = ld16(src + pos - 4); q1 = ld16(src + pos + 12); }
                 K2PH(pt_cur); K2CNT(pt_nwin);
                 const uint64_t v8 = u64(q0.d1, q0.d2);
                 const uint32_t h = hash_of<U32TAB>(v8);
@@ -277,7 +348,9 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 const bool sat = hit && fw == 24;
                 if (__ballot(sat)) {
                     if (sat) {
-                        const Q16 q2 = ld16(src + pos + 28), q3 = ld16(src + pos + 44), c2 = ld16(src + c + 28), c3 = ld16(src + c + 44);
+                        Q16 q2, q3;
+                        if (U32TAB) lds_ld32(rpos + 32, q2, q3); else { q2 = ld16(src + pos + 28); q3 = ld16(src + pos + 44); }
+                        const Q16 c2 = ld16(src + c + 28), c3 = ld16(src + c + 44);
                         const uint64_t x3 = u64(q2.d0, q2.d1) ^ u64(c2.d0, c2.d1), x4 = u64(q2.d2, q2.d3) ^ u64(c2.d2, c2.d3),
                                        x5 = u64(q3.d0, q3.d1) ^ u64(c3.d0, c3.d1), x6 = u64(q3.d2, q3.d3) ^ u64(c3.d2, c3.d3);
                         fw = x3 ? 24u + uint32_t(__builtin_ctzll(x3) >> 3) : (x4 ? 32u + uint32_t(__builtin_ctzll(x4) >> 3)
@@ -300,16 +373,15 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 const unsigned long long m_cond = __ballot(second && (hitA || hit));
                 const unsigned long long m_hit = __ballot(hit) & ~m_cond, m_dirty = __ballot(dirty), m_slow = __ballot(hit && slow);
                 K2PH(pt_gather);
-                // The first sequence may own literals of the previous window: they are still in registers if that was
-                // a dense window too (pw_sp); anything older goes through the general path.  Near the end of the
-                // output buffer every sequence does, for its exact capacity checks.
-                const uint32_t pw_lo = (pw_sp != 0xFFFFFFFFu && pw_sp + 64 >= sp0) ? pw_sp : sp0;
-                const bool capok = !limited || op + 320 <= uint32_t(cap);
+                // The first sequence may own literals from before the window, any number of them: its record needs only
+                // where they begin.  Near the end of the output buffer (what the window can write at most: those literals
+                // and 320 bytes) every sequence goes through the general path, for its exact capacity checks.
+                const uint32_t before = anchor < sp0 ? sp0 - anchor : 0u;
+                const bool capok = !limited || op + before + before / 255 + 320 <= uint32_t(cap);
                 unsigned long long stop2 = m_dirty | m_slow | m_cond | (capok ? 0ull : m_hit);
                 unsigned long long stop1 = stop2;
                 const int scut = (!retest && k0 > 1) ? 65 - int(k0) : 64;   // first lane that is not one byte on from its predecessor
                 if (scut < 64) stop1 |= 1ull << scut;
-                if (anchor < pw_lo) stop1 |= m_hit & (0ull - m_hit);
                 const unsigned long long hd2 = m_hit | stop2;
                 unsigned long long hd = m_hit | stop1, stp = stop1;
                 unsigned long long selw = 0, xint = 0;                  // chosen hit lanes; lanes inside directly emitted matches
@@ -394,7 +466,7 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                         const int myanc = below ? endP : anc0;           // my anchor: the end of the sequence chosen before me
                         const uint32_t b = uint32_t(min(int((info >> 8) & 7), lane - myanc));
                         const uint32_t lit = uint32_t(lane - myanc) - b, mc = (info & 255) - uint32_t(lane) - 4 + b;
-                        const uint32_t size = mine ? 3 + lit + (lit >= 15 ? 1u : 0u) + (mc >= 15 ? 1u : 0u) : 0u;
+                        const uint32_t size = mine ? 3 + lit + (lit >= 15 ? (lit - 15) / 255 + 1 : 0u) + (mc >= 15 ? 1u : 0u) : 0u;
                         const uint32_t incl = scan_add(size);
                         if (mine) rec[rc + uint32_t(__popcll(below))] = make_uint4(op + incl - size, sp0 + uint32_t(myanc), lit, pos - c);
                         rc = U(rc + uint32_t(__popcll(sel)));
@@ -491,7 +563,6 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                         else for (;;) { tab16[h] = uint16_t(pos); asm volatile("" ::: "memory"); if (uint32_t(tab16[h]) >= pos) break; }
                     }
                 }
-                pw_sp = sp0;
                 sp = U(sp); k0 = U(k0);
                 K2PH(pt_match);
                 continue;
@@ -502,7 +573,12 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
             // the batch; it is cut at the first lane that shares a table slot with an earlier one.
             {
                 const bool rt = retest;                                 // lane 0 is the re-test of sp, the search starts at sp+1
-                pw_sp = 0xFFFFFFFFu;
+                if (U32TAB && rend != 0) {                              // the ring's memory is the scoreboard again
+#pragma unroll
+                    for (uint32_t i = 0; i < (kRing + kPiece) / 16; i += 64) reinterpret_cast<uint4*>(score)[i + uint32_t(lane)] = make_uint4(~0u, ~0u, ~0u, ~0u);
+                    rend = VG(0);
+                    K2CNT(pt_nrst);
+                }
                 uint32_t pos, next;
                 if (k0 == 0) { pos = sp + lane; next = pos + 1; }
                 else { pos = sp + probe_offset(k0 + lane) - probe_offset(k0); next = sp + probe_offset(k0 + lane + 1) - probe_offset(k0); }
@@ -583,7 +659,7 @@ last_literals:
         op += 1 + (run >= 15 ? (run - 15) / 255 + 1 : 0) + run;
     }
 #ifdef K2_PROF
-    if (lane == 0 && n == (4 << 20)) { uint64_t* c = reinterpret_cast<uint64_t*>(dst + n - 32); c[0] = pt_search; c[1] = pt_ext; c[2] = pt_match; uint64_t* d = reinterpret_cast<uint64_t*>(dst + n - 128); d[0] = pt_cur; d[1] = pt_tab; d[2] = pt_gather; d[3] = pt_emit; d[4] = pt_nwin; d[5] = pt_nseq; d[6] = pt_nslow; uint64_t* f = reinterpret_cast<uint64_t*>(dst + n - 192); f[0] = pt_none; f[1] = pt_cross; f[2] = pt_dcut; f[3] = pt_scut; f[4] = pt_prep; f[5] = pt_gen; f[6] = pt_nit; }
+    if (lane == 0 && n == (4 << 20)) { uint64_t* c = reinterpret_cast<uint64_t*>(dst + n - 32); c[0] = pt_search; c[1] = pt_ext; c[2] = pt_match; uint64_t* d = reinterpret_cast<uint64_t*>(dst + n - 128); d[0] = pt_cur; d[1] = pt_tab; d[2] = pt_gather; d[3] = pt_emit; d[4] = pt_nwin; d[5] = pt_nseq; d[6] = pt_nslow; uint64_t* f = reinterpret_cast<uint64_t*>(dst + n - 192); f[0] = pt_none; f[1] = pt_cross; f[2] = pt_dcut; f[3] = pt_scut; f[4] = pt_prep; f[5] = pt_gen; f[6] = pt_nit; uint64_t* g = reinterpret_cast<uint64_t*>(dst + n - 256); g[0] = pt_nrel; g[1] = pt_nrot; g[2] = pt_nrst; g[3] = pt_ring; }
 #endif
     nrec = rc;
     return int(op);
@@ -599,7 +675,7 @@ void lz4_encode_fast_kernel(const uint8_t* __restrict__ src_base, uint8_t* dst_b
                             fourmc_block* blocks, uint32_t nblocks, int container_mode, uint8_t* work, uint32_t reccap)
 {
     __shared__ uint32_t tab[1 << kHashLog];
-    __shared__ uint32_t score[kScore];
+    __shared__ __attribute__((aligned(16))) uint32_t score[kScore];   // (16: the 32-bit-table instance keeps its input ring here)
     const uint32_t b = blockIdx.x;
     if (b >= nblocks) return;
     const fourmc_block blk = uniform_block(blocks[b]);
