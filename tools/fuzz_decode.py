@@ -10,18 +10,16 @@ import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import helpers
+import lz4_shapes
 gpu = importlib.import_module("4mc_amd"); gpu.gpu_init(0)
 
 
 def build_stream(rng, target):
-    """a valid LZ4 block of about `target` decoded bytes from random sequences; returns (stream, decoded)"""
-    out = bytearray(); dec = bytearray()
+    """a valid LZ4 block of about `target` decoded bytes from random sequences, assembled by the suite's builder
+    (tests/lz4_shapes.py: build); returns (stream, decoded)"""
+    seqs, n = [], 0
     style = int(rng.integers(0, 6))
-    def lenbytes(v):
-        b = bytearray()
-        while v >= 255: b.append(255); v -= 255
-        b.append(v); return b
-    while len(dec) < target:
+    while n < target:
         lit_cls = int(rng.integers(0, 10))
         if style == 0: L = int(rng.integers(0, 4))                                   # dense tokens: up to 21 per row
         elif style == 1: L = int(rng.integers(0, 40))
@@ -29,7 +27,7 @@ def build_stream(rng, target):
         elif lit_cls < 8: L = int(rng.integers(15, 270))
         elif lit_cls < 9: L = int(rng.integers(270, 2000))
         else: L = int(rng.integers(2000, 70000))
-        if len(dec) == 0 and L == 0: L = 1                                            # the first match needs something behind it
+        if n == 0 and L == 0: L = 1                                                   # the first match needs something behind it
         m_cls = int(rng.integers(0, 10))
         if style == 0: M = int(rng.integers(4, 8))
         elif m_cls < 5: M = int(rng.integers(4, 19))
@@ -38,23 +36,11 @@ def build_stream(rng, target):
         else: M = int(rng.integers(3000, 200000))
         lits = rng.integers(0, 256, L, dtype=np.uint8).tobytes() if style != 5 else bytes([int(rng.integers(0, 3))]) * L
         o_cls = int(rng.integers(0, 6))
-        avail = len(dec) + L
-        hi = min(avail, 65535)
+        hi = min(n + L, 65535)
         off = 1 if o_cls == 0 else int(rng.integers(1, min(hi, 8) + 1)) if o_cls == 1 else int(rng.integers(1, min(hi, 300) + 1)) if o_cls < 4 else int(rng.integers(1, hi + 1))
-        out.append((min(L, 15) << 4) | min(M - 4, 15))
-        if L >= 15: out += lenbytes(L - 15)
-        out += lits; dec += lits
-        out += bytes([off & 255, off >> 8])
-        if M - 4 >= 15: out += lenbytes(M - 4 - 15)
-        start = len(dec) - off
-        for k in range(M): dec.append(dec[start + k])
+        seqs.append((lits, off, M)); n += L + M
     # the block's end: a last sequence of literals only, at least 5, the last match 12 bytes before the end (lz4.c:243-247)
-    L = int(rng.integers(12, 40))
-    lits = rng.integers(0, 256, L, dtype=np.uint8).tobytes()
-    out.append(min(L, 15) << 4)
-    if L >= 15: out += lenbytes(L - 15)
-    out += lits; dec += lits
-    return np.frombuffer(bytes(out), np.uint8).copy(), np.frombuffer(bytes(dec), np.uint8).copy()
+    return lz4_shapes.build(seqs, rng.integers(0, 256, int(rng.integers(12, 40)), dtype=np.uint8).tobytes())
 
 
 def decode_batch(comps, caps):
