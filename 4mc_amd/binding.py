@@ -36,6 +36,15 @@ class ImageItem(C.Structure):
 assert C.sizeof(ImageItem) == 72
 
 
+# struct fourmc_image_enc_item (include/fourmc_gpu.h: many images encoded with one call)
+class ImageEncItem(C.Structure):
+    _fields_ = [("src_off", C.c_uint64), ("src_bytes", C.c_uint64), ("image_off", C.c_uint64), ("image_cap", C.c_uint64),
+                ("image_bytes", C.c_uint64)]
+
+
+assert C.sizeof(ImageEncItem) == 40
+
+
 # struct fourmc_image_entry / fourmc_image_index_info / fourmc_image_range (include/fourmc_gpu.h: random access)
 class ImageEntry(C.Structure):
     _fields_ = [("image_off", C.c_uint64), ("data_off", C.c_uint64), ("usize", C.c_uint32), ("csize", C.c_uint32),
@@ -127,6 +136,7 @@ _GPU_API = {
     "fourmc_gpu_4mc_pack_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_image_bound": (C.c_uint64, [C.c_uint64]),
     "fourmc_gpu_image_compress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
+    "fourmc_gpu_images_compress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_image_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_images_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_image_reason_text": (C.c_char_p, [C.c_int]),

@@ -512,6 +512,86 @@ int fourmc_gpu_image_compress(const void* d_src, uint64_t src_bytes, void* d_ima
     return FOURMC_OK;
 }
 
+// Many images with one call.  Every size is known on the host, so the argument loop lays out the tables: image i owns descriptors
+// [first, first + nblocks) and a run of staging slots from stage_off, each block's slot its src_len rounded up to 256 bytes (only an
+// image's last block is short, so the image's run is its src_bytes rounded up and block b's slot starts b * 4 MiB into it).
+// Workspace (g_img_ws), one lease: the results, the plans, the end offsets, the dense offset table, the descriptors, the staging and
+// kImagesStageSlack bytes behind it.  One upload (the plans), one container encode, one pack, one read-back (the results).
+constexpr size_t kImagesStageSlack = 4096;
+int fourmc_gpu_images_compress(const void* d_src, uint64_t src_total, void* d_images, uint64_t images_bytes,
+                               uint32_t magic, int level, fourmc_image_enc_item* items, uint32_t n, void* stream)
+{
+    if (magic != FOURMC_MAGIC_4MC && magic != FOURMC_MAGIC_4MZ) { snprintf(g_err, sizeof g_err, "magic 0x%08x is neither 4mc nor 4mz", magic); return FOURMC_EINVAL; }
+    if (n == 0) return FOURMC_OK;
+    if (!items) { snprintf(g_err, sizeof g_err, "images_compress: null items"); return FOURMC_EINVAL; }
+    if (!d_images) { snprintf(g_err, sizeof g_err, "images_compress: null images"); return FOURMC_EINVAL; }
+    std::vector<fourmc_image_enc_plan> plans(n);
+    uint64_t nb64 = 0, stage = 0;
+    {
+        std::vector<std::pair<uint64_t, uint64_t>> d(n);
+        for (uint32_t i = 0; i < n; i++) {
+            const fourmc_image_enc_item& it = items[i];
+            if (it.src_bytes && !d_src) { snprintf(g_err, sizeof g_err, "images_compress: null source"); return FOURMC_EINVAL; }
+            if (it.src_off > src_total || it.src_bytes > src_total - it.src_off) {
+                snprintf(g_err, sizeof g_err, "images_compress: the source of image %u lies beyond the %llu bytes of sources", i, (unsigned long long)src_total);
+                return FOURMC_EINVAL;
+            }
+            const uint64_t k = it.src_bytes / FOURMC_BLOCKSIZE + (it.src_bytes % FOURMC_BLOCKSIZE ? 1 : 0);
+            if (k > 0x3FFFFFFFull) { snprintf(g_err, sizeof g_err, "images_compress: image %u has %llu blocks", i, (unsigned long long)k); return FOURMC_EINVAL; }
+            if (it.image_off > images_bytes || it.image_cap > images_bytes - it.image_off) {
+                snprintf(g_err, sizeof g_err, "images_compress: the region of image %u lies beyond the %llu bytes of images", i, (unsigned long long)images_bytes);
+                return FOURMC_EINVAL;
+            }
+            if (it.image_cap < fourmc_gpu_image_bound(it.src_bytes)) {
+                snprintf(g_err, sizeof g_err, "images_compress: image %u: capacity %llu below the bound %llu", i, (unsigned long long)it.image_cap,
+                         (unsigned long long)fourmc_gpu_image_bound(it.src_bytes));
+                return FOURMC_EINVAL;
+            }
+            d[i] = { it.image_off, it.image_off + it.image_cap };
+            fourmc_image_enc_plan& pl = plans[i];
+            pl.src_off = it.src_off; pl.src_bytes = it.src_bytes; pl.image_off = it.image_off; pl.stage_off = stage;
+            pl.first = uint32_t(nb64 > 0x7FFFFFFFull ? 0 : nb64); pl.nblocks = uint32_t(k);
+            nb64 += k; stage += (it.src_bytes + 255) & ~uint64_t(255);
+        }
+        std::sort(d.begin(), d.end());
+        for (size_t i = 1; i < d.size(); i++)
+            if (d[i].first < d[i - 1].second) {
+                snprintf(g_err, sizeof g_err, "images_compress: image regions overlap at %llu", (unsigned long long)d[i].first);
+                return FOURMC_EINVAL;
+            }
+    }
+    if (nb64 > 0x7FFFFFFFull) { snprintf(g_err, sizeof g_err, "images_compress: %llu blocks", (unsigned long long)nb64); return FOURMC_EUNSUP; }
+    if (int r = ensure_device()) return r;
+    const uint32_t nb = uint32_t(nb64);
+    int codec_level = 0;
+    const int codec = fourmc_level_codec(magic, level, &codec_level);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t o_plan = align256(size_t(n) * sizeof(fourmc_image_enc_result)), o_end = o_plan + align256(size_t(n) * sizeof(fourmc_image_enc_plan));
+    const size_t o_off = o_end + align256(size_t(n) * 8), o_blk = o_off + align256(size_t(nb) * 8);
+    const size_t o_stage = o_blk + align256(size_t(nb) * sizeof(fourmc_block));
+    WsLease ws(&g_img_ws); void* w = nullptr;
+    if (int r = ws.get(s, o_stage + size_t(stage) + kImagesStageSlack, &w)) return r;
+    char* base = static_cast<char*>(w);
+    auto* d_res = reinterpret_cast<fourmc_image_enc_result*>(base);
+    auto* d_plans = reinterpret_cast<fourmc_image_enc_plan*>(base + o_plan);
+    auto* d_end = reinterpret_cast<uint64_t*>(base + o_end);
+    auto* d_off = reinterpret_cast<uint64_t*>(base + o_off);
+    auto* d_blk = reinterpret_cast<fourmc_block*>(base + o_blk);
+    void* d_stage = base + o_stage;
+    HIP_TRY(hipMemcpyAsync(d_plans, plans.data(), size_t(n) * sizeof(fourmc_image_enc_plan), hipMemcpyHostToDevice, s));
+    HIP_TRY(fourmc_launch_images_enc_desc(d_plans, n, d_blk, nb, s));
+    if (nb) { if (int r = fourmc_gpu_4mc_encode_blocks(d_src, d_stage, d_blk, nb, codec, codec_level, s)) return r; }
+    HIP_TRY(fourmc_launch_images_enc_frame(d_images, d_plans, n, d_blk, nb, d_off, d_end, magic, d_stage, d_res, s));
+    std::vector<fourmc_image_enc_result> back(n);
+    HIP_TRY(hipMemcpyAsync(back.data(), d_res, size_t(n) * sizeof(fourmc_image_enc_result), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    uint64_t bad = 0;
+    for (uint32_t i = 0; i < n; i++) bad += back[i].bad_blocks;
+    if (bad) { snprintf(g_err, sizeof g_err, "images_compress: %llu blocks with an encoder result outside [1, src_len]", (unsigned long long)bad); return FOURMC_EINVAL; }
+    for (uint32_t i = 0; i < n; i++) items[i].image_bytes = back[i].image_bytes;
+    return FOURMC_OK;
+}
+
 // ------------------------------------------------------------------------ streaming image writer (image.hip)
 // One device allocation per writer, made by begin and freed by finish / abort: the running state, the descriptors of one batch, the
 // index (the absolute offset of every block header, then the running offset behind the last one), the carry slot and the staging.

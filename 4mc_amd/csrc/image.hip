@@ -15,6 +15,8 @@
 // runs on from the offset the previous batch left in the writer's device index.
 // Many images (fourmc_gpu_images_decompress): the same parsers and reduction, one wave per image of one buffer, and a plan that
 // gives every image its slice of one descriptor table.
+// Many images, the encode (fourmc_gpu_images_compress): the same descriptors, scan and tail, one wave or workgroup per image, over
+// slices of one descriptor table and one dense offset table that the engine has laid out from the sizes.
 // Random access (second half): the footer index of a single stream, block-range decodes and byte-range reads, each with the
 // verdict fourmc_file_decode_blocks (fourmc_file.c) reaches on the same bytes as a file.
 // Streaming reads (last part): the walk restated to stop at the end of each appended chunk and resume at the next, the gather of
@@ -73,10 +75,11 @@ __device__ __forceinline__ uint32_t scan_add(uint32_t v)
 __device__ __forceinline__ uint32_t wave_total(uint32_t incl) { return uint32_t(__builtin_amdgcn_readlane(int(incl), 63)); }
 
 // ------------------------------------------------------------------------------------------------------------- encode
-// block b of n: src0 + b * 4 MiB of the source, dst0 + b * 4 MiB of the staging, src_len = what is left of src_bytes, at most 4 MiB
-__device__ __forceinline__ void enc_desc(fourmc_block* __restrict__ blocks, uint64_t src0, uint64_t dst0, uint64_t src_bytes, uint32_t n)
+// block b of an item's n: src0 + b * 4 MiB of the source, dst0 + b * 4 MiB of the staging, src_len = what is left of src_bytes, at
+// most 4 MiB.  The item's descriptors are blocks[0, n): a single image and a writer's batch pass the table, one image of many its slice.
+__device__ __forceinline__ void enc_desc(fourmc_block* __restrict__ blocks, uint64_t src0, uint64_t dst0, uint64_t src_bytes, uint32_t n,
+                                         uint32_t b)
 {
-    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
     if (b >= n) return;
     const uint64_t at = uint64_t(b) * kBlock;
     fourmc_block d;
@@ -87,24 +90,21 @@ __device__ __forceinline__ void enc_desc(fourmc_block* __restrict__ blocks, uint
 }
 __global__ __launch_bounds__(256)
 void image_enc_desc_kernel(fourmc_block* __restrict__ blocks, uint64_t src_bytes, uint32_t n)
-{ enc_desc(blocks, 0, 0, src_bytes, n); }
+{ enc_desc(blocks, 0, 0, src_bytes, n, blockIdx.x * 256 + threadIdx.x); }
 // a batch of the streaming writer: its blocks start at src0 of its chunk (or of the carry slot) and at dst0 of its staging
 __global__ __launch_bounds__(256)
 void image_wr_desc_kernel(fourmc_block* __restrict__ blocks, uint64_t src0, uint64_t dst0, uint64_t src_bytes, uint32_t n)
-{ enc_desc(blocks, src0, dst0, src_bytes, n); }
+{ enc_desc(blocks, src0, dst0, src_bytes, n, blockIdx.x * 256 + threadIdx.x); }
 
-// off[b] = 12 + sum_{j<b} (12 + csize_j), b = 0..n (off[n]: where the end mark goes); one wave, 64 blocks per step with a 64-bit
-// carry.  A result outside [1, src_len] cannot come from the container encode; it is counted (the engine fails the call) and
-// clamped so that the pack and the footer stay inside the bound the engine checked the capacity against.
-// kWriter: one batch of the streaming writer.  `off` is its device index at the batch's first block number; the scan starts from
-// off[0], the running image offset the previous batch left there as its off[n] (12 before the first), and adds its bad results to
-// the running count.
-template <bool kWriter>
-__global__ __launch_bounds__(64)
-void image_enc_scan_kernel(fourmc_block* __restrict__ blocks, uint64_t* __restrict__ off, uint32_t n, fourmc_image_enc_summary* sum)
+// off[b] = start + sum_{j<b} (12 + csize_j), b = 0..n-1, on one wave, 64 blocks per step with a 64-bit carry; returns what off[n]
+// would be (where the end mark goes).  `start` is where the first block header lies: 12 in a single image (native/4mc.c:293).  A
+// result outside [1, src_len] cannot come from the container encode; it is counted in *bad (every lane gets the wave's count; the
+// engine fails the call) and clamped so that the pack and the footer stay inside the bound the engine checked the capacity against.
+__device__ __forceinline__ uint64_t enc_scan(fourmc_block* __restrict__ blocks, uint64_t* __restrict__ off, uint32_t n, uint64_t start,
+                                             uint32_t* bad_out)
 {
     const int lane = threadIdx.x;
-    uint64_t carry = kWriter ? off[0] : 12;
+    uint64_t carry = start;
     uint32_t bad = 0;
     for (uint32_t b0 = 0; b0 < n; b0 += 64) {
         const uint32_t b = b0 + uint32_t(lane);
@@ -120,7 +120,20 @@ void image_enc_scan_kernel(fourmc_block* __restrict__ blocks, uint64_t* __restri
         carry += wave_total(incl);
     }
     for (int o = 32; o; o >>= 1) bad += uint32_t(__shfl_xor(int(bad), o));
-    if (lane == 0) {
+    *bad_out = bad;
+    return carry;
+}
+// A single image: the scan from 12, off[n] and the summary.
+// kWriter: one batch of the streaming writer.  `off` is its device index at the batch's first block number; the scan starts from
+// off[0], the running image offset the previous batch left there as its off[n] (12 before the first), and adds its bad results to
+// the running count.
+template <bool kWriter>
+__global__ __launch_bounds__(64)
+void image_enc_scan_kernel(fourmc_block* __restrict__ blocks, uint64_t* __restrict__ off, uint32_t n, fourmc_image_enc_summary* sum)
+{
+    uint32_t bad = 0;
+    const uint64_t carry = enc_scan(blocks, off, n, kWriter ? off[0] : 12, &bad);
+    if (threadIdx.x == 0) {
         off[n] = carry;
         if (kWriter) {
             sum->bad_blocks += bad;
@@ -131,12 +144,13 @@ void image_enc_scan_kernel(fourmc_block* __restrict__ blocks, uint64_t* __restri
     }
 }
 
-// file header at 0, end mark at off[n], footer behind it (framing.c: fourmc_frame_header / fourmc_frame_footer)
-__global__ __launch_bounds__(256)
-void image_enc_tail_kernel(uint8_t* __restrict__ image, const uint64_t* __restrict__ off, uint32_t n, uint32_t magic)
+// file header at 0 of `image`, end mark at `end`, footer behind it (framing.c: fourmc_frame_header / fourmc_frame_footer), on one
+// workgroup of 256.  off[0, n): the block headers' offsets, counted from `base` bytes in front of the image (0: in-image offsets);
+// end: the in-image offset of the end mark.  Only differences of off[] and off[0] - base (the 12 of the first header) are written.
+__device__ __forceinline__ void enc_tail(uint8_t* __restrict__ image, const uint64_t* __restrict__ off, uint32_t n, uint64_t end,
+                                         uint64_t base, uint32_t magic)
 {
     const uint32_t t = threadIdx.x;
-    const uint64_t end = off[n];
     uint8_t* foot = image + end + 12;
     const uint32_t fsz = 20u + 4u * n;
     if (t == 0) {
@@ -145,14 +159,54 @@ void image_enc_tail_kernel(uint8_t* __restrict__ image, const uint64_t* __restri
         put_be32(foot + 8 + 4 * n, fsz); put_be32(foot + 12 + 4 * n, magic);
     }
     if (t < 12) image[end + t] = 0;
-    for (uint32_t i = t; i < n; i += 256)                 // delta to the previous block; the first one absolute
-        put_be32(foot + 8 + 4 * i, uint32_t(i ? off[i] - off[i - 1] : off[0]));
+    for (uint32_t i = t; i < n; i += 256)                 // delta to the previous block; the first one absolute in the image
+        put_be32(foot + 8 + 4 * i, uint32_t(i ? off[i] - off[i - 1] : off[0] - base));
     __threadfence();
     __syncthreads();
     if (t == 0) {
         put_be32(image + 8, xxh32_lane(image, 8, 0));
         put_be32(foot + fsz - 4, xxh32_lane(foot, fsz - 4, 0));
     }
+}
+__global__ __launch_bounds__(256)
+void image_enc_tail_kernel(uint8_t* __restrict__ image, const uint64_t* __restrict__ off, uint32_t n, uint32_t magic)
+{ enc_tail(image, off, n, off[n], 0, magic); }
+
+// ---- many images (fourmc_gpu_images_compress): the three steps above for n images at once.  ONE descriptor table, with offsets
+// relative to the common source and to one staging, describes every block of every image, so one container encode serves them all;
+// the dense offset table holds offsets absolute in d_images, so one pack does too.
+// Descriptors, one wave per image over its slice (the engine's argument loop has computed the slices: fourmc_image_enc_plan).
+__global__ __launch_bounds__(64)
+void images_enc_desc_kernel(const fourmc_image_enc_plan* __restrict__ plans, fourmc_block* __restrict__ blocks)
+{
+    const fourmc_image_enc_plan pl = plans[blockIdx.x];
+    for (uint32_t b0 = 0; b0 < pl.nblocks; b0 += 64)
+        enc_desc(blocks + pl.first, pl.src_off, pl.stage_off, pl.src_bytes, pl.nblocks, b0 + threadIdx.x);
+}
+// Scan, one wave per image: its first block header lies at image_off + 12 of d_images.  end[i]: where its end mark goes (absolute);
+// res[i]: its length and its bad results.  An image without blocks has its end mark at 12.
+__global__ __launch_bounds__(64)
+void images_enc_scan_kernel(const fourmc_image_enc_plan* __restrict__ plans, fourmc_block* __restrict__ blocks, uint64_t* __restrict__ off,
+                            uint64_t* __restrict__ end, fourmc_image_enc_result* __restrict__ res)
+{
+    const uint32_t i = blockIdx.x;
+    const fourmc_image_enc_plan pl = plans[i];
+    uint32_t bad = 0;
+    const uint64_t carry = enc_scan(blocks + pl.first, off + pl.first, pl.nblocks, pl.image_off + 12, &bad);
+    if (threadIdx.x == 0) {
+        end[i] = carry;
+        res[i].image_bytes = carry - pl.image_off + 12 + 20 + 4ull * pl.nblocks;
+        res[i].bad_blocks = bad;
+    }
+}
+// Tail, one workgroup per image: the footer's first delta is the in-image 12, whatever image_off is
+__global__ __launch_bounds__(256)
+void images_enc_tail_kernel(uint8_t* __restrict__ images, const fourmc_image_enc_plan* __restrict__ plans, const uint64_t* __restrict__ off,
+                            const uint64_t* __restrict__ end, uint32_t magic)
+{
+    const uint32_t i = blockIdx.x;
+    const fourmc_image_enc_plan pl = plans[i];
+    enc_tail(images + pl.image_off, off + pl.first, pl.nblocks, end[i] - pl.image_off, pl.image_off, magic);
 }
 
 // ------------------------------------------------------------------------------------------------------------- decode
@@ -1001,6 +1055,26 @@ hipError_t fourmc_launch_image_wr_batch(void* d_image, fourmc_block* d_blocks, u
 hipError_t fourmc_launch_image_wr_tail(void* d_image, const uint64_t* d_off, uint32_t n, uint32_t magic, hipStream_t s)
 {
     hipLaunchKernelGGL(image_enc_tail_kernel, dim3(1), dim3(256), 0, s, static_cast<uint8_t*>(d_image), d_off, n, magic);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_images_enc_desc(const fourmc_image_enc_plan* d_plans, uint32_t n, fourmc_block* d_blocks, uint32_t nblocks,
+                                         hipStream_t s)
+{
+    if (n == 0 || nblocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(images_enc_desc_kernel, dim3(n), dim3(64), 0, s, d_plans, d_blocks);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_images_enc_frame(void* d_images, const fourmc_image_enc_plan* d_plans, uint32_t n, fourmc_block* d_blocks,
+                                          uint32_t nblocks, uint64_t* d_off, uint64_t* d_end, uint32_t magic, const void* d_staging,
+                                          fourmc_image_enc_result* d_res, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(images_enc_scan_kernel, dim3(n), dim3(64), 0, s, d_plans, d_blocks, d_off, d_end, d_res);
+    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = fourmc_launch_pack_image(d_staging, d_images, d_blocks, d_off, nblocks, s)) return e;
+    hipLaunchKernelGGL(images_enc_tail_kernel, dim3(n), dim3(256), 0, s, static_cast<uint8_t*>(d_images), d_plans, d_off, d_end, magic);
     return hipGetLastError();
 }
 

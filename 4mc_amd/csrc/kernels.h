@@ -121,6 +121,28 @@ hipError_t fourmc_launch_images_plan(const fourmc_image_item* d_items, uint32_t 
                                      uint64_t* d_first, fourmc_images_summary* d_sum, fourmc_image_status* d_status, hipStream_t s);
 hipError_t fourmc_launch_images_reduce(const fourmc_image_item* d_items, uint32_t n, const fourmc_image_parse* d_ps,
                                        const uint64_t* d_first, const fourmc_block* d_desc, fourmc_image_status* d_status, hipStream_t s);
+/* many images in one call, the encode (fourmc_gpu_images_compress).  The sizes are known on the host, so its argument loop computes
+ * each image's slice of the tables and sends it up with the item: block b of image i is descriptor first + b, its source
+ * src_off + b * 4 MiB of d_src and its staging slot stage_off + b * 4 MiB (only an image's last block is short: slots abut). */
+typedef struct fourmc_image_enc_plan {  /* 40 bytes */
+    uint64_t src_off, src_bytes;        /* the item's source */
+    uint64_t image_off;                 /* where its image starts in d_images */
+    uint64_t stage_off;                 /* the staging slot of its first block */
+    uint32_t first, nblocks;            /* its descriptors, and its entries of the dense offset table */
+} fourmc_image_enc_plan;
+typedef struct fourmc_image_enc_result {
+    uint64_t image_bytes;
+    uint64_t bad_blocks;                /* encoder results outside [1, src_len] in this image: the engine folds them */
+} fourmc_image_enc_result;
+/* the descriptors of all nblocks blocks (offsets relative to d_src and to the staging); no launch without blocks */
+hipError_t fourmc_launch_images_enc_desc(const fourmc_image_enc_plan* d_plans, uint32_t n, fourmc_block* d_blocks, uint32_t nblocks,
+                                         hipStream_t s);
+/* after the container encode: per image the scan from image_off + 12 into d_off (dense, nblocks entries, absolute in d_images),
+ * its end mark's offset into d_end[i] and its length and bad results into d_res[i]; ONE pack over all blocks; per image the
+ * header, end mark and footer */
+hipError_t fourmc_launch_images_enc_frame(void* d_images, const fourmc_image_enc_plan* d_plans, uint32_t n, fourmc_block* d_blocks,
+                                          uint32_t nblocks, uint64_t* d_off, uint64_t* d_end, uint32_t magic, const void* d_staging,
+                                          fourmc_image_enc_result* d_res, hipStream_t s);
 /* random access (image.hip, second half): the index summary plus where the last block must end (read_index's data_end) */
 typedef struct fourmc_image_index_dev {
     fourmc_image_index_info info;

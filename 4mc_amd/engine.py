@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .binding import (BLOCK_DTYPE, CODEC_LZ4_FAST, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageIndexInfo, ImageItem, ImageLines,
+from .binding import (BLOCK_DTYPE, CODEC_LZ4_FAST, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines,
                       ImageRange, ImageRecords, ImageSlice, ImageStatus, check, lib)
 
 
@@ -122,6 +122,27 @@ def compress_image(d_src, d_image, magic=MAGIC_4MC, level=1, stream=None):
     check(lib().fourmc_gpu_image_compress(_dev_ptr(d_src, "compress_image d_src"), d_src.numel(), _dev_ptr(d_image, "compress_image d_image"),
                                           d_image.numel(), C.byref(out), magic, level, _stream_ptr(stream)), "fourmc_gpu_image_compress")
     return int(out.value)
+
+
+def compress_images(d_src, items, d_images, magic=MAGIC_4MC, level=1, src_bytes=None, images_bytes=None, stream=None):
+    """Encode many sources of one buffer into many file images of one buffer with one call (fourmc_gpu_images_compress).  `items` is
+    a sequence of (src_off, src_bytes, image_off, image_cap): input i is d_src[src_off:src_off + src_bytes] and its image goes to
+    d_images[image_off:image_off + image_cap], image_cap >= image_bound(src_bytes).  src_bytes / images_bytes: how much of the two
+    tensors the items may name (default: all of each).  Returns the list of image lengths, each what compress_image returns for
+    that source alone, with the same bytes."""
+    src = _dev_ptr(d_src, "compress_images d_src")
+    dst = _dev_ptr(d_images, "compress_images d_images")
+    total = d_src.numel() if src_bytes is None else int(src_bytes)
+    cap = d_images.numel() if images_bytes is None else int(images_bytes)
+    if total > d_src.numel() or cap > d_images.numel():
+        raise EngineError("compress_images: %s beyond the tensor" % ("src_bytes" if total > d_src.numel() else "images_bytes"))
+    q = [tuple(int(v) for v in it) for it in items]
+    arr = (ImageEncItem * len(q))()
+    for i, (so, sb, io, ic) in enumerate(q):
+        arr[i].src_off, arr[i].src_bytes, arr[i].image_off, arr[i].image_cap = so, sb, io, ic
+    check(lib().fourmc_gpu_images_compress(src, total, dst, cap, magic, level, C.cast(arr, C.c_void_p), len(q), _stream_ptr(stream)),
+          "fourmc_gpu_images_compress")
+    return [int(arr[i].image_bytes) for i in range(len(q))]
 
 
 def image_parse_stats():

@@ -141,7 +141,7 @@ int fourmc_gpu_4mc_pack_image(const void* d_staging, void* d_image, const fourmc
 
 /* ---- whole file images in device memory ------------------------------------------------------------------------------------
  * "device image in -> device bytes out", with the result the CLI gives for the same bytes as a file.  The calls synchronize
- * `stream`: the encode once (the image size), the decode twice (the block count its workspace is sized by, then the status),
+ * `stream`: the encode once (the image size; the encode of many images once as well), the decode twice (the block count its workspace is sized by, then the status),
  * the decode of many images twice as well.  No per-block data crosses to the host. */
 /* worst-case image size for src_bytes of input: header + 12 per block + src_bytes + end mark + footer */
 uint64_t fourmc_gpu_image_bound(uint64_t src_bytes);
@@ -151,6 +151,38 @@ uint64_t fourmc_gpu_image_bound(uint64_t src_bytes);
  * *image_bytes (host) = the image's length. */
 int fourmc_gpu_image_compress(const void* d_src, uint64_t src_bytes, void* d_image, uint64_t image_cap,
                               uint64_t* image_bytes, uint32_t magic, int level, void* stream);
+/* Many images with one call: the encode's side of fourmc_gpu_images_decompress below.  A job that writes a directory of part files
+ * of a few blocks each pays, per fourmc_gpu_image_compress, one synchronization and a codec launch that holds a handful of blocks,
+ * and every encoder launch lasts as long as its slowest block.  All sources lie in ONE device buffer and all images go to ONE
+ * device buffer, so a single descriptor table describes every block of every image and one container encode serves them all.
+ * The one rule.  After the call, items[i].image_bytes and d_images[image_off, image_off + image_bytes) equal what the single-image
+ *   compress call above writes for d_src + src_off, src_bytes at the same magic and level: for every level of both formats (the
+ *   level -> codec mapping is the shared one), an empty source (the 44-byte image), sources that are no multiple of 4 MiB, under
+ *   FOURMC_LZ4_ENCODE=parallel / fourmc_gpu_set_lz4_encode_mode(1) (the bytes the single call gives in that mode), and when the
+ *   engine cuts the encode into several launches, wherever a cut falls inside an image.
+ * Writes.  Nothing outside the images: every byte of d_images outside each [image_off, image_off + image_bytes) keeps its value.
+ * Sources.  Two items may name the same or overlapping source bytes.  d_src and d_images must not overlap each other (not checked).
+ * Arguments.  Checked on the host before any device is looked for, the magic first; each of these returns FOURMC_EINVAL with
+ *   `items` untouched: a magic that is neither 4mc nor 4mz; items NULL with n > 0; d_src NULL with a nonzero src_bytes; d_images
+ *   NULL; a source that does not lie inside [0, src_total) or an image region that does not lie inside [0, images_bytes);
+ *   image_cap < fourmc_gpu_image_bound(src_bytes); an item of more than 0x3FFFFFFF blocks; two image regions that overlap (every
+ *   region is at least 44 bytes, so the same region twice is an overlap; regions that touch are fine).  n == 0 returns FOURMC_OK
+ *   and does nothing.  More than 0x7FFFFFFF blocks in all: FOURMC_EUNSUP.  No device: FOURMC_ENODEV.  A block whose encoder result
+ *   falls outside [1, src_len]: FOURMC_EINVAL, the guard image_compress has.  On every failure `items` is left as it came.
+ * Staging.  The engine's image workspace holds the encoded blocks before the pack: block b of an image has a slot of its src_len
+ *   rounded up to 256 bytes, every slot starts 256-byte aligned and the slots abut, so the staging is
+ *   sum over the items of ((src_bytes + 255) & ~255) bytes, plus 4096 bytes of slack behind the last slot - not 4 MiB per block:
+ *   ten thousand part files of a few KiB take their own size, not 40 GB.
+ * Synchronizations of `stream`: one, however many images there are (the lengths and the count of bad encoder results come back
+ *   together).  `items` crosses to the device once.
+ * Not reproduced: .4mc and .4mz in one call, sources or images at unrelated device pointers, a batched streaming writer. */
+typedef struct fourmc_image_enc_item {   /* 40 bytes */
+    uint64_t src_off, src_bytes;         /* in : the input is d_src[src_off, src_off + src_bytes)                 */
+    uint64_t image_off, image_cap;       /* in : its image goes to d_images[image_off, image_off + image_cap)     */
+    uint64_t image_bytes;                /* out: the image's length                                               */
+} fourmc_image_enc_item;
+int fourmc_gpu_images_compress(const void* d_src, uint64_t src_total, void* d_images, uint64_t images_bytes,
+                               uint32_t magic, int level, fourmc_image_enc_item* items /*host*/, uint32_t n, void* stream);
 
 /* ---- streaming writes of one image: append chunks of any size as they arrive --------------------------------------------------
  * Output.  After finish, d_image[0, *image_bytes) is byte-identical to what fourmc_gpu_image_compress writes for the concatenation
@@ -252,7 +284,7 @@ int fourmc_gpu_image_decompress(const void* d_image, uint64_t image_bytes, void*
  *   the single call; the parse statistics below count each image once, under the parser that accepted it.
  * Synchronizations of `stream`: two, however many images there are (the block count the workspace is sized by, then the
  *   statuses); the size query takes one.  `items` crosses to the device once and the statuses come back once.
- * Not reproduced: a batched encode, .4mc and .4mz in one call, images at unrelated device pointers. */
+ * Not reproduced: .4mc and .4mz in one call, images at unrelated device pointers. */
 typedef struct fourmc_image_item {      /* 72 bytes */
     uint64_t image_off, image_bytes;    /* in : the image is d_images[image_off, image_off + image_bytes)           */
     uint64_t dst_off, dst_cap;          /* in : its output region is d_dst[dst_off, dst_off + dst_cap)              */
