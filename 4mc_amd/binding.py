@@ -75,7 +75,13 @@ class ImageLines(C.Structure):         # struct fourmc_image_lines: as ImageReco
     _fields_ = list(ImageRecords._fields_)
 
 
-assert C.sizeof(ImageSlice) == 48 and C.sizeof(ImageRecords) == 40 and C.sizeof(ImageLines) == 40
+# struct fourmc_image_split_item (include/fourmc_gpu.h: the lines of many splits with one call)
+class ImageSplitItem(C.Structure):
+    _fields_ = [("split_start", C.c_uint64), ("split_end", C.c_uint64), ("dst_off", C.c_uint64), ("dst_cap", C.c_uint64),
+                ("table_off", C.c_uint64), ("lines_cap", C.c_uint64), ("out", ImageLines)]
+
+
+assert C.sizeof(ImageSlice) == 48 and C.sizeof(ImageRecords) == 40 and C.sizeof(ImageLines) == 40 and C.sizeof(ImageSplitItem) == 88
 IMAGE_ENTRY_DTYPE = np.dtype([("image_off", "<u8"), ("data_off", "<u8"), ("usize", "<u4"), ("csize", "<u4"),
                               ("xxh32", "<u4"), ("pad", "<u4")])
 assert C.sizeof(ImageEntry) == 32 and C.sizeof(ImageRange) == 32 and C.sizeof(ImageIndexInfo) == 32
@@ -149,6 +155,9 @@ _GPU_API = {
                                                 C.c_uint64, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_read_lines": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
                                               C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_image_read_lines_batch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                    C.c_void_p, C.c_uint32, C.c_void_p]),
+    "fourmc_gpu_image_lines_batch_stats": (None, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_debug_lines_scan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_debug_records_scan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint8, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_writer_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p]),

@@ -1484,6 +1484,259 @@ int fourmc_gpu_image_read_lines(const void* d_image, uint64_t image_bytes, uint6
     return FOURMC_OK;
 }
 
+// groups processed, tail rounds run and container decode calls made by the batch call (fourmc_gpu_image_lines_batch_stats)
+static std::atomic<unsigned long long> g_lb_groups{0}, g_lb_rounds{0}, g_lb_decodes{0};
+void fourmc_gpu_image_lines_batch_stats(unsigned long long* groups, unsigned long long* tail_rounds, unsigned long long* block_decodes)
+{
+    if (groups) *groups = g_lb_groups.load();
+    if (tail_rounds) *tail_rounds = g_lb_rounds.load();
+    if (block_decodes) *block_decodes = g_lb_decodes.load();
+}
+
+// FOURMC_SPLIT_GROUP: the most splits of one group (a staging slot each); read at every call, like FOURMC_IMAGE_PARSE
+static uint32_t split_group()
+{
+    const char* e = getenv("FOURMC_SPLIT_GROUP");
+    if (!e || !*e) return 256;
+    const long v = strtol(e, nullptr, 10);
+    return v < 1 ? 1u : v > 4096 ? 4096u : uint32_t(v);
+}
+
+// image_read_lines for many splits.  The host walks the single call's steps for a group of splits at a time: the plans come back
+// once, each tail round's verdicts once, the states once; everything between is one launch for the whole group.  Workspace
+// (g_img_ws): the index and the entries, then per group the requests, plans, jobs, tails and tail descriptors, and - sized after
+// the rounds, when the spans are known - the spans, their two tables of firsts, the states, the body descriptors and the tile
+// counts.  A buffer that grows there loses the entries: the index kernel runs again.  Staging (g_img_stage): one slot per split
+// of the group that searches.
+int fourmc_gpu_image_read_lines_batch(const void* d_image, uint64_t image_bytes, uint32_t max_line_len, void* d_dst, uint64_t dst_bytes,
+                                      uint64_t* d_starts, uint32_t* d_text_len, uint64_t table_entries,
+                                      fourmc_image_split_item* items, uint32_t n, void* stream)
+{
+    if (n == 0) return FOURMC_OK;
+    if (!items) { snprintf(g_err, sizeof g_err, "image_read_lines_batch: null items"); return FOURMC_EINVAL; }
+    if (!d_image) { snprintf(g_err, sizeof g_err, "image_read_lines_batch: null image"); return FOURMC_EINVAL; }
+    if (!d_dst) { snprintf(g_err, sizeof g_err, "image_read_lines_batch: null destination"); return FOURMC_EINVAL; }
+    if (!d_starts != !d_text_len) { snprintf(g_err, sizeof g_err, "image_read_lines_batch: d_starts and d_text_len go together (both NULL: count only)"); return FOURMC_EINVAL; }
+    if (max_line_len > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "image_read_lines_batch: max_line_len %u above 0x7FFFFFFF", max_line_len); return FOURMC_EINVAL; }
+    {
+        std::vector<std::pair<uint64_t, uint64_t>> d, t;
+        d.reserve(n);
+        if (d_starts) t.reserve(n);
+        for (uint32_t i = 0; i < n; i++) {
+            const fourmc_image_split_item& it = items[i];
+            if (it.dst_off > dst_bytes || it.dst_cap > dst_bytes - it.dst_off) {
+                snprintf(g_err, sizeof g_err, "image_read_lines_batch: the output region of split %u lies beyond the %llu bytes of the destination", i,
+                         (unsigned long long)dst_bytes);
+                return FOURMC_EINVAL;
+            }
+            if (it.dst_cap) d.emplace_back(it.dst_off, it.dst_off + it.dst_cap);
+            if (!d_starts) continue;                          // count only looks at no table
+            if (it.table_off > table_entries || it.lines_cap > table_entries - it.table_off) {
+                snprintf(g_err, sizeof g_err, "image_read_lines_batch: the table region of split %u lies beyond the %llu entries of the tables", i,
+                         (unsigned long long)table_entries);
+                return FOURMC_EINVAL;
+            }
+            if (it.lines_cap) t.emplace_back(it.table_off, it.table_off + it.lines_cap);
+        }
+        std::sort(d.begin(), d.end());
+        for (size_t i = 1; i < d.size(); i++)
+            if (d[i].first < d[i - 1].second) {
+                snprintf(g_err, sizeof g_err, "image_read_lines_batch: output regions overlap at %llu", (unsigned long long)d[i].first);
+                return FOURMC_EINVAL;
+            }
+        std::sort(t.begin(), t.end());
+        for (size_t i = 1; i < t.size(); i++)
+            if (t[i].first < t[i - 1].second) {
+                snprintf(g_err, sizeof g_err, "image_read_lines_batch: table regions overlap at %llu", (unsigned long long)t[i].first);
+                return FOURMC_EINVAL;
+            }
+    }
+    if (int r = ensure_device()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<fourmc_image_lines> res(n);                   // collected on the side: `items` changes only when the call succeeds
+    memset(res.data(), 0, size_t(n) * sizeof(fourmc_image_lines));
+    auto deliver = [&]() { for (uint32_t i = 0; i < n; i++) items[i].out = res[i]; return FOURMC_OK; };
+    WsLease ws(&g_img_ws);
+    fourmc_image_index_dev idx;
+    if (int r = image_index_count(ws, s, d_image, image_bytes, &idx)) return r;
+    const int64_t code = idx.info.nblocks < 0 ? idx.info.nblocks : idx.info.framing;
+    if (code != 0) { for (auto& o : res) o.result = code; return deliver(); }
+    const uint32_t nb = uint32_t(idx.info.nblocks);
+    const uint64_t total = idx.info.total_bytes;
+    const int codec = image_codec(idx);
+    // the groups: at most FOURMC_SPLIT_GROUP splits, and no more tiles than one grid takes (by the bound the counts are sized by)
+    const uint32_t most = split_group();
+    std::vector<uint32_t> cut(1, 0);
+    size_t cnt_most = 0;
+    {
+        uint64_t tiles = 0; uint32_t in = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            const uint64_t t = records_cnt_bytes(std::min(items[i].dst_cap, total)) / sizeof(uint64_t);
+            if (in == most || (in && tiles + t > 0x7FFFFFFFull)) { cut.push_back(i); in = 0; tiles = 0; }
+            in++; tiles += t;
+            cnt_most = std::max(cnt_most, size_t(tiles) * sizeof(uint64_t));
+        }
+        cut.push_back(n);
+    }
+    uint32_t m_most = 0;
+    for (size_t g = 1; g < cut.size(); g++) m_most = std::max(m_most, cut[g] - cut[g - 1]);
+    // the layout: what is fixed for the call, then the group's first phase, then its second
+    const size_t o_ent = kIdxBytes;
+    const size_t o_req = o_ent + align256(size_t(nb) * sizeof(fourmc_image_entry));
+    const size_t o_plan = o_req + align256(size_t(m_most) * sizeof(fourmc_split_req));
+    const size_t o_job = o_plan + align256(size_t(m_most) * sizeof(fourmc_records_plan));
+    const size_t o_tail = o_job + align256(size_t(m_most) * sizeof(fourmc_tail_job));
+    const size_t o_tdesc = o_tail + align256(size_t(m_most) * sizeof(fourmc_records_tail));
+    const size_t o_span = o_tdesc + align256(size_t(m_most) * sizeof(fourmc_block));
+    const size_t o_ft = o_span + align256(size_t(m_most) * sizeof(fourmc_lines_span));
+    const size_t o_fd = o_ft + align256((size_t(m_most) + 1) * sizeof(uint64_t));
+    const size_t o_st = o_fd + align256((size_t(m_most) + 1) * sizeof(uint32_t));
+    const size_t o_cnt = o_st + align256(size_t(m_most) * sizeof(fourmc_records_state));
+    auto o_bdesc = [&](uint64_t tiles) { return o_cnt + align256((size_t(tiles) + 1) * sizeof(uint64_t)); };
+    void* w = nullptr;
+    // the body descriptors of a partition of the image: a block each, and one more per split whose tail block ends with a CR
+    if (int r = ws.get(s, o_bdesc(cnt_most / sizeof(uint64_t)) + (size_t(nb) + m_most) * sizeof(fourmc_block), &w)) return r;
+    char* base = static_cast<char*>(w);
+    HIP_TRY(fourmc_launch_image_index(d_image, image_bytes, reinterpret_cast<fourmc_image_index_dev*>(base),
+                                      reinterpret_cast<fourmc_image_entry*>(base + o_ent), nb, s));
+    WsLease ws2(&g_img_stage);
+    constexpr uint64_t kSlot = uint64_t(FOURMC_BLOCKSIZE) + 64;
+
+    struct Search { bool live, searching, pending; uint32_t b, bt, slot; uint64_t hi; fourmc_records_tail tail; };
+    auto run_group = [&](uint32_t g0, uint32_t m) -> int {
+        g_lb_groups++;
+        auto* d_idx = reinterpret_cast<fourmc_image_index_dev*>(base);
+        auto* d_ent = reinterpret_cast<fourmc_image_entry*>(base + o_ent);
+        auto* d_req = reinterpret_cast<fourmc_split_req*>(base + o_req);
+        auto* d_plan = reinterpret_cast<fourmc_records_plan*>(base + o_plan);
+        auto* d_job = reinterpret_cast<fourmc_tail_job*>(base + o_job);
+        auto* d_tail = reinterpret_cast<fourmc_records_tail*>(base + o_tail);
+        auto* d_tdesc = reinterpret_cast<fourmc_block*>(base + o_tdesc);
+        std::vector<fourmc_split_req> req(m);
+        for (uint32_t i = 0; i < m; i++) { req[i].split_start = items[g0 + i].split_start; req[i].split_end = items[g0 + i].split_end; }
+        std::vector<fourmc_records_plan> plan(m);
+        HIP_TRY(hipMemcpyAsync(d_req, req.data(), size_t(m) * sizeof(fourmc_split_req), hipMemcpyHostToDevice, s));
+        HIP_TRY(fourmc_launch_lines_batch_plan(d_ent, nb, d_idx, d_req, m, d_plan, s));
+        HIP_TRY(hipMemcpyAsync(plan.data(), d_plan, size_t(m) * sizeof(fourmc_records_plan), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        // hi, split by split as the single call finds it; a round stages one block for every split that still searches
+        std::vector<Search> q(m);
+        uint32_t nslots = 0;
+        for (uint32_t i = 0; i < m; i++) {
+            Search& h = q[i];
+            h = Search();
+            if (plan[i].code != 0) { res[g0 + i].result = plan[i].code; continue; }
+            res[g0 + i].base = plan[i].ds;
+            h.live = true; h.hi = plan[i].total; h.bt = nb; h.b = plan[i].b1;
+            h.searching = plan[i].b1 < nb;
+            if (h.searching) h.slot = nslots++;
+        }
+        char* d_stage = nullptr;
+        if (nslots) {
+            void* w2 = nullptr;
+            if (int r = ws2.get(s, size_t(nslots) * kSlot, &w2)) return r;
+            d_stage = static_cast<char*>(w2);
+        }
+        std::vector<fourmc_tail_job> jobs;
+        std::vector<uint32_t> owner;
+        std::vector<fourmc_records_tail> tails;
+        for (;;) {
+            jobs.clear(); owner.clear();
+            for (uint32_t i = 0; i < m; i++)
+                if (q[i].searching) {
+                    fourmc_tail_job j; j.b = q[i].b; j.slot = q[i].slot; j.last_block = q[i].b + 1 == nb; j.pending = q[i].pending;
+                    jobs.push_back(j); owner.push_back(i);
+                }
+            if (jobs.empty()) break;
+            const uint32_t nj = uint32_t(jobs.size());
+            g_lb_rounds++;
+            tails.resize(nj);
+            HIP_TRY(hipMemcpyAsync(d_job, jobs.data(), size_t(nj) * sizeof(fourmc_tail_job), hipMemcpyHostToDevice, s));
+            HIP_TRY(fourmc_launch_lines_batch_tail_desc(d_ent, d_job, nj, kSlot, d_tdesc, s));
+            g_lb_decodes++;
+            if (int r = fourmc_gpu_4mc_decode_blocks(d_image, d_stage, d_tdesc, nj, codec, s)) return r;
+            HIP_TRY(fourmc_launch_lines_batch_tail_find(d_stage, kSlot, d_tdesc, d_ent, d_job, nj, d_tail, s));
+            HIP_TRY(hipMemcpyAsync(tails.data(), d_tail, size_t(nj) * sizeof(fourmc_records_tail), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            for (uint32_t j = 0; j < nj; j++) {
+                Search& h = q[owner[j]];
+                h.tail = tails[j];
+                if (h.tail.code != 0) { res[g0 + owner[j]].result = h.tail.code; h.live = h.searching = false; continue; }
+                if (h.tail.found == 1) { h.bt = h.b; h.hi = h.tail.hi; h.searching = false; continue; }
+                if (h.tail.found == 2) { h.pending = true; h.hi = h.tail.hi; }
+                if (++h.b == nb) h.searching = false;
+            }
+        }
+        // the spans: the splits whose content fits
+        std::vector<fourmc_lines_span> spans;
+        std::vector<uint64_t> first_tile;
+        std::vector<uint32_t> first_desc, span_item;
+        uint64_t tiles = 0, ndesc = 0, longest = 0, longest_copy = 0;
+        for (uint32_t i = 0; i < m; i++) {
+            const Search& h = q[i];
+            if (!h.live) continue;
+            const fourmc_image_split_item& it = items[g0 + i];
+            const uint64_t len = h.hi - plan[i].ds;
+            if (len > it.dst_cap) { res[g0 + i].result = -5; res[g0 + i].data_bytes = len; continue; }
+            fourmc_lines_span sp;
+            memset(&sp, 0, sizeof sp);
+            sp.dst = static_cast<uint8_t*>(d_dst) + it.dst_off; sp.len = len;
+            sp.tile0 = tiles; sp.ntiles = fourmc_records_tiles(sp.dst, len);
+            sp.desc0 = uint32_t(ndesc); sp.ndesc = h.bt - plan[i].b0; sp.b0 = plan[i].b0;
+            sp.first_split = it.split_start == 0; sp.ds = plan[i].ds; sp.body = plan[i].de - plan[i].ds;
+            if (d_starts) { sp.starts = d_starts + it.table_off; sp.tlen = d_text_len + it.table_off; sp.lines_cap = it.lines_cap; }
+            if (h.bt < nb && h.hi > h.tail.data_off) {
+                sp.stage = reinterpret_cast<const uint8_t*>(d_stage) + uint64_t(h.slot) * kSlot;
+                sp.copy_off = h.tail.data_off - plan[i].ds; sp.copy_len = h.hi - h.tail.data_off;
+                longest_copy = std::max(longest_copy, sp.copy_len);
+            }
+            tiles += sp.ntiles; ndesc += sp.ndesc; longest = std::max(longest, len);
+            if (tiles > 0x7FFFFFFFull || ndesc > 0x7FFFFFFFull) {
+                snprintf(g_err, sizeof g_err, "image_read_lines_batch: %llu bytes or %llu blocks in one group", (unsigned long long)tiles * FOURMC_RECORDS_TILE,
+                         (unsigned long long)ndesc);
+                return FOURMC_EUNSUP;
+            }
+            spans.push_back(sp); first_tile.push_back(sp.tile0); first_desc.push_back(sp.desc0); span_item.push_back(g0 + i);
+        }
+        if (spans.empty()) return FOURMC_OK;
+        const uint32_t ns = uint32_t(spans.size());
+        first_tile.push_back(tiles); first_desc.push_back(uint32_t(ndesc));
+        const size_t had = ws.cap();
+        void* wg = nullptr;
+        if (int r = ws.get(s, o_bdesc(tiles) + size_t(ndesc) * sizeof(fourmc_block), &wg)) return r;
+        base = static_cast<char*>(wg);
+        d_ent = reinterpret_cast<fourmc_image_entry*>(base + o_ent);
+        if (ws.cap() != had)                                  // the buffer moved: the entries again
+            HIP_TRY(fourmc_launch_image_index(d_image, image_bytes, reinterpret_cast<fourmc_image_index_dev*>(base), d_ent, nb, s));
+        auto* d_span = reinterpret_cast<fourmc_lines_span*>(base + o_span);
+        auto* d_ft = reinterpret_cast<uint64_t*>(base + o_ft);
+        auto* d_fd = reinterpret_cast<uint32_t*>(base + o_fd);
+        auto* d_st = reinterpret_cast<fourmc_records_state*>(base + o_st);
+        auto* d_cnt = reinterpret_cast<uint64_t*>(base + o_cnt);
+        auto* d_bdesc = reinterpret_cast<fourmc_block*>(base + o_bdesc(tiles));
+        HIP_TRY(hipMemcpyAsync(d_span, spans.data(), size_t(ns) * sizeof(fourmc_lines_span), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_ft, first_tile.data(), (size_t(ns) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_fd, first_desc.data(), (size_t(ns) + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (ndesc) {
+            HIP_TRY(fourmc_launch_lines_batch_body_desc(d_ent, d_span, d_fd, ns, uint32_t(ndesc), d_dst, d_bdesc, s));
+            g_lb_decodes++;
+            if (int r = fourmc_gpu_4mc_decode_blocks(d_image, d_dst, d_bdesc, uint32_t(ndesc), codec, s)) return r;
+        }
+        HIP_TRY(fourmc_launch_lines_batch_copy(d_span, ns, longest_copy, s));
+        HIP_TRY(fourmc_launch_lines_batch_count(d_span, d_ft, ns, d_cnt, tiles, s));
+        HIP_TRY(fourmc_launch_lines_batch_finish(d_span, ns, d_cnt, d_bdesc, d_st, s));
+        if (d_starts) HIP_TRY(fourmc_launch_lines_batch_write(d_span, d_ft, ns, d_cnt, tiles, longest, max_line_len, d_st, s));
+        std::vector<fourmc_records_state> st(ns);
+        HIP_TRY(hipMemcpyAsync(st.data(), d_st, size_t(ns) * sizeof(fourmc_records_state), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (uint32_t k = 0; k < ns; k++) memcpy(&res[span_item[k]], &st[k].r, sizeof(fourmc_image_lines));
+        return FOURMC_OK;
+    };
+    for (size_t g = 1; g < cut.size(); g++)
+        if (int r = run_group(cut[g - 1], cut[g] - cut[g - 1])) return r;
+    return deliver();
+}
+
 #ifdef FOURMC_RESEARCH
 int fourmc_gpu_debug_lines_scan(const void* d, uint64_t len, uint32_t max_line_len, uint64_t* d_starts, uint32_t* d_text_len,
                                 uint64_t lines_cap, int64_t* lines, void* stream)

@@ -293,6 +293,47 @@ hipError_t fourmc_launch_lines_finish(const void* d, uint64_t len, uint64_t* d_c
 /* the starts and each line's terminator length, then the pass that turns d_tlen into text lengths cut at max_line_len */
 hipError_t fourmc_launch_lines_write(const void* d, uint64_t len, uint32_t max_line_len, const uint64_t* d_cnt, uint64_t ntiles,
                                      const fourmc_records_state* d_st, uint64_t* d_starts, uint32_t* d_tlen, hipStream_t s);
+/* Many splits with one call (fourmc_gpu_image_read_lines_batch): the kernels above over a group of splits. */
+typedef struct fourmc_split_req { uint64_t split_start, split_end; } fourmc_split_req;
+/* one split still looking for its hi, for one round: block b goes to staging slot `slot` and is searched there */
+typedef struct fourmc_tail_job { uint32_t b, slot; int32_t last_block, pending; } fourmc_tail_job;
+/* one split whose content fits its region: what the body decode, the prefix copy and the scan need of it */
+typedef struct fourmc_lines_span {
+    uint8_t*  dst;          /* d_dst + dst_off */
+    uint64_t  len;          /* hi - ds */
+    uint64_t  tile0, ntiles;/* its tiles in the group's count table: fourmc_records_tiles(dst, len) of them from tile0 on */
+    uint32_t  desc0, ndesc; /* its body blocks' descriptors in the group's table */
+    uint32_t  b0;           /* the first body block */
+    int32_t   first_split;  /* split_start == 0 */
+    uint64_t  ds, body;     /* decoded offset of dst[0]; de - ds */
+    uint64_t* starts;       /* d_starts + table_off, NULL: count only */
+    uint32_t* tlen;
+    uint64_t  lines_cap;
+    const uint8_t* stage;   /* the split's staging slot */
+    uint64_t  copy_off, copy_len;   /* dst[copy_off, +copy_len) = stage[0, copy_len): the last tail block's prefix (0: none) */
+} fourmc_lines_span;
+hipError_t fourmc_launch_lines_batch_plan(const fourmc_image_entry* d_ent, uint32_t n, const fourmc_image_index_dev* d_idx,
+                                          const fourmc_split_req* d_req, uint32_t m, fourmc_records_plan* d_plan, hipStream_t s);
+/* per round: job j's block to slot * stride of the staging; after the decode, job j's verdict to d_tail[j] */
+hipError_t fourmc_launch_lines_batch_tail_desc(const fourmc_image_entry* d_ent, const fourmc_tail_job* d_job, uint32_t nj,
+                                               uint64_t stride, fourmc_block* d_desc, hipStream_t s);
+hipError_t fourmc_launch_lines_batch_tail_find(const void* d_stage, uint64_t stride, const fourmc_block* d_desc,
+                                               const fourmc_image_entry* d_ent, const fourmc_tail_job* d_job, uint32_t nj,
+                                               fourmc_records_tail* d_tail, hipStream_t s);
+/* d_first_desc[k] = spans[k].desc0 and d_first_tile[k] = spans[k].tile0: the tables a lane or a wave finds its span in.  The body
+ * descriptors' offsets are relative to d_dst. */
+hipError_t fourmc_launch_lines_batch_body_desc(const fourmc_image_entry* d_ent, const fourmc_lines_span* d_spans,
+                                               const uint32_t* d_first_desc, uint32_t ns, uint32_t ndesc, const void* d_dst,
+                                               fourmc_block* d_desc, hipStream_t s);
+hipError_t fourmc_launch_lines_batch_copy(const fourmc_lines_span* d_spans, uint32_t ns, uint64_t longest, hipStream_t s);
+hipError_t fourmc_launch_lines_batch_count(const fourmc_lines_span* d_spans, const uint64_t* d_first_tile, uint32_t ns,
+                                           uint64_t* d_cnt, uint64_t ntiles, hipStream_t s);
+hipError_t fourmc_launch_lines_batch_finish(const fourmc_lines_span* d_spans, uint32_t ns, uint64_t* d_cnt, const fourmc_block* d_desc,
+                                            fourmc_records_state* d_st, hipStream_t s);
+/* the write pass and the length pass; `longest`: the longest span's len */
+hipError_t fourmc_launch_lines_batch_write(const fourmc_lines_span* d_spans, const uint64_t* d_first_tile, uint32_t ns,
+                                           const uint64_t* d_cnt, uint64_t ntiles, uint64_t longest, uint32_t max_line_len,
+                                           const fourmc_records_state* d_st, hipStream_t s);
 #ifdef FOURMC_RESEARCH      /* the research side build exports these two: tools/zstd_timing.py and tools/k7x_prof.py size their read-backs with them */
 #pragma GCC visibility push(default)
 #endif

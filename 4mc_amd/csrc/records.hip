@@ -168,12 +168,10 @@ void image_align_kernel(const fourmc_image_entry* __restrict__ ent, uint32_t n, 
     slices[i] = q;
 }
 
-// one lane: the split's offsets into blocks and decoded offsets
-__global__ __launch_bounds__(64)
-void records_plan_kernel(const fourmc_image_entry* __restrict__ ent, uint32_t n, const fourmc_image_index_dev* __restrict__ idx,
-                         uint64_t split_start, uint64_t split_end, fourmc_records_plan* __restrict__ plan)
+// the split's offsets into blocks and decoded offsets
+__device__ __forceinline__ fourmc_records_plan plan_split(const fourmc_image_entry* __restrict__ ent, uint32_t n,
+                                                          const fourmc_image_index_dev* __restrict__ idx, uint64_t split_start, uint64_t split_end)
 {
-    if (threadIdx.x != 0) return;
     fourmc_records_plan p = {};
     p.total = idx->info.total_bytes;
     p.de = p.total; p.b1 = n;
@@ -187,7 +185,16 @@ void records_plan_kernel(const fourmc_image_entry* __restrict__ ent, uint32_t n,
         if (b < n && ent[b].image_off == split_end && split_end >= split_start) { p.b1 = b; p.de = ent[b].data_off; }
         else p.code = -3;
     }
-    *plan = p;
+    return p;
+}
+
+// one lane
+__global__ __launch_bounds__(64)
+void records_plan_kernel(const fourmc_image_entry* __restrict__ ent, uint32_t n, const fourmc_image_index_dev* __restrict__ idx,
+                         uint64_t split_start, uint64_t split_end, fourmc_records_plan* __restrict__ plan)
+{
+    if (threadIdx.x != 0) return;
+    *plan = plan_split(ent, n, idx, split_start, split_end);
 }
 
 __global__ __launch_bounds__(256)
@@ -383,14 +390,9 @@ __device__ __forceinline__ uint32_t step_ends(const Span& sp, uint64_t c, const 
     return ends16<WITH_T>(v, nx, pv, two);
 }
 
-// one wave per tile: the line ends of its 16 KiB
-__global__ __launch_bounds__(64 * kWaves)
-void lines_count_kernel(const uint8_t* __restrict__ d, uint64_t len, uint64_t* __restrict__ cnt, uint64_t ntiles)
+// one wave over one tile: the line ends of its 16 KiB, in every lane
+__device__ __forceinline__ uint32_t lines_count_tile(const Span& sp, uint64_t tile, uint32_t lane)
 {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t tile = uint64_t(blockIdx.x) * kWaves + (threadIdx.x >> 6);
-    if (tile >= ntiles) return;
-    const Span sp(d, len);
     const uint64_t c0 = tile * kTileChunks + lane;
     uint32_t k = 0, two;
     if (sp.inner(tile)) {
@@ -404,6 +406,18 @@ void lines_count_kernel(const uint8_t* __restrict__ d, uint64_t len, uint64_t* _
         for (uint32_t i = 0; i < kSteps; i++) k += __popc(step_ends<false>(sp, c0 + 64 * i, clean_chunk(sp, c0 + 64 * i), lane, two));
     }
     for (int o = 32; o; o >>= 1) k += uint32_t(__shfl_xor(int(k), o));
+    return k;
+}
+
+// one wave per tile
+__global__ __launch_bounds__(64 * kWaves)
+void lines_count_kernel(const uint8_t* __restrict__ d, uint64_t len, uint64_t* __restrict__ cnt, uint64_t ntiles)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t tile = uint64_t(blockIdx.x) * kWaves + (threadIdx.x >> 6);
+    if (tile >= ntiles) return;
+    const Span sp(d, len);
+    const uint32_t k = lines_count_tile(sp, tile, lane);
     if (lane == 0) cnt[tile] = k;
 }
 
@@ -416,17 +430,10 @@ void lines_finish_kernel(const uint8_t* __restrict__ d, uint64_t len, uint64_t* 
 // The count kernel's walk.  Line end number r of d closes line shift + r - 1 and opens line shift + r: the start behind it goes
 // to starts[shift + r] and its terminator's length (2 for the LF of a CR LF, else 1) to tlen[shift + r - 1]; the end a split that
 // does not start the file drops (shift 0, r 0) closes a line the split does not own.
-__global__ __launch_bounds__(64 * kWaves)
-void lines_write_kernel(const uint8_t* __restrict__ d, uint64_t len, const uint64_t* __restrict__ base, uint64_t ntiles,
-                        const fourmc_records_state* __restrict__ st, uint64_t* __restrict__ starts, uint32_t* __restrict__ tlen)
+__device__ __forceinline__ void lines_write_tile(const Span& sp, uint64_t tile, uint32_t lane, uint64_t run,
+                                                 uint64_t* __restrict__ starts, uint32_t* __restrict__ tlen)
 {
-    if (!st->write) return;
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t tile = uint64_t(blockIdx.x) * kWaves + (threadIdx.x >> 6);
-    if (tile >= ntiles) return;
-    const Span sp(d, len);
     const uint64_t c0 = tile * kTileChunks + lane;
-    uint64_t run = base[tile] + st->shift;
     const bool inner = sp.inner(tile);
     for (uint32_t i0 = 0; i0 < kSteps; i0 += 4) {
         uint32_t m[4], two[4];
@@ -455,11 +462,22 @@ void lines_write_kernel(const uint8_t* __restrict__ d, uint64_t len, const uint6
     }
 }
 
+__global__ __launch_bounds__(64 * kWaves)
+void lines_write_kernel(const uint8_t* __restrict__ d, uint64_t len, const uint64_t* __restrict__ base, uint64_t ntiles,
+                        const fourmc_records_state* __restrict__ st, uint64_t* __restrict__ starts, uint32_t* __restrict__ tlen)
+{
+    if (!st->write) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t tile = uint64_t(blockIdx.x) * kWaves + (threadIdx.x >> 6);
+    if (tile >= ntiles) return;
+    const Span sp(d, len);
+    lines_write_tile(sp, tile, lane, base[tile] + st->shift, starts, tlen);
+}
+
 // tlen[i], the terminator's length of line i, into the length of its text, cut at max_len.  The line count is on the device
 // only, so a fixed grid strides over it.
-__global__ __launch_bounds__(256)
-void lines_len_kernel(const fourmc_records_state* __restrict__ st, const uint64_t* __restrict__ starts, uint32_t* __restrict__ tlen,
-                      uint32_t max_len)
+__device__ __forceinline__ void lines_len_body(const fourmc_records_state* __restrict__ st, const uint64_t* __restrict__ starts,
+                                               uint32_t* __restrict__ tlen, uint32_t max_len)
 {
     if (!st->write) return;
     const uint64_t n = uint64_t(st->r.result), step = uint64_t(gridDim.x) * 256;
@@ -469,14 +487,19 @@ void lines_len_kernel(const fourmc_records_state* __restrict__ st, const uint64_
     }
 }
 
+__global__ __launch_bounds__(256)
+void lines_len_kernel(const fourmc_records_state* __restrict__ st, const uint64_t* __restrict__ starts, uint32_t* __restrict__ tlen,
+                      uint32_t max_len)
+{ lines_len_body(st, starts, tlen, max_len); }
+
 // records_tail_find_kernel by lines: the first line end of a staged block.  A CR in the block's last byte ends a line only if
 // the next block does not open with LF, which this block cannot say unless it is the last (found = 2, hi behind the block).
 // `pending`: the block BEHIND such a CR; its first byte decides (hi behind the LF, or still behind the CR), an empty block
-// leaves the question open.
-__global__ __launch_bounds__(1024)
-void lines_tail_find_kernel(const uint8_t* __restrict__ stage, const fourmc_block* __restrict__ desc,
-                            const fourmc_image_entry* __restrict__ ent, uint32_t b, int last_block, int pending,
-                            fourmc_records_tail* __restrict__ out)
+// leaves the question open.  One workgroup of 1024.
+__device__ __forceinline__
+void lines_tail_find_body(const uint8_t* __restrict__ stage, const fourmc_block* __restrict__ desc,
+                          const fourmc_image_entry* __restrict__ ent, uint32_t b, int last_block, int pending,
+                          fourmc_records_tail* __restrict__ out)
 {
     __shared__ uint32_t first;
     const fourmc_block d = *desc;
@@ -512,6 +535,144 @@ void lines_tail_find_kernel(const uint8_t* __restrict__ stage, const fourmc_bloc
         }
         *out = r;
     }
+}
+
+__global__ __launch_bounds__(1024)
+void lines_tail_find_kernel(const uint8_t* __restrict__ stage, const fourmc_block* __restrict__ desc,
+                            const fourmc_image_entry* __restrict__ ent, uint32_t b, int last_block, int pending,
+                            fourmc_records_tail* __restrict__ out)
+{ lines_tail_find_body(stage, desc, ent, b, last_block, pending, out); }
+
+// ------------------------------------------------------------------------------------- many splits with one call, by lines
+// fourmc_gpu_image_read_lines_batch: the kernels above with one more index.  A group of splits is a table of spans (kernels.h:
+// fourmc_lines_span), each with its own destination, tables, descriptors and state; the tiles of all spans are numbered through,
+// first[k] being span k's first tile, and a wave finds its span by a binary search over `first`.  Inside its span a wave is the
+// single call's wave: the same Span, the same walk, the same seam loads, so a span's bytes are cut as the single call cuts them
+// whatever lies in front of and behind its region.
+template <class T>
+__device__ __forceinline__ uint32_t span_of(const T* __restrict__ first, uint32_t ns, T key)     // the last k with first[k] <= key
+{
+    uint32_t lo = 0, hi = ns;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (first[mid] <= key) lo = mid + 1; else hi = mid;
+    }
+    return uint32_t(__builtin_amdgcn_readfirstlane(int(lo - 1)));
+}
+
+// one lane per split
+__global__ __launch_bounds__(256)
+void lines_batch_plan_kernel(const fourmc_image_entry* __restrict__ ent, uint32_t n, const fourmc_image_index_dev* __restrict__ idx,
+                             const fourmc_split_req* __restrict__ req, uint32_t m, fourmc_records_plan* __restrict__ plan)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < m) plan[i] = plan_split(ent, n, idx, req[i].split_start, req[i].split_end);
+}
+
+// one lane per searching split: its next tail block into its staging slot
+__global__ __launch_bounds__(256)
+void lines_batch_tail_desc_kernel(const fourmc_image_entry* __restrict__ ent, const fourmc_tail_job* __restrict__ job, uint32_t nj,
+                                  uint64_t stride, fourmc_block* __restrict__ desc)
+{
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= nj) return;
+    const fourmc_image_entry e = ent[job[j].b];
+    fourmc_block d;
+    d.src_off = e.image_off + 12; d.dst_off = uint64_t(job[j].slot) * stride; d.src_len = e.csize; d.dst_cap = e.usize; d.result = 0; d.xxh32 = e.xxh32;
+    desc[j] = d;
+}
+
+// one workgroup per searching split, over that split's slot
+__global__ __launch_bounds__(1024)
+void lines_batch_tail_find_kernel(const uint8_t* __restrict__ stage, uint64_t stride, const fourmc_block* __restrict__ desc,
+                                  const fourmc_image_entry* __restrict__ ent, const fourmc_tail_job* __restrict__ job,
+                                  fourmc_records_tail* __restrict__ out)
+{
+    const fourmc_tail_job q = job[blockIdx.x];
+    lines_tail_find_body(stage + uint64_t(q.slot) * stride, desc + blockIdx.x, ent, q.b, q.last_block, q.pending, out + blockIdx.x);
+}
+
+// one lane per body block of the group: block b0 + i of its span, at its decoded offset in the span's region
+__global__ __launch_bounds__(256)
+void lines_batch_body_desc_kernel(const fourmc_image_entry* __restrict__ ent, const fourmc_lines_span* __restrict__ spans,
+                                  const uint32_t* __restrict__ first, uint32_t ns, uint32_t ndesc, const uint8_t* __restrict__ d_dst,
+                                  fourmc_block* __restrict__ desc)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= ndesc) return;
+    uint32_t lo = 0, hi = ns;
+    while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (first[mid] <= i) lo = mid + 1; else hi = mid; }
+    const fourmc_lines_span& sp = spans[lo - 1];
+    const fourmc_image_entry e = ent[sp.b0 + (i - sp.desc0)];
+    fourmc_block d;
+    d.src_off = e.image_off + 12; d.dst_off = uint64_t(sp.dst - d_dst) + (e.data_off - sp.ds); d.src_len = e.csize; d.dst_cap = e.usize;
+    d.result = 0; d.xxh32 = e.xxh32;
+    desc[i] = d;
+}
+
+// blockIdx.y: the span; its staged prefix to where it belongs.  The slot is 16-byte aligned: whole chunks when the destination is too.
+__global__ __launch_bounds__(256)
+void lines_batch_copy_kernel(const fourmc_lines_span* __restrict__ spans)
+{
+    const fourmc_lines_span& sp = spans[blockIdx.y];
+    const uint64_t n = sp.copy_len;
+    if (!n) return;
+    const uint8_t* __restrict__ src = sp.stage;
+    uint8_t* __restrict__ dst = sp.dst + sp.copy_off;
+    const uint64_t t = uint64_t(blockIdx.x) * 256 + threadIdx.x, step = uint64_t(gridDim.x) * 256;
+    uint64_t done = 0;
+    if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+        const uint64_t nv = n / 16;
+        for (uint64_t i = t; i < nv; i += step) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
+        done = nv * 16;
+    }
+    for (uint64_t i = done + t; i < n; i += step) dst[i] = src[i];
+}
+
+// one wave per tile of the group
+__global__ __launch_bounds__(64 * kWaves)
+void lines_batch_count_kernel(const fourmc_lines_span* __restrict__ spans, const uint64_t* __restrict__ first, uint32_t ns,
+                              uint64_t* __restrict__ cnt, uint64_t ntiles)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t tile = uint64_t(blockIdx.x) * kWaves + (threadIdx.x >> 6);
+    if (tile >= ntiles) return;
+    const fourmc_lines_span& s = spans[span_of(first, ns, tile)];
+    const Span sp(s.dst, s.len);
+    const uint32_t k = lines_count_tile(sp, tile - s.tile0, lane);
+    if (lane == 0) cnt[tile] = k;
+}
+
+// one workgroup per span: its counts into their prefix, its verdict, its state
+__global__ __launch_bounds__(1024)
+void lines_batch_finish_kernel(const fourmc_lines_span* __restrict__ spans, uint64_t* __restrict__ cnt,
+                               const fourmc_block* __restrict__ desc, fourmc_records_state* __restrict__ st)
+{
+    const fourmc_lines_span& s = spans[blockIdx.x];
+    finish_body<true>(s.dst, s.len, 0, cnt + s.tile0, s.ntiles, desc + s.desc0, s.ndesc, s.first_split, s.ds, s.body, s.starts,
+                      s.lines_cap, s.tlen, st + blockIdx.x);
+}
+
+__global__ __launch_bounds__(64 * kWaves)
+void lines_batch_write_kernel(const fourmc_lines_span* __restrict__ spans, const uint64_t* __restrict__ first, uint32_t ns,
+                              const uint64_t* __restrict__ cnt, uint64_t ntiles, const fourmc_records_state* __restrict__ st)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t tile = uint64_t(blockIdx.x) * kWaves + (threadIdx.x >> 6);
+    if (tile >= ntiles) return;
+    const uint32_t k = span_of(first, ns, tile);
+    if (!st[k].write) return;
+    const fourmc_lines_span& s = spans[k];
+    const Span sp(s.dst, s.len);
+    lines_write_tile(sp, tile - s.tile0, lane, cnt[tile] + st[k].shift, s.starts, s.tlen);
+}
+
+// blockIdx.y: the span
+__global__ __launch_bounds__(256)
+void lines_batch_len_kernel(const fourmc_lines_span* __restrict__ spans, const fourmc_records_state* __restrict__ st, uint32_t max_len)
+{
+    const fourmc_lines_span& s = spans[blockIdx.y];
+    lines_len_body(st + blockIdx.y, s.starts, s.tlen, max_len);
 }
 
 } // namespace
@@ -618,6 +779,83 @@ hipError_t fourmc_launch_lines_write(const void* d, uint64_t len, uint32_t max_l
     // one thread per line up to 2048 workgroups (a line of text per ~100 bytes: the grid is full from ~50 MB on), strides above
     const uint64_t most = len / 256 + 1;
     hipLaunchKernelGGL(lines_len_kernel, dim3(uint32_t(most < 2048 ? most : 2048)), dim3(256), 0, s, d_st, d_starts, d_tlen, max_line_len);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_lines_batch_plan(const fourmc_image_entry* d_ent, uint32_t n, const fourmc_image_index_dev* d_idx,
+                                          const fourmc_split_req* d_req, uint32_t m, fourmc_records_plan* d_plan, hipStream_t s)
+{
+    if (!m) return hipSuccess;
+    hipLaunchKernelGGL(lines_batch_plan_kernel, dim3((m + 255) / 256), dim3(256), 0, s, d_ent, n, d_idx, d_req, m, d_plan);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_lines_batch_tail_desc(const fourmc_image_entry* d_ent, const fourmc_tail_job* d_job, uint32_t nj,
+                                               uint64_t stride, fourmc_block* d_desc, hipStream_t s)
+{
+    if (!nj) return hipSuccess;
+    hipLaunchKernelGGL(lines_batch_tail_desc_kernel, dim3((nj + 255) / 256), dim3(256), 0, s, d_ent, d_job, nj, stride, d_desc);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_lines_batch_tail_find(const void* d_stage, uint64_t stride, const fourmc_block* d_desc,
+                                               const fourmc_image_entry* d_ent, const fourmc_tail_job* d_job, uint32_t nj,
+                                               fourmc_records_tail* d_tail, hipStream_t s)
+{
+    if (!nj) return hipSuccess;
+    hipLaunchKernelGGL(lines_batch_tail_find_kernel, dim3(nj), dim3(1024), 0, s, static_cast<const uint8_t*>(d_stage), stride, d_desc,
+                       d_ent, d_job, d_tail);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_lines_batch_body_desc(const fourmc_image_entry* d_ent, const fourmc_lines_span* d_spans,
+                                               const uint32_t* d_first_desc, uint32_t ns, uint32_t ndesc, const void* d_dst,
+                                               fourmc_block* d_desc, hipStream_t s)
+{
+    if (!ndesc) return hipSuccess;
+    hipLaunchKernelGGL(lines_batch_body_desc_kernel, dim3((ndesc + 255) / 256), dim3(256), 0, s, d_ent, d_spans, d_first_desc, ns, ndesc,
+                       static_cast<const uint8_t*>(d_dst), d_desc);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_lines_batch_copy(const fourmc_lines_span* d_spans, uint32_t ns, uint64_t longest, hipStream_t s)
+{
+    if (!ns || !longest) return hipSuccess;
+    const uint64_t most = (longest + 4095) / 4096;                 // 16 bytes per thread
+    hipLaunchKernelGGL(lines_batch_copy_kernel, dim3(uint32_t(most < 64 ? most : 64), ns), dim3(256), 0, s, d_spans);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_lines_batch_count(const fourmc_lines_span* d_spans, const uint64_t* d_first_tile, uint32_t ns,
+                                           uint64_t* d_cnt, uint64_t ntiles, hipStream_t s)
+{
+    if (!ntiles) return hipSuccess;
+    hipLaunchKernelGGL(lines_batch_count_kernel, dim3(uint32_t((ntiles + kWaves - 1) / kWaves)), dim3(64 * kWaves), 0, s, d_spans,
+                       d_first_tile, ns, d_cnt, ntiles);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_lines_batch_finish(const fourmc_lines_span* d_spans, uint32_t ns, uint64_t* d_cnt, const fourmc_block* d_desc,
+                                            fourmc_records_state* d_st, hipStream_t s)
+{
+    if (!ns) return hipSuccess;
+    hipLaunchKernelGGL(lines_batch_finish_kernel, dim3(ns), dim3(1024), 0, s, d_spans, d_cnt, d_desc, d_st);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_lines_batch_write(const fourmc_lines_span* d_spans, const uint64_t* d_first_tile, uint32_t ns,
+                                           const uint64_t* d_cnt, uint64_t ntiles, uint64_t longest, uint32_t max_line_len,
+                                           const fourmc_records_state* d_st, hipStream_t s)
+{
+    if (!ns) return hipSuccess;
+    if (ntiles) {
+        hipLaunchKernelGGL(lines_batch_write_kernel, dim3(uint32_t((ntiles + kWaves - 1) / kWaves)), dim3(64 * kWaves), 0, s, d_spans,
+                           d_first_tile, ns, d_cnt, ntiles, d_st);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    // per span one thread per line at a line of text per ~32 bytes, up to 256 workgroups; strides above
+    const uint64_t most = longest / 8192 + 1;
+    hipLaunchKernelGGL(lines_batch_len_kernel, dim3(uint32_t(most < 256 ? most : 256), ns), dim3(256), 0, s, d_spans, d_st, max_line_len);
     return hipGetLastError();
 }
 

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .binding import (BLOCK_DTYPE, CODEC_LZ4_FAST, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines,
+from .binding import (BLOCK_DTYPE, CODEC_LZ4_FAST, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines, ImageSplitItem,
                       ImageRange, ImageRecords, ImageSlice, ImageStatus, check, lib)
 
 
@@ -305,6 +305,50 @@ def image_read_lines(d_image, split_start, split_end, d_dst, starts=None, text_l
     check(lib().fourmc_gpu_image_read_lines(ptr, n, int(split_start), int(split_end), int(max_line_len), dst, d_dst.numel(), sp, tp, cap,
                                             C.byref(out), _stream_ptr(stream)), "fourmc_gpu_image_read_lines")
     return out
+
+
+_SPLIT_KEYS = ("split_start", "split_end", "dst_off", "dst_cap", "table_off", "lines_cap")
+
+
+def image_read_lines_batch(d_image, splits, d_dst, starts=None, text_len=None, max_line_len=0x7FFFFFFF, image_bytes=None, stream=None):
+    """image_read_lines for many splits of one image with one call (fourmc_gpu_image_read_lines_batch).  `splits` is a sequence of
+    (split_start, split_end, dst_off, dst_cap, table_off, lines_cap) tuples, or of dicts with those keys (table_off and lines_cap
+    default to 0): split i's content goes to d_dst[dst_off:dst_off + dst_cap] and its tables are starts[table_off:table_off +
+    lines_cap] and text_len[table_off:table_off + lines_cap], the starts being offsets in the split's own region.  Both tables or
+    neither (count only).  Returns one dict per split with the fields of ImageLines (result, base, data_off, data_bytes, reserved),
+    each what image_read_lines returns for that split with those regions."""
+    ptr = _dev_ptr(d_image, "image_read_lines_batch d_image")
+    dst = _dev_ptr(d_dst, "image_read_lines_batch d_dst")
+    n = _image_len(d_image, image_bytes, "image_read_lines_batch")
+    if (starts is None) != (text_len is None):
+        raise EngineError("image_read_lines_batch: starts and text_len go together (both None: count only)")
+    if not 0 <= int(max_line_len) <= 0x7FFFFFFF:
+        raise EngineError("image_read_lines_batch max_line_len: 0 .. 0x7FFFFFFF")
+    sp, tp, entries = 0, 0, 0
+    if starts is not None:
+        if not (isinstance(starts, torch.Tensor) and starts.is_cuda and starts.is_contiguous() and starts.dtype == torch.int64):
+            raise EngineError("image_read_lines_batch starts: a contiguous int64 CUDA tensor is required")
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if not (isinstance(text_len, torch.Tensor) and text_len.is_cuda and text_len.is_contiguous() and text_len.dtype in words):
+            raise EngineError("image_read_lines_batch text_len: a contiguous int32 or uint32 CUDA tensor is required")
+        # a split's region of text_len is read and written one entry short of its lines_cap, as in image_read_lines
+        sp, tp, entries = int(starts.data_ptr()), int(text_len.data_ptr()), min(starts.numel(), text_len.numel() + 1)
+    rows = [tuple(int(q.get(k, 0)) for k in _SPLIT_KEYS) if isinstance(q, dict) else tuple(int(v) for v in q) for q in splits]
+    arr = (ImageSplitItem * len(rows))()
+    for i, row in enumerate(rows):
+        if len(row) != 6:
+            raise EngineError("image_read_lines_batch splits: (split_start, split_end, dst_off, dst_cap, table_off, lines_cap) each")
+        (arr[i].split_start, arr[i].split_end, arr[i].dst_off, arr[i].dst_cap, arr[i].table_off, arr[i].lines_cap) = row
+    check(lib().fourmc_gpu_image_read_lines_batch(ptr, n, int(max_line_len), dst, d_dst.numel(), sp, tp, entries, C.cast(arr, C.c_void_p),
+                                                  len(rows), _stream_ptr(stream)), "fourmc_gpu_image_read_lines_batch")
+    return [{name: int(getattr(arr[i].out, name)) for name, _ in ImageLines._fields_} for i in range(len(rows))]
+
+
+def image_lines_batch_stats():
+    """(groups, tail_rounds, block_decodes) image_read_lines_batch has processed, run and made so far in this process."""
+    g, r, d = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
+    lib().fourmc_gpu_image_lines_batch_stats(C.byref(g), C.byref(r), C.byref(d))
+    return int(g.value), int(r.value), int(d.value)
 
 
 class ImageWriter:

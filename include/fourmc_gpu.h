@@ -465,13 +465,66 @@ int fourmc_gpu_image_read_records(const void* d_image, uint64_t image_bytes, uin
  * above is the contract, and every line has exactly one owner.
  * Not reproduced: the reference's IOException("Too many bytes before newline") for a line of 2 GiB or more; the key (the raw file
  * position after the last block read); multi-byte delimiters (textinputformat.record.delimiter, which the reference never reads);
- * batching of splits; multi-stream images (the index code). */
+ * multi-stream images (the index code). */
 typedef struct fourmc_image_lines { int64_t result; uint64_t base, data_off, data_bytes, reserved; } fourmc_image_lines; /* as fourmc_image_records */
 int fourmc_gpu_image_read_lines(const void* d_image, uint64_t image_bytes, uint64_t split_start, uint64_t split_end,
                                 uint32_t max_line_len,               /* Hadoop's default: 0x7FFFFFFF; larger: FOURMC_EINVAL; 0: every text empty */
                                 void* d_dst, uint64_t dst_cap,
                                 uint64_t* d_starts, uint32_t* d_text_len, uint64_t lines_cap,
                                 fourmc_image_lines* out /*host*/, void* stream);
+/* The lines of many splits of ONE image with one call: a job that holds an image in HBM wants the lines of every split of it, or of
+ * the splits one rank was given, and one call per split builds the index again, synchronizes four times or more, decodes the tail
+ * block of split k alone and again as the first block of split k+1, and launches a decode and a scan that fill a corner of the chip.
+ * All contents go to ONE device buffer and all tables to ONE pair of device tables, each split to a region of its own.
+ * The one rule.  After the call items[i].out equals, field for field, what fourmc_gpu_image_read_lines gives for the same image,
+ *   split_start, split_end and max_line_len with d_dst + dst_off, dst_cap, d_starts + table_off, d_text_len + table_off and
+ *   lines_cap, and d_dst[dst_off, dst_off + out.data_bytes), d_starts[table_off .. table_off + lines] and d_text_len[table_off,
+ *   table_off + lines) hold the same values; the starts are offsets in the item's own region.  This holds for every case the single
+ *   call documents: ownership and lo / hi with the CR at a block's end, lines longer than a block, -3 for a bad split offset, both
+ *   -4s and both -5s with their precedence, `reserved`, and data_bytes as the smallest dst_cap that works, so an item with dst_cap
+ *   == 0 is a size query.  An image that cannot be indexed (a damaged footer, several streams) gives every item the index code and
+ *   the call returns FOURMC_OK, as fourmc_gpu_image_read does for its ranges.  A damaged block changes nothing for the splits that
+ *   do not cover it.  Two items may name the same split.
+ * Count only.  d_starts and d_text_len both NULL; table_off, lines_cap and table_entries are ignored.  One without the other:
+ *   FOURMC_EINVAL.
+ * Writes.  Nothing outside the items' regions; for an item, nothing outside d_dst[dst_off, dst_off + dst_cap), d_starts[table_off,
+ *   table_off + lines_cap) and d_text_len[table_off, table_off + lines_cap).  An item whose result is -3, an index code, the tail's
+ *   -4 or the -5 of dst_cap leaves its regions untouched; the -5 of lines_cap and the body's -4 leave its tables untouched.  Regions
+ *   may abut at any byte: the scan reads whole 16-byte chunks and masks, and neither writes nor counts a neighbour's byte.
+ * Arguments.  Checked on the host before any device is looked for; each of these returns FOURMC_EINVAL with `items` untouched:
+ *   items NULL with n > 0; d_image NULL; d_dst NULL; one table without the other; max_line_len > 0x7FFFFFFF; an output region that
+ *   does not lie inside [0, dst_bytes) (dst_off + dst_cap may not wrap); two output regions of nonzero dst_cap that overlap; with
+ *   tables, a table region that does not lie inside [0, table_entries), or two table regions of nonzero lines_cap that overlap.
+ *   n == 0 returns FOURMC_OK and does nothing.  No device: FOURMC_ENODEV.  On every failure `items` is left as it came.
+ * Groups.  A split still looking for its hi needs one staged tail block of 4 MiB + 64 bytes per round, so the items are processed
+ *   in groups of at most FOURMC_SPLIT_GROUP splits (env, read at every call; default 256, which is 1 GiB of staging at the most;
+ *   clamped to 1..4096; a test knob as much as a tuning knob), cut also where the tiles of one launch's grid would pass 0x7FFFFFFF.
+ *   The staging stays with the stream until fourmc_gpu_release_workspaces, like the single call's slot.
+ * Work per group.  One plan kernel, one lane per split.  Per tail round, for all splits still searching: one descriptor kernel, one
+ *   container decode, one tail-find launch of one workgroup per split.  Then ONE container decode for the bodies of all the group's
+ *   splits straight into their regions, one kernel for the staged prefixes, and one count, one finish, one write and one length
+ *   launch over all the group's spans.
+ * Synchronizations of `stream`: one for the call (the index summary; the index itself is built once per call, on the stream, and
+ *   is read back by nobody), and per group one for the plans, one per tail round and one for the results; a group none of whose
+ *   splits fits its region ends after its rounds.  The tail rounds of a group are the most tail blocks any of its splits stages:
+ *   usually 1; 0 when every split_end is at or past the end mark; more only for a line longer than a block or a block-ending CR.
+ *   A workspace that has to grow synchronizes once more, the first time a stream sees a call of that size.
+ * Settings.  FOURMC_DECODE, FOURMC_ZDECODE and the batch limits of the block decode apply as they do to the single call.
+ * Not reproduced: several images in one call; the one-byte rule of image_read_records in batch form; sharing one decode between two
+ *   items that cover the same block (each item's region gets its own copy). */
+typedef struct fourmc_image_split_item {     /* 88 bytes, no padding */
+    uint64_t split_start, split_end;         /* in : as fourmc_gpu_image_read_lines takes them                                  */
+    uint64_t dst_off, dst_cap;               /* in : the split's content goes to d_dst[dst_off, dst_off + dst_cap)              */
+    uint64_t table_off, lines_cap;           /* in : its tables are d_starts[table_off, +lines_cap), d_text_len[table_off, +lines_cap) */
+    fourmc_image_lines out;                  /* out                                                                             */
+} fourmc_image_split_item;
+int fourmc_gpu_image_read_lines_batch(const void* d_image, uint64_t image_bytes, uint32_t max_line_len,
+                                      void* d_dst, uint64_t dst_bytes,
+                                      uint64_t* d_starts, uint32_t* d_text_len, uint64_t table_entries,
+                                      fourmc_image_split_item* items /*host*/, uint32_t n, void* stream);
+/* Statistics (read-only), as fourmc_gpu_image_parse_stats: the groups image_read_lines_batch has processed so far, the tail rounds
+ * it has run and the container block-decode calls it has made (one per tail round, one per group with a body block). */
+void fourmc_gpu_image_lines_batch_stats(unsigned long long* groups, unsigned long long* tail_rounds, unsigned long long* block_decodes);
 
 /* ---- host-buffer conveniences with the reference's per-block signatures ------------------- */
 /* These stage one block through HBM (H2D, one launch, D2H).  They exist so the JNI entry points
