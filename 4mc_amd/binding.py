@@ -81,6 +81,21 @@ class ImageSplitItem(C.Structure):
                 ("table_off", C.c_uint64), ("lines_cap", C.c_uint64), ("out", ImageLines)]
 
 
+# struct fourmc_image_ref / fourmc_images_split_item / fourmc_images_slice (include/fourmc_gpu.h: the splits of many images)
+class ImageRef(C.Structure):
+    _fields_ = [("image_off", C.c_uint64), ("image_bytes", C.c_uint64)]
+
+
+class ImagesSplitItem(C.Structure):
+    _fields_ = [("image", C.c_uint32), ("pad", C.c_uint32), ("split_start", C.c_uint64), ("split_end", C.c_uint64), ("dst_off", C.c_uint64),
+                ("dst_cap", C.c_uint64), ("table_off", C.c_uint64), ("lines_cap", C.c_uint64), ("out", ImageLines)]
+
+
+class ImagesSlice(C.Structure):
+    _fields_ = [("image", C.c_uint32), ("pad", C.c_uint32), ("s", ImageSlice)]
+
+
+assert C.sizeof(ImageRef) == 16 and C.sizeof(ImagesSplitItem) == 96 and C.sizeof(ImagesSlice) == 56
 assert C.sizeof(ImageSlice) == 48 and C.sizeof(ImageRecords) == 40 and C.sizeof(ImageLines) == 40 and C.sizeof(ImageSplitItem) == 88
 IMAGE_ENTRY_DTYPE = np.dtype([("image_off", "<u8"), ("data_off", "<u8"), ("usize", "<u4"), ("csize", "<u4"),
                               ("xxh32", "<u4"), ("pad", "<u4")])
@@ -158,6 +173,10 @@ _GPU_API = {
     "fourmc_gpu_image_read_lines_batch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                                     C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_image_lines_batch_stats": (None, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_images_read_lines": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                               C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "fourmc_gpu_images_lines_stats": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_images_align_slices": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_debug_lines_scan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_debug_records_scan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint8, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_writer_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p]),

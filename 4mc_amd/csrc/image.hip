@@ -537,9 +537,8 @@ __device__ int64_t index_header(const uint8_t* img, uint64_t N, uint32_t* magic,
 
 // The index, one wave, 64 blocks per step: offsets and data offsets by scan, each block's header where the footer puts it, and the
 // verdict of fourmc_file_decode_blocks(0, n) with unlimited capacity - the first block, in order, that fails a check.
-__global__ __launch_bounds__(64)
-void image_index_kernel(const uint8_t* __restrict__ img, uint64_t N, fourmc_image_index_dev* __restrict__ idx,
-                        fourmc_image_entry* __restrict__ ent, uint64_t cap)
+__device__ __forceinline__ void image_index_body(const uint8_t* __restrict__ img, uint64_t N, fourmc_image_index_dev* __restrict__ idx,
+                                                 fourmc_image_entry* __restrict__ ent, uint64_t cap)
 {
     const int lane = threadIdx.x;
     uint32_t magic = 0;
@@ -589,6 +588,23 @@ void image_index_kernel(const uint8_t* __restrict__ img, uint64_t N, fourmc_imag
         idx->info.is_zstd = magic == FOURMC_MAGIC_4MZ; idx->info.pad = 0;
         idx->data_end = end;
     }
+}
+
+__global__ __launch_bounds__(64)
+void image_index_kernel(const uint8_t* __restrict__ img, uint64_t N, fourmc_image_index_dev* __restrict__ idx,
+                        fourmc_image_entry* __restrict__ ent, uint64_t cap)
+{ image_index_body(img, N, idx, ent, cap); }
+
+// The index of many images (fourmc_gpu_images_read_lines / _images_align_slices): blockIdx.x's wave is the kernel above on image
+// blockIdx.x, its summary to idx[blockIdx.x] and - when entries are asked for - its first tab[].cap entries from ent[tab[].ent0]
+// on, image-relative as fourmc_gpu_image_index writes them.  cap 0: the summary only (an image nobody asks, or one that cannot
+// be indexed).
+__global__ __launch_bounds__(64)
+void images_index_kernel(const uint8_t* __restrict__ base, const fourmc_images_tab* __restrict__ tab,
+                         fourmc_image_index_dev* __restrict__ idx, fourmc_image_entry* __restrict__ ent)
+{
+    const fourmc_images_tab t = tab[blockIdx.x];
+    image_index_body(base + t.image_off, t.image_bytes, idx + blockIdx.x, ent ? ent + t.ent0 : nullptr, ent ? uint64_t(t.cap) : 0);
 }
 
 // fourmc_file_decode_blocks(first, count, dst_cap) after read_index, one wave: lo / hi, then its loop's checks (-2 index and
@@ -1126,6 +1142,14 @@ hipError_t fourmc_launch_image_index(const void* d_image, uint64_t image_bytes, 
                                      fourmc_image_entry* d_ent, uint64_t cap, hipStream_t s)
 {
     hipLaunchKernelGGL(image_index_kernel, dim3(1), dim3(64), 0, s, static_cast<const uint8_t*>(d_image), image_bytes, d_idx, d_ent, cap);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_images_index(const void* d_images, const fourmc_images_tab* d_tab, uint32_t nimages,
+                                      fourmc_image_index_dev* d_idx, fourmc_image_entry* d_ent, hipStream_t s)
+{
+    if (!nimages) return hipSuccess;
+    hipLaunchKernelGGL(images_index_kernel, dim3(nimages), dim3(64), 0, s, static_cast<const uint8_t*>(d_images), d_tab, d_idx, d_ent);
     return hipGetLastError();
 }
 

@@ -169,6 +169,18 @@ typedef struct fourmc_image_span {
 /* d_ent NULL: the summary only; else min(n, cap) entries */
 hipError_t fourmc_launch_image_index(const void* d_image, uint64_t image_bytes, fourmc_image_index_dev* d_idx,
                                      fourmc_image_entry* d_ent, uint64_t cap, hipStream_t s);
+/* Many images with one index launch (fourmc_gpu_images_read_lines / _images_align_slices): where image i lies in the buffer and
+ * where its entries go in the one entry table.  nblocks is 0 until the summaries have come back, and stays 0 for an image that
+ * cannot be indexed, so nothing ever looks an entry of such an image up. */
+typedef struct fourmc_images_tab {
+    uint64_t image_off, image_bytes;
+    uint64_t ent0;          /* index of its first entry in the table */
+    uint32_t nblocks;       /* its blocks, for the kernels that search its entries */
+    uint32_t cap;           /* entries the index kernel writes: nblocks, or 0 for an image no item names */
+} fourmc_images_tab;
+/* one wave per image: d_idx[i] = image i's summary; d_ent NULL: nothing else, else its first cap entries at d_ent + ent0 */
+hipError_t fourmc_launch_images_index(const void* d_images, const fourmc_images_tab* d_tab, uint32_t nimages,
+                                      fourmc_image_index_dev* d_idx, fourmc_image_entry* d_ent, hipStream_t s);
 /* decode_blocks: the range's framing checks into *d_span, then its `count` descriptors (all-zero ones if a check failed) */
 hipError_t fourmc_launch_image_span(const fourmc_image_entry* d_ent, const fourmc_image_index_dev* d_idx, uint64_t image_bytes,
                                     uint32_t first, uint32_t count, uint64_t dst_cap, fourmc_image_span* d_span,
@@ -265,6 +277,10 @@ typedef struct fourmc_records_state {
 #define FOURMC_RECORDS_TILE (16u * 1024u)       /* bytes one wave scans: one count per tile */
 hipError_t fourmc_launch_image_align(const fourmc_image_entry* d_ent, uint32_t n, uint64_t image_bytes,
                                      fourmc_image_slice* d_slices, uint32_t nslices, hipStream_t s);
+/* the same over the slices of many images, each against its own image's entries; a slice of an image without entries (nblocks 0
+ * in the table) is left as it came */
+hipError_t fourmc_launch_images_align(const fourmc_image_entry* d_ent, const fourmc_images_tab* d_tab, fourmc_images_slice* d_slices,
+                                      uint32_t nslices, hipStream_t s);
 hipError_t fourmc_launch_records_plan(const fourmc_image_entry* d_ent, uint32_t n, const fourmc_image_index_dev* d_idx,
                                       uint64_t split_start, uint64_t split_end, fourmc_records_plan* d_plan, hipStream_t s);
 /* descriptors of blocks [first, first + count) with block i at data_off[i] - ds of the decode's destination (to_stage: at 0) */
@@ -294,16 +310,20 @@ hipError_t fourmc_launch_lines_finish(const void* d, uint64_t len, uint64_t* d_c
 hipError_t fourmc_launch_lines_write(const void* d, uint64_t len, uint32_t max_line_len, const uint64_t* d_cnt, uint64_t ntiles,
                                      const fourmc_records_state* d_st, uint64_t* d_starts, uint32_t* d_tlen, hipStream_t s);
 /* Many splits with one call (fourmc_gpu_image_read_lines_batch): the kernels above over a group of splits. */
-typedef struct fourmc_split_req { uint64_t split_start, split_end; } fourmc_split_req;
-/* one split still looking for its hi, for one round: block b goes to staging slot `slot` and is searched there */
-typedef struct fourmc_tail_job { uint32_t b, slot; int32_t last_block, pending; } fourmc_tail_job;
+/* The same kernels serve fourmc_gpu_images_read_lines: every request, job and span names its image, the entries of all images
+ * lie in one table (image i's from fourmc_images_tab.ent0 on, image-relative), and a descriptor's src_off is the entry's offset
+ * plus the image's.  The one-image call passes a table of one image at offset 0. */
+typedef struct fourmc_split_req { uint64_t split_start, split_end; uint32_t image, pad; } fourmc_split_req;
+/* one split still looking for its hi, for one round: entry e (its image's ent0 + the block) goes to staging slot `slot` and is
+ * searched there; src_base: the image's offset in the buffer */
+typedef struct fourmc_tail_job { uint32_t e, slot; int32_t last_block, pending; uint64_t src_base; } fourmc_tail_job;
 /* one split whose content fits its region: what the body decode, the prefix copy and the scan need of it */
 typedef struct fourmc_lines_span {
     uint8_t*  dst;          /* d_dst + dst_off */
     uint64_t  len;          /* hi - ds */
     uint64_t  tile0, ntiles;/* its tiles in the group's count table: fourmc_records_tiles(dst, len) of them from tile0 on */
     uint32_t  desc0, ndesc; /* its body blocks' descriptors in the group's table */
-    uint32_t  b0;           /* the first body block */
+    uint32_t  e0;           /* the first body block's entry: its image's ent0 + b0 */
     int32_t   first_split;  /* split_start == 0 */
     uint64_t  ds, body;     /* decoded offset of dst[0]; de - ds */
     uint64_t* starts;       /* d_starts + table_off, NULL: count only */
@@ -311,8 +331,11 @@ typedef struct fourmc_lines_span {
     uint64_t  lines_cap;
     const uint8_t* stage;   /* the split's staging slot */
     uint64_t  copy_off, copy_len;   /* dst[copy_off, +copy_len) = stage[0, copy_len): the last tail block's prefix (0: none) */
+    uint64_t  src_base;     /* the image's offset in the buffer the body decode reads from */
 } fourmc_lines_span;
-hipError_t fourmc_launch_lines_batch_plan(const fourmc_image_entry* d_ent, uint32_t n, const fourmc_image_index_dev* d_idx,
+/* d_tab / d_idx: one entry per image; request i is planned against the entries and the summary of image d_req[i].image, and its
+ * b0 / b1 count that image's blocks */
+hipError_t fourmc_launch_lines_batch_plan(const fourmc_image_entry* d_ent, const fourmc_images_tab* d_tab, const fourmc_image_index_dev* d_idx,
                                           const fourmc_split_req* d_req, uint32_t m, fourmc_records_plan* d_plan, hipStream_t s);
 /* per round: job j's block to slot * stride of the staging; after the decode, job j's verdict to d_tail[j] */
 hipError_t fourmc_launch_lines_batch_tail_desc(const fourmc_image_entry* d_ent, const fourmc_tail_job* d_job, uint32_t nj,

@@ -144,14 +144,10 @@ __device__ uint32_t next_block(const fourmc_image_entry* ent, uint32_t n, uint64
     return lo;
 }
 
-// one lane per slice: alignSliceStartToIndex / alignSliceEndToIndex (FourMcBlockIndex.java:142-173), fileSize = image_bytes
-__global__ __launch_bounds__(256)
-void image_align_kernel(const fourmc_image_entry* __restrict__ ent, uint32_t n, uint64_t image_bytes,
-                        fourmc_image_slice* __restrict__ slices, uint32_t nslices)
+// alignSliceStartToIndex / alignSliceEndToIndex (FourMcBlockIndex.java:142-173), fileSize = image_bytes
+__device__ __forceinline__ fourmc_image_slice align_slice(const fourmc_image_entry* __restrict__ ent, uint32_t n, uint64_t image_bytes,
+                                                          fourmc_image_slice q)
 {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= nslices) return;
-    fourmc_image_slice q = slices[i];
     const uint32_t j = next_block(ent, n, q.end);
     q.split_end = j < n ? ent[j].image_off : image_bytes;
     uint32_t first = 0;
@@ -165,7 +161,28 @@ void image_align_kernel(const fourmc_image_entry* __restrict__ ent, uint32_t n, 
     q.first_block = kept ? first : 0;
     q.block_count = kept ? j - first : 0;
     q.result = kept ? 1 : 0;
-    slices[i] = q;
+    return q;
+}
+
+// one lane per slice
+__global__ __launch_bounds__(256)
+void image_align_kernel(const fourmc_image_entry* __restrict__ ent, uint32_t n, uint64_t image_bytes,
+                        fourmc_image_slice* __restrict__ slices, uint32_t nslices)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nslices) return;
+    slices[i] = align_slice(ent, n, image_bytes, slices[i]);
+}
+
+// one lane per slice of any of the images
+__global__ __launch_bounds__(256)
+void images_align_kernel(const fourmc_image_entry* __restrict__ ent, const fourmc_images_tab* __restrict__ tab,
+                         fourmc_images_slice* __restrict__ slices, uint32_t nslices)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nslices) return;
+    const fourmc_images_tab t = tab[slices[i].image];
+    if (t.nblocks) slices[i].s = align_slice(ent + t.ent0, t.nblocks, t.image_bytes, slices[i].s);
 }
 
 // the split's offsets into blocks and decoded offsets
@@ -562,11 +579,15 @@ __device__ __forceinline__ uint32_t span_of(const T* __restrict__ first, uint32_
 
 // one lane per split
 __global__ __launch_bounds__(256)
-void lines_batch_plan_kernel(const fourmc_image_entry* __restrict__ ent, uint32_t n, const fourmc_image_index_dev* __restrict__ idx,
-                             const fourmc_split_req* __restrict__ req, uint32_t m, fourmc_records_plan* __restrict__ plan)
+void lines_batch_plan_kernel(const fourmc_image_entry* __restrict__ ent, const fourmc_images_tab* __restrict__ tab,
+                             const fourmc_image_index_dev* __restrict__ idx, const fourmc_split_req* __restrict__ req, uint32_t m,
+                             fourmc_records_plan* __restrict__ plan)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i < m) plan[i] = plan_split(ent, n, idx, req[i].split_start, req[i].split_end);
+    if (i >= m) return;
+    const fourmc_split_req q = req[i];
+    const fourmc_images_tab t = tab[q.image];
+    plan[i] = plan_split(ent + t.ent0, t.nblocks, idx + q.image, q.split_start, q.split_end);
 }
 
 // one lane per searching split: its next tail block into its staging slot
@@ -576,9 +597,9 @@ void lines_batch_tail_desc_kernel(const fourmc_image_entry* __restrict__ ent, co
 {
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j >= nj) return;
-    const fourmc_image_entry e = ent[job[j].b];
+    const fourmc_image_entry e = ent[job[j].e];
     fourmc_block d;
-    d.src_off = e.image_off + 12; d.dst_off = uint64_t(job[j].slot) * stride; d.src_len = e.csize; d.dst_cap = e.usize; d.result = 0; d.xxh32 = e.xxh32;
+    d.src_off = job[j].src_base + e.image_off + 12; d.dst_off = uint64_t(job[j].slot) * stride; d.src_len = e.csize; d.dst_cap = e.usize; d.result = 0; d.xxh32 = e.xxh32;
     desc[j] = d;
 }
 
@@ -589,7 +610,7 @@ void lines_batch_tail_find_kernel(const uint8_t* __restrict__ stage, uint64_t st
                                   fourmc_records_tail* __restrict__ out)
 {
     const fourmc_tail_job q = job[blockIdx.x];
-    lines_tail_find_body(stage + uint64_t(q.slot) * stride, desc + blockIdx.x, ent, q.b, q.last_block, q.pending, out + blockIdx.x);
+    lines_tail_find_body(stage + uint64_t(q.slot) * stride, desc + blockIdx.x, ent, q.e, q.last_block, q.pending, out + blockIdx.x);
 }
 
 // one lane per body block of the group: block b0 + i of its span, at its decoded offset in the span's region
@@ -603,9 +624,9 @@ void lines_batch_body_desc_kernel(const fourmc_image_entry* __restrict__ ent, co
     uint32_t lo = 0, hi = ns;
     while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (first[mid] <= i) lo = mid + 1; else hi = mid; }
     const fourmc_lines_span& sp = spans[lo - 1];
-    const fourmc_image_entry e = ent[sp.b0 + (i - sp.desc0)];
+    const fourmc_image_entry e = ent[sp.e0 + (i - sp.desc0)];
     fourmc_block d;
-    d.src_off = e.image_off + 12; d.dst_off = uint64_t(sp.dst - d_dst) + (e.data_off - sp.ds); d.src_len = e.csize; d.dst_cap = e.usize;
+    d.src_off = sp.src_base + e.image_off + 12; d.dst_off = uint64_t(sp.dst - d_dst) + (e.data_off - sp.ds); d.src_len = e.csize; d.dst_cap = e.usize;
     d.result = 0; d.xxh32 = e.xxh32;
     desc[i] = d;
 }
@@ -684,6 +705,14 @@ hipError_t fourmc_launch_image_align(const fourmc_image_entry* d_ent, uint32_t n
 {
     if (!nslices) return hipSuccess;
     hipLaunchKernelGGL(image_align_kernel, dim3((nslices + 255) / 256), dim3(256), 0, s, d_ent, n, image_bytes, d_slices, nslices);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_images_align(const fourmc_image_entry* d_ent, const fourmc_images_tab* d_tab, fourmc_images_slice* d_slices,
+                                      uint32_t nslices, hipStream_t s)
+{
+    if (!nslices) return hipSuccess;
+    hipLaunchKernelGGL(images_align_kernel, dim3((nslices + 255) / 256), dim3(256), 0, s, d_ent, d_tab, d_slices, nslices);
     return hipGetLastError();
 }
 
@@ -782,11 +811,11 @@ hipError_t fourmc_launch_lines_write(const void* d, uint64_t len, uint32_t max_l
     return hipGetLastError();
 }
 
-hipError_t fourmc_launch_lines_batch_plan(const fourmc_image_entry* d_ent, uint32_t n, const fourmc_image_index_dev* d_idx,
+hipError_t fourmc_launch_lines_batch_plan(const fourmc_image_entry* d_ent, const fourmc_images_tab* d_tab, const fourmc_image_index_dev* d_idx,
                                           const fourmc_split_req* d_req, uint32_t m, fourmc_records_plan* d_plan, hipStream_t s)
 {
     if (!m) return hipSuccess;
-    hipLaunchKernelGGL(lines_batch_plan_kernel, dim3((m + 255) / 256), dim3(256), 0, s, d_ent, n, d_idx, d_req, m, d_plan);
+    hipLaunchKernelGGL(lines_batch_plan_kernel, dim3((m + 255) / 256), dim3(256), 0, s, d_ent, d_tab, d_idx, d_req, m, d_plan);
     return hipGetLastError();
 }
 

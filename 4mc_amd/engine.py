@@ -8,7 +8,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .binding import (BLOCK_DTYPE, CODEC_LZ4_FAST, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines, ImageSplitItem,
+from .binding import (BLOCK_DTYPE, CODEC_LZ4_FAST, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines, ImageRef, ImageSplitItem,
+                      ImagesSlice, ImagesSplitItem,
                       ImageRange, ImageRecords, ImageSlice, ImageStatus, check, lib)
 
 
@@ -349,6 +350,73 @@ def image_lines_batch_stats():
     g, r, d = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
     lib().fourmc_gpu_image_lines_batch_stats(C.byref(g), C.byref(r), C.byref(d))
     return int(g.value), int(r.value), int(d.value)
+
+
+def _image_refs(images, who):
+    refs = [tuple(int(v) for v in im) for im in images]
+    arr = (ImageRef * max(len(refs), 1))()
+    for k, im in enumerate(refs):
+        if len(im) != 2:
+            raise EngineError("%s images: (image_off, image_bytes) each" % who)
+        arr[k].image_off, arr[k].image_bytes = im
+    return arr, len(refs)
+
+
+def images_read_lines(d_images, images, splits, d_dst, starts=None, text_len=None, max_line_len=0x7FFFFFFF, images_bytes=None, stream=None):
+    """image_read_lines_batch for the splits of many images that lie in one device buffer (fourmc_gpu_images_read_lines).  `images`
+    is a sequence of (image_off, image_bytes), `splits` a sequence of (image, split_start, split_end, dst_off, dst_cap, table_off,
+    lines_cap) with `image` an index into `images` and the split offsets counted in that image.  The regions, the tables and the
+    returned dicts (one per split) are image_read_lines_batch's; .4mc and .4mz images may be mixed, and an image that cannot be
+    indexed gives only its own splits the index code."""
+    ptr = _dev_ptr(d_images, "images_read_lines d_images")
+    dst = _dev_ptr(d_dst, "images_read_lines d_dst")
+    n = _image_len(d_images, images_bytes, "images_read_lines")
+    if (starts is None) != (text_len is None):
+        raise EngineError("images_read_lines: starts and text_len go together (both None: count only)")
+    if not 0 <= int(max_line_len) <= 0x7FFFFFFF:
+        raise EngineError("images_read_lines max_line_len: 0 .. 0x7FFFFFFF")
+    sp, tp, entries = 0, 0, 0
+    if starts is not None:
+        if not (isinstance(starts, torch.Tensor) and starts.is_cuda and starts.is_contiguous() and starts.dtype == torch.int64):
+            raise EngineError("images_read_lines starts: a contiguous int64 CUDA tensor is required")
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if not (isinstance(text_len, torch.Tensor) and text_len.is_cuda and text_len.is_contiguous() and text_len.dtype in words):
+            raise EngineError("images_read_lines text_len: a contiguous int32 or uint32 CUDA tensor is required")
+        sp, tp, entries = int(starts.data_ptr()), int(text_len.data_ptr()), min(starts.numel(), text_len.numel() + 1)
+    refs, nimages = _image_refs(images, "images_read_lines")
+    rows = [tuple(int(v) for v in q) for q in splits]
+    arr = (ImagesSplitItem * max(len(rows), 1))()
+    for i, row in enumerate(rows):
+        if len(row) != 7:
+            raise EngineError("images_read_lines splits: (image, split_start, split_end, dst_off, dst_cap, table_off, lines_cap) each")
+        (arr[i].image, arr[i].split_start, arr[i].split_end, arr[i].dst_off, arr[i].dst_cap, arr[i].table_off, arr[i].lines_cap) = row
+    check(lib().fourmc_gpu_images_read_lines(ptr, n, C.cast(refs, C.c_void_p), nimages, int(max_line_len), dst, d_dst.numel(), sp, tp, entries,
+                                             C.cast(arr, C.c_void_p), len(rows), _stream_ptr(stream)), "fourmc_gpu_images_read_lines")
+    return [{name: int(getattr(arr[i].out, name)) for name, _ in ImageLines._fields_} for i in range(len(rows))]
+
+
+def images_lines_stats():
+    """(groups, tail_rounds, block_decodes, index_launches) of images_read_lines so far in this process."""
+    g, r, d, x = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
+    lib().fourmc_gpu_images_lines_stats(C.byref(g), C.byref(r), C.byref(d), C.byref(x))
+    return int(g.value), int(r.value), int(d.value), int(x.value)
+
+
+def images_align_slices(d_images, images, slices, images_bytes=None, stream=None):
+    """image_align_slices for the raw slices [(image, start, end), ...] of many images in one device buffer
+    (fourmc_gpu_images_align_slices).  Returns one dict per slice: image and the fields image_align_slices returns."""
+    ptr = _dev_ptr(d_images, "images_align_slices d_images")
+    n = _image_len(d_images, images_bytes, "images_align_slices")
+    refs, nimages = _image_refs(images, "images_align_slices")
+    q = [tuple(int(v) for v in sl) for sl in slices]
+    arr = (ImagesSlice * max(len(q), 1))()
+    for i, sl in enumerate(q):
+        if len(sl) != 3:
+            raise EngineError("images_align_slices slices: (image, start, end) each")
+        arr[i].image, arr[i].s.start, arr[i].s.end = sl
+    check(lib().fourmc_gpu_images_align_slices(ptr, n, C.cast(refs, C.c_void_p), nimages, C.cast(arr, C.c_void_p), len(q), _stream_ptr(stream)),
+          "fourmc_gpu_images_align_slices")
+    return [dict({"image": int(arr[i].image)}, **{name: int(getattr(arr[i].s, name)) for name, _ in ImageSlice._fields_}) for i in range(len(q))]
 
 
 class ImageWriter:

@@ -510,8 +510,9 @@ int fourmc_gpu_image_read_lines(const void* d_image, uint64_t image_bytes, uint6
  *   usually 1; 0 when every split_end is at or past the end mark; more only for a line longer than a block or a block-ending CR.
  *   A workspace that has to grow synchronizes once more, the first time a stream sees a call of that size.
  * Settings.  FOURMC_DECODE, FOURMC_ZDECODE and the batch limits of the block decode apply as they do to the single call.
- * Not reproduced: several images in one call; the one-byte rule of image_read_records in batch form; sharing one decode between two
- *   items that cover the same block (each item's region gets its own copy). */
+ * Several images in one call: fourmc_gpu_images_read_lines below.
+ * Not reproduced: the one-byte rule of image_read_records in batch form; sharing one decode between two items that cover the same
+ *   block (each item's region gets its own copy). */
 typedef struct fourmc_image_split_item {     /* 88 bytes, no padding */
     uint64_t split_start, split_end;         /* in : as fourmc_gpu_image_read_lines takes them                                  */
     uint64_t dst_off, dst_cap;               /* in : the split's content goes to d_dst[dst_off, dst_off + dst_cap)              */
@@ -525,6 +526,71 @@ int fourmc_gpu_image_read_lines_batch(const void* d_image, uint64_t image_bytes,
 /* Statistics (read-only), as fourmc_gpu_image_parse_stats: the groups image_read_lines_batch has processed so far, the tail rounds
  * it has run and the container block-decode calls it has made (one per tail round, one per group with a body block). */
 void fourmc_gpu_image_lines_batch_stats(unsigned long long* groups, unsigned long long* tail_rounds, unsigned long long* block_decodes);
+
+/* ---- the lines of the splits of MANY images with one call --------------------------------------------------------------------
+ * A Hadoop dataset is a directory of part files of a few blocks each (the case fourmc_gpu_images_decompress and _images_compress
+ * were built for).  image_read_lines_batch takes the splits of ONE image: a job with a thousand part files in HBM makes a thousand
+ * calls, each of which builds an index, synchronizes four times or more and launches decodes and scans that fill a corner of the
+ * chip.  Here the images lie in ONE device buffer, image k at d_images + images[k].image_off, and every item names its image.
+ * The one rule.  After the call items[i].out and the item's regions of d_dst, d_starts and d_text_len equal what
+ *   fourmc_gpu_image_read_lines_batch gives for a one-item call with the image d_images + images[image].image_off of
+ *   images[image].image_bytes bytes and the same split offsets and capacities - and so, by that call's rule, what
+ *   fourmc_gpu_image_read_lines gives for the split.  Every case documented there carries over: ownership and lo / hi with a CR at
+ *   a block's end, lines longer than a block, -3 for a bad split offset, both -4s and both -5s with their precedence, `reserved`,
+ *   data_bytes as the smallest capacity that works (dst_cap == 0 is a size query), count only with both tables NULL, and what an
+ *   item may write.
+ * Only with several images.  The format is each image's own header's, as in the random-access group: one call may mix .4mc and
+ *   .4mz.  An image that cannot be indexed (a damaged footer, several streams, fewer than 12 bytes, image_bytes == 0) gives ITS
+ *   items the index code; every other item is unaffected and the call returns FOURMC_OK.  A damaged block changes nothing for the
+ *   splits that do not cover it, in its own image or any other.  A split offset is judged against its own image's headers: one
+ *   that is a block header of another image of the call is -3.  Two entries of `images` may name the same or overlapping bytes,
+ *   and two items may name the same split.
+ * Arguments.  Checked on the host before any device is looked for; each returns FOURMC_EINVAL with `items` untouched: all that
+ *   image_read_lines_batch checks (d_images for d_image); images NULL with nimages > 0; an image region that does not lie inside
+ *   [0, images_bytes); an item whose image >= nimages.  n == 0 returns FOURMC_OK and does nothing.  More than 0x7FFFFFFF blocks
+ *   over all images: FOURMC_EUNSUP.  No device: FOURMC_ENODEV.  On every failure `items` is left as it came.
+ * Slack.  The decoders may read up to 64 bytes past a payload: inside the buffer that is the next image; behind the last image
+ *   the caller keeps that slack, as for fourmc_gpu_images_decompress.
+ * Index.  One kernel indexes all images, one wave per image in a grid of nimages; its body is the one-image index kernel's, so
+ *   the verdicts are the same by construction.  It runs twice: the first run writes only the summaries, which come back in ONE
+ *   read-back (the call's first synchronization: nblocks, the code and the format of every image, which size the entry table);
+ *   the second writes the entries of every indexable image that an item names, image k's at that image's first-entry index (the
+ *   host's prefix sum over the block counts, uploaded with the image table).  The entries are image-relative, equal to
+ *   fourmc_gpu_image_index's; the image's offset is added where descriptors are made.  A workspace that has to grow later loses
+ *   the entries and the kernel runs again.
+ * Groups.  As in the one-image call (the same host function runs both): the items in the order given, at most FOURMC_SPLIT_GROUP
+ *   to a group with the same cut at the grid limit; per group one synchronization for the plans, one per tail round and one for
+ *   the results; one plan launch with a lane per split, each request carrying its image; per round one descriptor launch and one
+ *   tail-find launch for all searching splits of all images ("last block" is the last of the split's own image); the body
+ *   descriptors, the prefix copy and the count / finish / write / length launches once over all the group's spans.
+ * Decodes.  The host knows every item's format after the index read-back and orders a round's jobs, and a group's spans, with .4mc
+ *   before .4mz: each phase is ONE fourmc_gpu_4mc_decode_blocks per format present, with d_images as its source - one call per
+ *   round and one for the bodies when the dataset has one format, two when it has both.  Staging is one slot of 4 MiB + 64 bytes
+ *   per searching split of the group.
+ * Synchronizations of `stream`: one for the summaries, then per group as above; a workspace that has to grow synchronizes once more.
+ * Statistics.  fourmc_gpu_images_lines_stats: the groups, tail rounds and block-decode calls of THIS call so far, and the launches
+ *   of the index kernel (2 per call when nothing grows).  fourmc_gpu_image_lines_batch_stats is not incremented by it. */
+typedef struct fourmc_image_ref { uint64_t image_off, image_bytes; } fourmc_image_ref;      /* 16 bytes */
+typedef struct fourmc_images_split_item {      /* 96 bytes, no padding */
+    uint32_t image, pad;                       /* in : index into `images`; pad is ignored            */
+    uint64_t split_start, split_end;           /* in : offsets in THAT image, as image_read_lines takes them */
+    uint64_t dst_off, dst_cap;
+    uint64_t table_off, lines_cap;
+    fourmc_image_lines out;                    /* out */
+} fourmc_images_split_item;
+int fourmc_gpu_images_read_lines(const void* d_images, uint64_t images_bytes,
+                                 const fourmc_image_ref* images /*host*/, uint32_t nimages, uint32_t max_line_len,
+                                 void* d_dst, uint64_t dst_bytes, uint64_t* d_starts, uint32_t* d_text_len, uint64_t table_entries,
+                                 fourmc_images_split_item* items /*host*/, uint32_t n, void* stream);
+void fourmc_gpu_images_lines_stats(unsigned long long* groups, unsigned long long* tail_rounds,
+                                   unsigned long long* block_decodes, unsigned long long* index_launches);
+/* fourmc_gpu_image_align_slices for the slices of many images: each slices[i].s comes back as that call returns it for the image
+ * images[slices[i].image] alone, the index code in `result` for an image that cannot be indexed and "unchanged, result 1" for an
+ * image without blocks included.  The batched index above and ONE align launch over all slices; two synchronizations whatever
+ * the counts (the summaries, the results).  Arguments as above (slices for items); n == 0 returns FOURMC_OK and does nothing. */
+typedef struct fourmc_images_slice { uint32_t image, pad; fourmc_image_slice s; } fourmc_images_slice;   /* 56 bytes */
+int fourmc_gpu_images_align_slices(const void* d_images, uint64_t images_bytes, const fourmc_image_ref* images /*host*/,
+                                   uint32_t nimages, fourmc_images_slice* slices /*host*/, uint32_t n, void* stream);
 
 /* ---- host-buffer conveniences with the reference's per-block signatures ------------------- */
 /* These stage one block through HBM (H2D, one launch, D2H).  They exist so the JNI entry points
