@@ -1,6 +1,7 @@
 // 4mc_amd/csrc/lz4hc_encode.hip — K3: batched LZ4 HC (hash-chain) block encode on gfx950,
-// BYTE-IDENTICAL to LZ4_compress_HC of the reference at the levels 4mc reaches
-// (4mc High = level 4, 4mc Ultra = level 8).
+// BYTE-IDENTICAL to LZ4_compress_HC of the reference at every hash-chain level 1..8
+// (4mc High = level 4, 4mc Ultra = level 8; compressBytesDirectHC(level) passes any level), checked per level on
+// the search-and-parse catalogue tests/hc_shapes.py.
 //
 // Replaces native/4mc.c:301 with LZ4_compress_HC (:249-252) and native/jniCompressor.c:157
 // (LZ4_compressHC2) -> native/lz4/lz4hc.c:958-973 -> :800-861 -> LZ4HC_compress_hashChain :553-788,

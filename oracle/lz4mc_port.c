@@ -35,6 +35,9 @@ static uint8_t* put_len(uint8_t* op, uint32_t rest)      /* continuation bytes o
 
 /* cap < 0: no output limit (LZ4_compressMC); else LZ4_compressMC_limitedOutput(.., cap) */
 int orc_lz4mc_compress(const uint8_t* src, uint8_t* dst, int n, int cap)
+{ return orc_lz4mc_compress_ex(src, dst, n, cap, NULL); }
+
+int orc_lz4mc_compress_ex(const uint8_t* src, uint8_t* dst, int n, int cap, orc_trace* t)
 {
     mc_t* c = (mc_t*)malloc(sizeof *c);
     const int limited = cap >= 0;
@@ -50,7 +53,14 @@ int orc_lz4mc_compress(const uint8_t* src, uint8_t* dst, int n, int cap)
     while (ip < mflimit) {
         int64_t ref, best = 0;
         size_t ml = 0;
-        int attempts = 4;
+        int attempts = 4, walked = 0, hits = 0, share = 0, win = -1;
+        if (t) {                                           /* which of the probe's three table slots meet in one bucket */
+            const int i0 = ntu < ip, i1 = ntu + 1 < ip;
+            const uint32_t w0 = i0 ? rd32(src + ntu) : 0, w1 = i1 ? rd32(src + ip - 1) : 0, w = rd32(src + ip);
+            if (i0 && i1 && mc_hash(src + ntu) == mc_hash(src + ip - 1)) share |= ORC_SHARE_NTU_PREV | (w0 != w1 ? ORC_DIFF_NTU_PREV : 0);
+            if (i0 && mc_hash(src + ntu) == mc_hash(src + ip)) share |= ORC_SHARE_NTU_IP | (w0 != w ? ORC_DIFF_NTU_IP : 0);
+            if (i1 && mc_hash(src + ip - 1) == mc_hash(src + ip)) share |= ORC_SHARE_PREV_IP | (w1 != w ? ORC_DIFF_PREV_IP : 0);
+        }
         /* insert: the first pending position, then jump to ip-1 (:391-403) */
         while (ntu < ip) {
             const uint32_t h = mc_hash(src + ntu);
@@ -63,24 +73,30 @@ int orc_lz4mc_compress(const uint8_t* src, uint8_t* dst, int n, int cap)
         }
         ref = (int64_t)c->hash[mc_hash(src + ip)];
         while ((uint32_t)(ip - ref) <= MAXDIST && attempts) {
-            attempts--;
+            attempts--; walked++;
+            if (t && rd32(src + ref) == rd32(src + ip)) hits++;
             if (src[ref + ml] == src[ip + ml] && rd32(src + ref) == rd32(src + ip)) {
                 size_t k = 4;
                 while (ip + (int64_t)k < matchlimit && src[ip + k] == src[ref + k]) k++;
-                if (k > ml) { ml = k; best = ref; }
+                if (k > ml) { ml = k; best = ref; win = walked - 1; }
             }
             ref -= c->chain[ref & (MAXD - 1)];
         }
+        {   const int32_t w[ORC_TR_PROBE_WORDS] = {t ? t->n[ORC_TR_EMIT] / 3 : 0, (int32_t)ip, (int32_t)step, (int32_t)tries, walked, hits,
+                                                   ml ? (int32_t)best : -1, (int32_t)ml, share, win,
+                                                   (uint32_t)(ip - ref) <= MAXDIST ? (int32_t)ref : -1};
+            orc_tr_put(t, ORC_TR_SEARCH, w, ORC_TR_PROBE_WORDS); }
         if (!ml) { ip += step; step = tries++ >> 6; continue; }
         {   /* encode (:466-505) */
             uint32_t len = (uint32_t)(ip - anchor);
             uint8_t* token = op++;
-            if (limited && op + len + (2 + 1 + LASTLIT) + (len >> 8) > oend) goto out;
+            {   const int32_t w[3] = {(int32_t)len, (int32_t)ml, (int32_t)(ip - best)}; orc_tr_put(t, ORC_TR_EMIT, w, 3); }
+            if (limited && op + len + (2 + 1 + LASTLIT) + (len >> 8) > oend) { orc_tr_arm(t, ORC_REFUSE_LITERALS, ip); goto out; }
             if (len >= 15) { *token = 0xF0; op = put_len(op, len - 15); } else *token = (uint8_t)(len << 4);
             memcpy(op, src + anchor, len); op += len;
             op[0] = (uint8_t)(ip - best); op[1] = (uint8_t)((ip - best) >> 8); op += 2;
             len = (uint32_t)ml - 4;
-            if (limited && op + (1 + LASTLIT) + (len >> 8) > oend) goto out;
+            if (limited && op + (1 + LASTLIT) + (len >> 8) > oend) { orc_tr_arm(t, ORC_REFUSE_MATCHLEN, ip); goto out; }
             if (len >= 15) { *token += 15; op = put_len(op, len - 15); } else *token += (uint8_t)len;
             ip += (int64_t)ml; anchor = ip;
         }
@@ -88,7 +104,8 @@ int orc_lz4mc_compress(const uint8_t* src, uint8_t* dst, int n, int cap)
     }
     {   /* last literals (:565-573) */
         const uint32_t run = (uint32_t)(n - anchor);
-        if (limited && (uint32_t)(op - dst) + run + 1 + (run + 255 - 15) / 255 > (uint32_t)cap) goto out;
+        {   const int32_t w[3] = {(int32_t)run, 0, 0}; orc_tr_put(t, ORC_TR_EMIT, w, 3); }
+        if (limited && (uint32_t)(op - dst) + run + 1 + (run + 255 - 15) / 255 > (uint32_t)cap) { orc_tr_arm(t, ORC_REFUSE_LAST, anchor); goto out; }
         if (run >= 15) { *op++ = 0xF0; op = put_len(op, run - 15); } else *op++ = (uint8_t)(run << 4);
         memcpy(op, src + anchor, run); op += run;
         result = (int)(op - dst);

@@ -58,10 +58,12 @@ def _run(gpu, srcs, caps, launch):
     return res, [out[d:d + max(r, 0)] for d, r in zip(dsts, res)], d_out, dsts
 
 
-@pytest.mark.parametrize("codec", ["lz4_fast", "lz4_mc", "lz4_hc4", "zstd1", "zstd3", "zstd6", "zstd12"])
+@pytest.mark.parametrize("codec", ["lz4_fast", "lz4_mc", "lz4_hc4", "zstd1", "zstd3", "zstd6", "zstd12",
+                                   "lz4_hc1", "lz4_hc3", "lz4_hc6", "lz4_hc7"])
 def test_fuzz_encoders_equal_oracle(gpu, codec):
-    srcs = _inputs({"lz4_fast": 1, "lz4_mc": 2, "lz4_hc4": 3, "zstd1": 4, "zstd3": 5, "zstd6": 6, "zstd12": 7}[codec],
-                   60 if codec == "lz4_hc4" else 240 if codec == "zstd12" else 160)
+    srcs = _inputs({"lz4_fast": 1, "lz4_mc": 2, "lz4_hc4": 3, "zstd1": 4, "zstd3": 5, "zstd6": 6, "zstd12": 7,
+                    "lz4_hc1": 8, "lz4_hc3": 9, "lz4_hc6": 10, "lz4_hc7": 11}[codec],
+                   60 if codec.startswith("lz4_hc") else 240 if codec == "zstd12" else 160)
     lz4_bound = [helpers.oracle().orc_lz4_compress_bound(len(s)) for s in srcs]
     rng = np.random.default_rng(99)
     # a mix of capacities: bound, n-1 (container), and something smaller
@@ -74,6 +76,7 @@ def test_fuzz_encoders_equal_oracle(gpu, codec):
         "lz4_fast": lambda a, b, c: gpu.lz4_compress_fast(a, b, c),
         "lz4_mc": lambda a, b, c: gpu.lz4_compress_mc(a, b, c),
         "lz4_hc4": lambda a, b, c: gpu.lz4_compress_hc(a, b, c, 4),
+        **{f"lz4_hc{v}": (lambda a, b, c, v=v: gpu.lz4_compress_hc(a, b, c, v)) for v in (1, 3, 6, 7)},
         "zstd1": lambda a, b, c: gpu.zstd_compress(a, b, c, 1),
         "zstd3": lambda a, b, c: gpu.zstd_compress(a, b, c, 3),
         "zstd6": lambda a, b, c: gpu.zstd_compress(a, b, c, 6),
@@ -83,6 +86,7 @@ def test_fuzz_encoders_equal_oracle(gpu, codec):
         "lz4_fast": lambda s, cap: helpers.orc_compress(s, cap),
         "lz4_mc": lambda s, cap: helpers.orc_compress_mc(s, cap),
         "lz4_hc4": lambda s, cap: helpers.orc_compress_hc(s, 4, cap),
+        **{f"lz4_hc{v}": (lambda s, cap, v=v: helpers.orc_compress_hc(s, v, cap)) for v in (1, 3, 6, 7)},
         "zstd1": lambda s, cap: helpers.orc_zstd_compress(s, 1, cap),
         "zstd3": lambda s, cap: helpers.orc_zstd_compress(s, 3, cap),
         "zstd6": lambda s, cap: helpers.orc_zstd_compress(s, 6, cap),
