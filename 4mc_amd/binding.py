@@ -45,6 +45,34 @@ class ImageEncItem(C.Structure):
 assert C.sizeof(ImageEncItem) == 40
 
 
+# struct fourmc_bstream_status / fourmc_bstream_item (include/fourmc_gpu.h: Hadoop block streams)
+class BstreamStatus(C.Structure):
+    _fields_ = [("decoded_bytes", C.c_uint64), ("total_bytes", C.c_uint64), ("fail_offset", C.c_uint64),
+                ("groups", C.c_uint32), ("chunks", C.c_uint32), ("reason", C.c_int32), ("pad", C.c_uint32)]
+
+
+class BstreamItem(C.Structure):
+    _fields_ = [("image_off", C.c_uint64), ("image_bytes", C.c_uint64), ("dst_off", C.c_uint64), ("dst_cap", C.c_uint64),
+                ("status", BstreamStatus)]
+
+
+assert C.sizeof(BstreamStatus) == 40 and C.sizeof(BstreamItem) == 72
+# FOURMC_BS_*: the verdict of a block-stream decode, by number
+BSTREAM_REASONS = ("OK", "BAD_RAWLEN", "CLEN_UNREADABLE", "BAD_CLEN", "DATA_UNREADABLE", "CORRUPT", "SHAPE", "DST_SMALL")
+# the extensions of the reference's eight block codecs -> (codec, level) for compress_bstream (Lz4Codec.java:162 and its siblings;
+# the levels from Lz4HighCompressor / Lz4UltraCompressor / Zstd*Compressor.compressBytesDirectSpecific)
+_BSTREAM_EXT = {".lz4_fast": (CODEC_LZ4_FAST, 0), ".lz4_mc": (CODEC_LZ4_MC, 0), ".lz4_hc": (CODEC_LZ4_HC, 4), ".lz4_uc": (CODEC_LZ4_HC, 8),
+                ".zstd_fast": (CODEC_ZSTD, 1), ".zstd_mc": (CODEC_ZSTD, 3), ".zstd_hc": (CODEC_ZSTD, 6), ".zstd_uc": (CODEC_ZSTD, 12)}
+
+
+def bstream_codec(ext):
+    """(codec, level) of a block-stream file by its extension or name: ".lz4_fast", "part-00000.zstd_hc", ..."""
+    key = "." + str(ext).rsplit(".", 1)[-1]
+    if key not in _BSTREAM_EXT:
+        raise EngineError(f"bstream_codec: {ext!r} names none of {', '.join(_BSTREAM_EXT)}")
+    return _BSTREAM_EXT[key]
+
+
 # struct fourmc_image_entry / fourmc_image_index_info / fourmc_image_range (include/fourmc_gpu.h: random access)
 class ImageEntry(C.Structure):
     _fields_ = [("image_off", C.c_uint64), ("data_off", C.c_uint64), ("usize", C.c_uint32), ("csize", C.c_uint32),
@@ -161,6 +189,12 @@ _GPU_API = {
     "fourmc_gpu_image_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_images_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_image_reason_text": (C.c_char_p, [C.c_int]),
+    "fourmc_gpu_bstream_max_input": (C.c_uint32, [C.c_int]),
+    "fourmc_gpu_bstream_bound": (C.c_uint64, [C.c_uint64, C.c_int, C.c_uint32]),
+    "fourmc_gpu_bstream_compress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p]),
+    "fourmc_gpu_bstream_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_bstreams_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "fourmc_gpu_bstream_reason_text": (C.c_char_p, [C.c_int]),
     "fourmc_gpu_image_parse_stats": (None, [C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_decode_blocks": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),

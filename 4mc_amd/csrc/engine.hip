@@ -1105,6 +1105,226 @@ int fourmc_gpu_images_decompress(const void* d_images, uint64_t images_bytes, vo
     return FOURMC_OK;
 }
 
+// ------------------------------------------------------------------------ Hadoop block streams (bstream.hip)
+// The part files of Lz4Codec / ZstdCodec and their siblings: BlockCompressorStream's framing around raw LZ4 blocks / zstd frames
+// (include/fourmc_gpu.h has the format, the reader rule and where they come from).
+static int bs_family(int codec)                     // 0 the LZ4 codecs, 1 zstd, -1 no codec
+{
+    if (codec == FOURMC_CODEC_LZ4_FAST || codec == FOURMC_CODEC_LZ4_MC || codec == FOURMC_CODEC_LZ4_HC) return 0;
+    return codec == FOURMC_CODEC_ZSTD ? 1 : -1;
+}
+static uint32_t bs_block_bound(int zstd, uint32_t n)
+{ return zstd ? uint32_t(fourmc_ZSTD_compressBound(n)) : uint32_t(fourmc_LZ4_compressBound(int(n))); }
+static int bs_bad_codec(const char* who, int codec)
+{ snprintf(g_err, sizeof g_err, "%s: codec %d is none of FOURMC_CODEC_*", who, codec); return FOURMC_EINVAL; }
+
+// MAX_INPUT_SIZE of BlockCompressorStream as the codecs construct it: the buffer less the overhead (Lz4Codec.java:102-103)
+uint32_t fourmc_gpu_bstream_max_input(int codec)
+{
+    const int zstd = bs_family(codec);
+    if (zstd < 0) return 0;
+    return FOURMC_BLOCKSIZE - (bs_block_bound(zstd, FOURMC_BLOCKSIZE) - FOURMC_BLOCKSIZE);
+}
+
+uint64_t fourmc_gpu_bstream_bound(uint64_t src_bytes, int codec, uint32_t group_bytes)
+{
+    const int zstd = bs_family(codec);
+    if (zstd < 0) return 0;
+    const uint32_t M = fourmc_gpu_bstream_max_input(codec), G = group_bytes ? group_bytes : M;
+    if (G > M) return 0;
+    if (!src_bytes) return 4;
+    const uint64_t full = src_bytes / G, per = 8ull + bs_block_bound(zstd, G);
+    const uint32_t rest = uint32_t(src_bytes % G);
+    if (full > (~0ull - 2 * per) / per) return ~0ull;
+    return full * per + (rest ? 8ull + bs_block_bound(zstd, rest) : 0);
+}
+
+// Pieces of at most kBsPiece groups: descriptors, the raw codec call into the staging slots, the scan (its 64-bit carry lives on the
+// device, in the summary) and the pack; one read-back of the length and the bad results at the end.
+constexpr uint32_t kBsPiece = 512;                  // the file API's batch
+int fourmc_gpu_bstream_compress(const void* d_src, uint64_t src_bytes, void* d_image, uint64_t image_cap, uint64_t* image_bytes,
+                                int codec, int level, uint32_t group_bytes, void* stream)
+{
+    const int zstd = bs_family(codec);
+    if (zstd < 0) return bs_bad_codec("bstream_compress", codec);
+    if (!image_bytes || !d_image || (src_bytes && !d_src)) { snprintf(g_err, sizeof g_err, "bstream_compress: null pointer"); return FOURMC_EINVAL; }
+    const uint32_t M = fourmc_gpu_bstream_max_input(codec), G = group_bytes ? group_bytes : M;
+    if (G > M) { snprintf(g_err, sizeof g_err, "bstream_compress: group_bytes %u above the %u a chunk may hold", group_bytes, M); return FOURMC_EINVAL; }
+    const uint64_t need = fourmc_gpu_bstream_bound(src_bytes, codec, group_bytes);
+    if (image_cap < need) {
+        snprintf(g_err, sizeof g_err, "bstream_compress: capacity %llu below the bound %llu", (unsigned long long)image_cap, (unsigned long long)need);
+        return FOURMC_EINVAL;
+    }
+    if (zstd && !fourmc_zstd_enc_level_ok(level)) { snprintf(g_err, sizeof g_err, "ZSTD level %d not on the device (levels 1..12 are)", level); return FOURMC_EUNSUP; }
+    if (int r = ensure_device()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!src_bytes) {                                // the stream nothing was written to: finish()'s rawlen of 0
+        HIP_TRY(hipMemsetAsync(d_image, 0, 4, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        *image_bytes = 4;
+        return FOURMC_OK;
+    }
+    const uint64_t ng = src_bytes / G + (src_bytes % G ? 1 : 0);
+    const uint32_t piece = uint32_t(ng < kBsPiece ? ng : kBsPiece);
+    const uint32_t stride = uint32_t(align256(bs_block_bound(zstd, uint32_t(src_bytes < G ? src_bytes : G))));
+    const size_t o_off = align256(sizeof(fourmc_bstream_enc_summary)), o_blk = o_off + align256(size_t(piece) * 8);
+    const size_t o_stage = o_blk + align256(size_t(piece) * sizeof(fourmc_block));
+    WsLease ws(&g_img_ws); void* w = nullptr;
+    if (int r = ws.get(s, o_stage + size_t(piece) * stride + kImagesStageSlack, &w)) return r;
+    char* base = static_cast<char*>(w);
+    auto* d_sum = reinterpret_cast<fourmc_bstream_enc_summary*>(base);
+    auto* d_off = reinterpret_cast<uint64_t*>(base + o_off);
+    auto* d_blk = reinterpret_cast<fourmc_block*>(base + o_blk);
+    void* d_stage = base + o_stage;
+    HIP_TRY(hipMemsetAsync(d_sum, 0, sizeof(fourmc_bstream_enc_summary), s));
+    for (uint64_t g0 = 0; g0 < ng; g0 += piece) {
+        const uint32_t m = uint32_t(ng - g0 < piece ? ng - g0 : piece);
+        const uint64_t src0 = g0 * G, left = src_bytes - src0, span = uint64_t(m) * G;
+        HIP_TRY(fourmc_launch_bstream_enc_desc(d_blk, src0, left < span ? left : span, G, stride, m, zstd, codec == FOURMC_CODEC_LZ4_MC, s));
+        int r;
+        switch (codec) {
+            case FOURMC_CODEC_LZ4_FAST: r = fourmc_gpu_lz4_compress_fast(d_src, d_stage, d_blk, m, s); break;
+            case FOURMC_CODEC_LZ4_MC:   r = fourmc_gpu_lz4_compress_mc(d_src, d_stage, d_blk, m, s); break;
+            case FOURMC_CODEC_LZ4_HC:   r = fourmc_gpu_lz4_compress_hc(d_src, d_stage, d_blk, m, level, s); break;
+            default:                    r = fourmc_gpu_zstd_compress(d_src, d_stage, d_blk, m, level, s); break;
+        }
+        if (r) return r;
+        HIP_TRY(fourmc_launch_bstream_enc_pack(d_image, d_blk, d_off, m, zstd, d_stage, d_sum, s));
+    }
+    fourmc_bstream_enc_summary h;
+    HIP_TRY(hipMemcpyAsync(&h, d_sum, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h.bad) { snprintf(g_err, sizeof g_err, "bstream_compress: %llu groups with a codec result outside [1, bound]", (unsigned long long)h.bad); return FOURMC_EINVAL; }
+    *image_bytes = h.image_bytes;
+    return FOURMC_OK;
+}
+
+// The decode of n streams: the single call is its n = 1 case.  Workspace (g_img_ws): the items, one summary, one first-descriptor
+// number and one status per stream, then - sized after the first read-back - the descriptors and the side table of every stream.
+// When that grows the buffer its contents are gone: the items and the summaries (the host has both) go up again.
+static int bstreams_run(const void* d_images, void* d_dst, int zstd, fourmc_bstream_item* items, uint32_t n, hipStream_t s)
+{
+    if (int r = ensure_device()) return r;
+    const uint32_t M = fourmc_gpu_bstream_max_input(zstd ? FOURMC_CODEC_ZSTD : FOURMC_CODEC_LZ4_FAST);
+    const size_t o_ws = align256(size_t(n) * sizeof(fourmc_bstream_item)), o_first = o_ws + align256(size_t(n) * sizeof(fourmc_bstream_walk));
+    const size_t o_st = o_first + align256(size_t(n) * 8), o_blk = o_st + align256(size_t(n) * sizeof(fourmc_bstream_status));
+    WsLease ws(&g_img_ws); void* w = nullptr;
+    if (int r = ws.get(s, o_blk, &w)) return r;
+    char* base = static_cast<char*>(w);
+    HIP_TRY(hipMemcpyAsync(base, items, size_t(n) * sizeof(fourmc_bstream_item), hipMemcpyHostToDevice, s));
+    HIP_TRY(fourmc_launch_bstream_walk(d_images, reinterpret_cast<fourmc_bstream_item*>(base), n, M,
+                                       reinterpret_cast<fourmc_bstream_walk*>(base + o_ws), nullptr, nullptr, nullptr, s));
+    std::vector<fourmc_bstream_walk> sums(n);
+    HIP_TRY(hipMemcpyAsync(sums.data(), base + o_ws, size_t(n) * sizeof(fourmc_bstream_walk), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<fourmc_bstream_status> back(n);
+    if (!d_dst) {                                    // the size query: the framing verdicts
+        for (uint32_t i = 0; i < n; i++) {
+            if (sums[i].chunks > 0x7FFFFFFFull) { snprintf(g_err, sizeof g_err, "bstreams_decompress: %llu chunks", (unsigned long long)sums[i].chunks); return FOURMC_EUNSUP; }
+            fourmc_bstream_status st = {};
+            st.total_bytes = sums[i].total; st.fail_offset = sums[i].fail_offset; st.groups = uint32_t(sums[i].groups);
+            st.chunks = uint32_t(sums[i].chunks); st.reason = sums[i].reason;
+            back[i] = st;
+        }
+        for (uint32_t i = 0; i < n; i++) items[i].status = back[i];
+        return FOURMC_OK;
+    }
+    std::vector<uint64_t> first(n);
+    uint64_t nb64 = 0;
+    for (uint32_t i = 0; i < n; i++) {               // each stream's slice of the one descriptor table
+        first[i] = nb64;
+        if (sums[i].total <= items[i].dst_cap) nb64 += sums[i].chunks;
+        if (nb64 > 0x7FFFFFFFull) { snprintf(g_err, sizeof g_err, "bstreams_decompress: more than 0x7FFFFFFF chunks"); return FOURMC_EUNSUP; }
+    }
+    const uint32_t nb = uint32_t(nb64);
+    const size_t o_side = o_blk + align256(size_t(nb) * sizeof(fourmc_block));
+    const size_t had = ws.cap();
+    if (int r = ws.get(s, o_side + size_t(nb) * sizeof(fourmc_bstream_side), &w)) return r;
+    base = static_cast<char*>(w);
+    if (ws.cap() != had) {
+        HIP_TRY(hipMemcpyAsync(base, items, size_t(n) * sizeof(fourmc_bstream_item), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(base + o_ws, sums.data(), size_t(n) * sizeof(fourmc_bstream_walk), hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipMemcpyAsync(base + o_first, first.data(), size_t(n) * 8, hipMemcpyHostToDevice, s));
+    auto* d_items = reinterpret_cast<fourmc_bstream_item*>(base);
+    auto* d_ws = reinterpret_cast<fourmc_bstream_walk*>(base + o_ws);
+    auto* d_first = reinterpret_cast<uint64_t*>(base + o_first);
+    auto* d_blk = reinterpret_cast<fourmc_block*>(base + o_blk);
+    auto* d_side = reinterpret_cast<fourmc_bstream_side*>(base + o_side);
+    if (nb) {
+        HIP_TRY(fourmc_launch_bstream_walk(d_images, d_items, n, M, d_ws, d_first, d_blk, d_side, s));
+        if (int r = zstd ? fourmc_gpu_zstd_decompress(d_images, d_dst, d_blk, nb, s) : fourmc_gpu_lz4_decompress(d_images, d_dst, d_blk, nb, s)) return r;
+    }
+    HIP_TRY(fourmc_launch_bstream_fold(d_items, n, d_ws, d_first, d_blk, d_side, reinterpret_cast<fourmc_bstream_status*>(base + o_st), s));
+    HIP_TRY(hipMemcpyAsync(back.data(), base + o_st, size_t(n) * sizeof(fourmc_bstream_status), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint32_t i = 0; i < n; i++) items[i].status = back[i];
+    return FOURMC_OK;
+}
+
+int fourmc_gpu_bstream_decompress(const void* d_image, uint64_t image_bytes, void* d_dst, uint64_t dst_cap, int codec,
+                                  fourmc_bstream_status* status, void* stream)
+{
+    const int zstd = bs_family(codec);
+    if (zstd < 0) return bs_bad_codec("bstream_decompress", codec);
+    if (!status || (image_bytes && !d_image)) { snprintf(g_err, sizeof g_err, "bstream_decompress: null pointer"); return FOURMC_EINVAL; }
+    fourmc_bstream_item it = {};
+    it.image_bytes = image_bytes; it.dst_cap = d_dst ? dst_cap : 0;
+    if (int r = bstreams_run(d_image, d_dst, zstd, &it, 1, static_cast<hipStream_t>(stream))) return r;
+    *status = it.status;
+    return FOURMC_OK;
+}
+
+int fourmc_gpu_bstreams_decompress(const void* d_images, uint64_t images_bytes, void* d_dst, uint64_t dst_bytes, int codec,
+                                   fourmc_bstream_item* items, uint32_t n, void* stream)
+{
+    const int zstd = bs_family(codec);
+    if (zstd < 0) return bs_bad_codec("bstreams_decompress", codec);
+    if (n == 0) return FOURMC_OK;
+    if (!items) { snprintf(g_err, sizeof g_err, "bstreams_decompress: null items"); return FOURMC_EINVAL; }
+    {
+        std::vector<std::pair<uint64_t, uint64_t>> d;
+        if (d_dst) d.reserve(n);
+        for (uint32_t i = 0; i < n; i++) {
+            const fourmc_bstream_item& it = items[i];
+            if (it.image_bytes && !d_images) { snprintf(g_err, sizeof g_err, "bstreams_decompress: null images"); return FOURMC_EINVAL; }
+            if (it.image_off > images_bytes || it.image_bytes > images_bytes - it.image_off) {
+                snprintf(g_err, sizeof g_err, "bstreams_decompress: stream %u lies beyond the %llu bytes of streams", i, (unsigned long long)images_bytes);
+                return FOURMC_EINVAL;
+            }
+            if (!d_dst) continue;                             // the size query looks at no destination
+            if (it.dst_off > dst_bytes || it.dst_cap > dst_bytes - it.dst_off) {
+                snprintf(g_err, sizeof g_err, "bstreams_decompress: the output region of stream %u lies beyond the %llu bytes of the destination", i,
+                         (unsigned long long)dst_bytes);
+                return FOURMC_EINVAL;
+            }
+            if (it.dst_cap) d.emplace_back(it.dst_off, it.dst_off + it.dst_cap);
+        }
+        std::sort(d.begin(), d.end());
+        for (size_t i = 1; i < d.size(); i++)
+            if (d[i].first < d[i - 1].second) {
+                snprintf(g_err, sizeof g_err, "bstreams_decompress: output regions overlap at %llu", (unsigned long long)d[i].first);
+                return FOURMC_EINVAL;
+            }
+    }
+    return bstreams_run(d_images, d_dst, zstd, items, n, static_cast<hipStream_t>(stream));
+}
+
+const char* fourmc_gpu_bstream_reason_text(int reason)
+{
+    switch (reason) {
+        case FOURMC_BS_OK:              return "";
+        case FOURMC_BS_BAD_RAWLEN:      return "Block stream : group length beyond 2 GiB";
+        case FOURMC_BS_CLEN_UNREADABLE: return "Block stream : cannot read next chunk length";
+        case FOURMC_BS_BAD_CLEN:        return "Block stream : chunk length zero or beyond 4MB limit";
+        case FOURMC_BS_DATA_UNREADABLE: return "Block stream : cannot read chunk data";
+        case FOURMC_BS_CORRUPT:         return "Block stream : decoding failed, corrupted chunk";
+        case FOURMC_BS_SHAPE:           return "Block stream : chunk shorter than the writer's shape allows";
+        case FOURMC_BS_DST_SMALL:       return "Destination buffer too small";
+        default:                        return "unknown";
+    }
+}
+
 // ------------------------------------------------------------------------ random access into images (image.hip)
 // Workspace of the three calls (g_img_ws): the index summary, then - sized after its read-back - the entries and what the call
 // needs besides.  A buffer that grows loses its contents: everything after the first read-back is recomputed on the device.

@@ -26,18 +26,15 @@
 #include "fourmc_gpu.h"
 #include "kernels.h"
 #include "devcopy.h"
+#include "devframe.h"       // be32 / put_be32, scan_add / wave_total
 
 namespace {
 
 constexpr uint32_t P1 = 2654435761u, P2 = 2246822519u, P3 = 3266489917u, P4 = 668265263u, P5 = 374761393u;
 constexpr uint32_t kBlock = FOURMC_BLOCKSIZE;
 
-__device__ __forceinline__ uint32_t be32(const uint8_t* p)
-{ return (uint32_t(p[0]) << 24) | (uint32_t(p[1]) << 16) | (uint32_t(p[2]) << 8) | uint32_t(p[3]); }
 __device__ __forceinline__ uint32_t le32(const uint8_t* p)
 { return uint32_t(p[0]) | (uint32_t(p[1]) << 8) | (uint32_t(p[2]) << 16) | (uint32_t(p[3]) << 24); }
-__device__ __forceinline__ void put_be32(uint8_t* p, uint32_t v)
-{ p[0] = uint8_t(v >> 24); p[1] = uint8_t(v >> 16); p[2] = uint8_t(v >> 8); p[3] = uint8_t(v); }
 __device__ __forceinline__ uint32_t rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 
 // XXH32 on one lane (xxhash.c:392-415): framing bytes (a footer, a file header) and, on the error path only, the payload whose
@@ -60,19 +57,6 @@ __device__ uint32_t xxh32_lane(const uint8_t* p, uint64_t len, uint32_t seed)
     h ^= h >> 15; h *= P2; h ^= h >> 13; h *= P3; h ^= h >> 16;
     return h;
 }
-
-// wave64 inclusive prefix sum: 4 row_shr steps scan each row of 16 lanes, row_bcast15 / row_bcast31 carry the row totals
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ uint32_t dpp0(uint32_t v)
-{ return uint32_t(__builtin_amdgcn_update_dpp(0, int(v), CTRL, ROWMASK, 0xf, false)); }
-__device__ __forceinline__ uint32_t scan_add(uint32_t v)
-{
-    v += dpp0<0x111, 0xf>(v); v += dpp0<0x112, 0xf>(v); v += dpp0<0x114, 0xf>(v); v += dpp0<0x118, 0xf>(v);
-    v += dpp0<0x142, 0xa>(v);
-    v += dpp0<0x143, 0xc>(v);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_total(uint32_t incl) { return uint32_t(__builtin_amdgcn_readlane(int(incl), 63)); }
 
 // ------------------------------------------------------------------------------------------------------------- encode
 // block b of an item's n: src0 + b * 4 MiB of the source, dst0 + b * 4 MiB of the staging, src_len = what is left of src_bytes, at

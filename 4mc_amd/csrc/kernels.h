@@ -357,6 +357,35 @@ hipError_t fourmc_launch_lines_batch_finish(const fourmc_lines_span* d_spans, ui
 hipError_t fourmc_launch_lines_batch_write(const fourmc_lines_span* d_spans, const uint64_t* d_first_tile, uint32_t ns,
                                            const uint64_t* d_cnt, uint64_t ntiles, uint64_t longest, uint32_t max_line_len,
                                            const fourmc_records_state* d_st, hipStream_t s);
+/* Hadoop block streams (bstream.hip, fourmc_gpu_bstream_*): what run 1 of the walk leaves per stream for the engine's read-back */
+typedef struct fourmc_bstream_walk {    /* 40 bytes */
+    uint64_t chunks;        /* chunks of the well-formed groups, in file order, before the walk stopped */
+    uint64_t groups;        /* well-formed groups */
+    uint64_t total;         /* sum of their rawlens */
+    uint64_t fail_offset;   /* stream offset of the field that ended the walk (image_bytes when it ended cleanly) */
+    int32_t  reason;        /* FOURMC_BS_*: the framing verdict */
+    uint32_t pad;
+} fourmc_bstream_walk;
+/* the side table of run 2, one entry per descriptor: where the chunk's header lies in its stream, and the group it belongs to */
+typedef struct fourmc_bstream_side { uint64_t at, group; } fourmc_bstream_side;
+/* the encode's running state on the device: the stream offset behind the last group packed, and the bad codec results so far */
+typedef struct fourmc_bstream_enc_summary { uint64_t image_bytes, bad; } fourmc_bstream_enc_summary;
+/* d_desc NULL: run 1, d_ws[i] = stream i's summary; else run 2: the descriptors (offsets relative to d_images and to the items'
+ * common destination) and side entries of the summaries d_ws holds, stream i's at d_first[i]; none for an item whose total exceeds
+ * its dst_cap.  max_input: M of the codec family */
+hipError_t fourmc_launch_bstream_walk(const void* d_images, const fourmc_bstream_item* d_items, uint32_t n, uint32_t max_input,
+                                      fourmc_bstream_walk* d_ws, const uint64_t* d_first, fourmc_block* d_desc,
+                                      fourmc_bstream_side* d_side, hipStream_t s);
+hipError_t fourmc_launch_bstream_fold(const fourmc_bstream_item* d_items, uint32_t n, const fourmc_bstream_walk* d_ws,
+                                      const uint64_t* d_first, const fourmc_block* d_desc, const fourmc_bstream_side* d_side,
+                                      fourmc_bstream_status* d_status, hipStream_t s);
+/* one staging piece of n groups: group b reads src0 + b * group_bytes of the source (src_bytes: the piece's bytes) and writes slot
+ * b * stride of the staging; nolimit: dst_cap = 0xFFFFFFFF (LZ4_compressMC) instead of the bound */
+hipError_t fourmc_launch_bstream_enc_desc(fourmc_block* d_blocks, uint64_t src0, uint64_t src_bytes, uint32_t group_bytes,
+                                          uint32_t stride, uint32_t n, int zstd, int nolimit, hipStream_t s);
+/* after the codec: the scan of 8 + csize from d_sum->image_bytes into d_off[0, n) and back into *d_sum, then the pack */
+hipError_t fourmc_launch_bstream_enc_pack(void* d_image, fourmc_block* d_blocks, uint64_t* d_off, uint32_t n, int zstd,
+                                          const void* d_staging, fourmc_bstream_enc_summary* d_sum, hipStream_t s);
 #ifdef FOURMC_RESEARCH      /* the research side build exports these two: tools/zstd_timing.py and tools/k7x_prof.py size their read-backs with them */
 #pragma GCC visibility push(default)
 #endif
@@ -388,6 +417,14 @@ static inline __host__ __device__ int32_t fourmc_image_exit_code(int32_t reason)
         case FOURMC_IMG_FOOTER_UNREADABLE: case FOURMC_IMG_DST_SMALL: return 1;
         default: return 4;
     }
+}
+
+// The codec's bound for n <= 4 MiB bytes of input, on the device: LZ4_compressBound (lz4.h:212) or ZSTD_compressBound (zstd.h:206).
+// The engine's own arithmetic (M, fourmc_gpu_bstream_bound) goes through fourmc_LZ4_compressBound / fourmc_ZSTD_compressBound.
+static inline __host__ __device__ uint32_t fourmc_bstream_block_bound(int zstd, uint32_t n)
+{
+    if (zstd) return n + (n >> 8) + (n < (128u << 10) ? ((128u << 10) - n) >> 11 : 0u);
+    return n + n / 255u + 16u;
 }
 
 #ifdef __HIPCC__

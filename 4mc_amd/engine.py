@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .binding import (BLOCK_DTYPE, CODEC_LZ4_FAST, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines, ImageRef, ImageSplitItem,
+from .binding import (BLOCK_DTYPE, BSTREAM_REASONS, CODEC_LZ4_FAST, BstreamItem, BstreamStatus, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines, ImageRef, ImageSplitItem,
                       ImagesSlice, ImagesSplitItem,
                       ImageRange, ImageRecords, ImageSlice, ImageStatus, check, lib)
 
@@ -191,6 +191,66 @@ def decompress_images(d_images, items, d_dst, magic=MAGIC_4MC, images_bytes=None
         res["message"] = lib().fourmc_gpu_image_reason_text(st.reason).decode()
         out.append(res)
     return out
+
+
+def bstream_max_input(codec=CODEC_LZ4_FAST):
+    """M, the most input bytes one chunk of a Hadoop block stream holds (fourmc_gpu_bstream_max_input); 0 for an unknown codec."""
+    return int(lib().fourmc_gpu_bstream_max_input(int(codec)))
+
+
+def bstream_bound(src_bytes, codec=CODEC_LZ4_FAST, group_bytes=0):
+    """Worst-case length of the block stream compress_bstream writes for src_bytes of input (fourmc_gpu_bstream_bound)."""
+    return int(lib().fourmc_gpu_bstream_bound(int(src_bytes), int(codec), int(group_bytes)))
+
+
+def compress_bstream(d_src, d_image, codec=CODEC_LZ4_FAST, level=0, group_bytes=0, stream=None):
+    """d_src as the block stream one of the reference's eight raw codecs writes (fourmc_gpu_bstream_compress): groups of group_bytes
+    of input (0: bstream_max_input(codec)), one chunk each.  (codec, level) as bstream_codec(ext) gives them.  d_image holds at
+    least bstream_bound(d_src.numel(), codec, group_bytes) bytes.  Returns the stream's length."""
+    out = C.c_uint64(0)
+    check(lib().fourmc_gpu_bstream_compress(_dev_ptr(d_src, "compress_bstream d_src"), d_src.numel(), _dev_ptr(d_image, "compress_bstream d_image"),
+                                            d_image.numel(), C.byref(out), int(codec), int(level), int(group_bytes), _stream_ptr(stream)),
+          "fourmc_gpu_bstream_compress")
+    return int(out.value)
+
+
+def _bstream_dict(st):
+    res = {name: int(getattr(st, name)) for name, _ in BstreamStatus._fields_ if name != "pad"}
+    res["name"] = BSTREAM_REASONS[st.reason] if 0 <= st.reason < len(BSTREAM_REASONS) else "?"
+    res["message"] = lib().fourmc_gpu_bstream_reason_text(st.reason).decode()
+    return res
+
+
+def decompress_bstream(d_image, d_dst, codec=CODEC_LZ4_FAST, image_bytes=None, stream=None):
+    """Decode the block stream d_image[:image_bytes] (default: the whole tensor) into d_dst; d_dst None: the size query.  `codec`
+    selects the family (any LZ4 selector, or CODEC_ZSTD).  Returns the status as a dict: decoded_bytes, total_bytes, fail_offset,
+    groups, chunks, reason (a FOURMC_BS_* number), "name" (its entry of BSTREAM_REASONS) and "message"."""
+    n = _image_len(d_image, image_bytes, "decompress_bstream")
+    st = BstreamStatus()
+    dst, cap = (0, 0) if d_dst is None else (_dev_ptr(d_dst, "decompress_bstream d_dst"), d_dst.numel())
+    if d_dst is not None and dst == 0:          # an empty tensor has no address, and to the library NULL is the size query
+        raise EngineError("decompress_bstream: d_dst is empty (None asks for the size)")
+    check(lib().fourmc_gpu_bstream_decompress(_dev_ptr(d_image, "decompress_bstream d_image"), n, dst, cap, int(codec), C.byref(st),
+                                              _stream_ptr(stream)), "fourmc_gpu_bstream_decompress")
+    return _bstream_dict(st)
+
+
+def decompress_bstreams(d_images, items, d_dst, codec=CODEC_LZ4_FAST, images_bytes=None, stream=None):
+    """Decode many block streams of one buffer with one call (fourmc_gpu_bstreams_decompress).  `items` is a sequence of
+    (image_off, image_bytes, dst_off, dst_cap); d_dst None: the size query.  Returns one status dict per item, each what
+    decompress_bstream returns for that stream alone."""
+    ptr = _dev_ptr(d_images, "decompress_bstreams d_images")
+    n = _image_len(d_images, images_bytes, "decompress_bstreams")
+    dst, cap = (0, 0) if d_dst is None else (_dev_ptr(d_dst, "decompress_bstreams d_dst"), d_dst.numel())
+    if d_dst is not None and dst == 0:
+        raise EngineError("decompress_bstreams: d_dst is empty (None asks for the sizes)")
+    q = [tuple(int(v) for v in it) for it in items]
+    arr = (BstreamItem * max(len(q), 1))()
+    for i, (io, ib, do, dc) in enumerate(q):
+        arr[i].image_off, arr[i].image_bytes, arr[i].dst_off, arr[i].dst_cap = io, ib, do, dc
+    check(lib().fourmc_gpu_bstreams_decompress(ptr, n, dst, cap, int(codec), C.cast(arr, C.c_void_p), len(q), _stream_ptr(stream)),
+          "fourmc_gpu_bstreams_decompress")
+    return [_bstream_dict(arr[i].status) for i in range(len(q))]
 
 
 def _image_len(d_image, image_bytes, what):

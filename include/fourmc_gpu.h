@@ -592,6 +592,116 @@ typedef struct fourmc_images_slice { uint32_t image, pad; fourmc_image_slice s; 
 int fourmc_gpu_images_align_slices(const void* d_images, uint64_t images_bytes, const fourmc_image_ref* images /*host*/,
                                    uint32_t nimages, fourmc_images_slice* slices /*host*/, uint32_t n, void* stream);
 
+/* ---- Hadoop block streams in device memory: the files of Lz4Codec / ZstdCodec and their six siblings ----------------------------
+ * The reference ships eight raw block codecs beside the .4mc / .4mz container: Lz4Codec, Lz4MediumCodec, Lz4HighCodec, Lz4UltraCodec,
+ * ZstdCodec, ZstdMediumCodec, ZstdHighCodec, ZstdUltraCodec (extensions .lz4_fast .lz4_mc .lz4_hc .lz4_uc .zstd_fast .zstd_mc
+ * .zstd_hc .zstd_uc).  A job that names one as its output or intermediate codec writes part files in the framing of Hadoop's
+ * BlockCompressorStream (Lz4Codec.java:95-104): no header, no checksum, no index.  These calls write and read that framing.
+ * Provenance.  BlockCompressorStream / BlockDecompressorStream are Hadoop's classes, not the reference's; their source was not at
+ *   hand and no JVM wrote or read a file for this code.  The rules below are written from knowledge of those classes and from the
+ *   reference's Lz4Codec.java, Lz4Compressor.java, jniCompressor.c, jniZstdCompressor.c and their twins.  They are the contract
+ *   here, by reading, as fourmc_gpu_image_read_lines' rule is.
+ * Format.  All integers are big-endian u32 at any byte offset.
+ *     stream := group* [ BE32(0) ]
+ *     group  := BE32(rawlen) chunk+          rawlen in 1 .. 0x7FFFFFFF
+ *     chunk  := BE32(clen) payload[clen]     payload = one raw LZ4 block / one zstd frame
+ * M, the most input bytes in one chunk: 4 MiB - (compressBound(4 MiB) - 4 MiB), the codec's buffer less the overhead the codec
+ *   hands to BlockCompressorStream (Lz4Codec.java:102-103).  fourmc_gpu_bstream_max_input derives it from fourmc_LZ4_compressBound
+ *   / fourmc_ZSTD_compressBound: 4177840 for the LZ4 codecs, 4177920 for the zstd codecs.
+ * What a writer produces.  Under every pattern of write() calls a group of rawlen R has exactly ceil(R / M) chunks, every chunk but
+ *   the last decoding to M bytes and the last to the rest: small writes accumulate until the next one would pass M, then ONE group
+ *   of ONE chunk goes out; a single write longer than M goes out as one group with chunks of M.  A stream nothing was written to is
+ *   the four bytes 00 00 00 00, and a stream whose last write took the long-write path ends with a trailing BE32(0).  Chunks are
+ *   compressed with unlimited output (LZ4_compress, LZ4_compressMC, LZ4_compressHC2(level), ZSTD_compress(level), capacity = the
+ *   bound): there is no stored-raw fallback and no checksum.
+ * Reader rule.  At a group boundary with fewer than 4 bytes left (0, or 1 - 3: Hadoop's reader swallows the EOF there) the stream
+ *   ends cleanly; rawlen == 0 ends it cleanly whatever follows; rawlen > 0x7FFFFFFF is FOURMC_BS_BAD_RAWLEN.  Inside a group: fewer
+ *   than 4 bytes where a clen is due is FOURMC_BS_CLEN_UNREADABLE; clen == 0 or clen > 4 MiB is FOURMC_BS_BAD_CLEN (Lz4Decompressor
+ *   would cut such an input at its 4 MiB direct buffer); a clen beyond the bytes left is FOURMC_BS_DATA_UNREADABLE.
+ * The walk assumes the writer's shape.  Chunk j of a group is expected to decode to min(M, R - j M) bytes, so finding the chunks is
+ *   pure header chasing, independent of the decode, and every chunk decodes straight to its final place.  The decode then proves
+ *   the assumption: each chunk is decoded with dst_cap = its expected size and must return exactly that.
+ * Not reproduced.  (a) Foreign chunkings: a stream chunked another way, which BlockDecompressorStream would accept but these
+ *   codecs never write, gets FOURMC_BS_SHAPE (or FOURMC_BS_CORRUPT when a chunk holds more than its expected size), never wrong
+ *   bytes.  (b) A group cut short by a framing error is not decoded at all, though Hadoop's reader would hand out its leading chunks
+ *   before it fails: total_bytes counts whole groups only and nothing is ever written beyond it.  (c) Multi-chunk groups on the
+ *   encode side: bstream_compress never writes a piece longer than M.  (d) A many-streams encode, streaming writer and reader
+ *   forms, the lines of a block stream, and .zst files (the libzstd pass-through of the file API) are not in this group. */
+enum {
+    FOURMC_BS_OK              = 0,
+    FOURMC_BS_BAD_RAWLEN      = 1,   /* a group's rawlen has its top bit set                                          */
+    FOURMC_BS_CLEN_UNREADABLE = 2,   /* fewer than 4 bytes left where a chunk's length is due                         */
+    FOURMC_BS_BAD_CLEN        = 3,   /* a chunk length of 0 or above 4 MiB                                            */
+    FOURMC_BS_DATA_UNREADABLE = 4,   /* a chunk length beyond the bytes left                                          */
+    FOURMC_BS_CORRUPT         = 5,   /* the codec returned < 0 for a chunk (a chunk holding more than its expected size included) */
+    FOURMC_BS_SHAPE           = 6,   /* a chunk decoded cleanly to fewer bytes than the writer's shape gives it      */
+    FOURMC_BS_DST_SMALL       = 7    /* total_bytes > dst_cap: nothing decoded                                       */
+};
+typedef struct fourmc_bstream_status {   /* 40 bytes */
+    uint64_t decoded_bytes;   /* the sum of the expected sizes of the chunks before the first failure: d_dst[0, decoded_bytes) is good */
+    uint64_t total_bytes;     /* the sum of the rawlens of the well-formed groups (the size query's answer)                           */
+    uint64_t fail_offset;     /* stream offset of the rawlen / clen field or chunk header that ended decoding; image_bytes if none     */
+    uint32_t groups, chunks;  /* well-formed groups and their chunks; when a chunk failed: the groups and chunks wholly in front of it */
+    int32_t  reason;          /* FOURMC_BS_*                                                                                          */
+    uint32_t pad;             /* 0                                                                                                    */
+} fourmc_bstream_status;
+/* M for a FOURMC_CODEC_* selector, 0 for an unknown one.  Host arithmetic: no device is looked for. */
+uint32_t fourmc_gpu_bstream_max_input(int codec);
+/* The exact worst case of bstream_compress: 4 for an empty source, else the sum over the groups of 8 + compressBound(group length).
+ * group_bytes 0 means M.  0 for an unknown codec or a group_bytes above M.  Host arithmetic. */
+uint64_t fourmc_gpu_bstream_bound(uint64_t src_bytes, int codec, uint32_t group_bytes);
+/* d_src[0, src_bytes) -> a block stream at d_image.  The source is cut at every group_bytes of input (0: M), the last piece short;
+ * piece g becomes BE32(len_g) BE32(csize_g) payload_g, the payload what the raw codec call writes for the piece with dst_cap =
+ * compressBound(len_g): fourmc_gpu_lz4_compress_fast, _mc (with its no-limit capacity), _hc(level), fourmc_gpu_zstd_compress(level).
+ * For the exact encoders these are the reference's bytes; FOURMC_LZ4_ENCODE=parallel applies exactly as it does to the raw call.
+ * The levels of the eight codec classes, from their *Compressor.java: LZ4 fast, MC, HC 4 (High), HC 8 (Ultra); zstd 1, 3, 6, 12.
+ * Correspondence.  This is byte for byte what BlockCompressorStream writes when each write() carries one piece and a piece is longer
+ *   than M / 2 (two never fit one group).  For smaller writes of w bytes each it is what the stream writes when group_bytes =
+ *   floor(M / w) * w: the writes that accumulate into one group.  An empty source writes 00 00 00 00.  Pieces longer than M - the
+ *   multi-chunk groups of a long write() - are never written.
+ * Arguments, checked on the host before any device is looked for, the codec first: an unknown codec, a NULL d_image or image_bytes,
+ *   a NULL d_src with a nonzero src_bytes, a group_bytes above M, image_cap < fourmc_gpu_bstream_bound(src_bytes, codec,
+ *   group_bytes): FOURMC_EINVAL.  A zstd level outside the device's 1 .. 12: FOURMC_EUNSUP.  A codec result <= 0 or above its bound
+ *   fails the call with FOURMC_EINVAL, the guard image_compress has.
+ * Cost.  One synchronization of `stream` (the length and the count of bad results together).  Staging: one slot of
+ *   compressBound(group_bytes) rounded up to 256 bytes per group in the engine's image workspace, for at most 512 groups at a time
+ *   (the file API's batch): larger inputs are encoded in pieces of 512 groups, the 64-bit offset carried on the device. */
+int fourmc_gpu_bstream_compress(const void* d_src, uint64_t src_bytes, void* d_image, uint64_t image_cap, uint64_t* image_bytes,
+                                int codec, int level, uint32_t group_bytes, void* stream);
+/* d_image[0, image_bytes) -> decoded bytes at d_dst, by the reader rule above.  `codec` only selects the family: any LZ4 selector
+ * means LZ4, FOURMC_CODEC_ZSTD means zstd.  d_dst NULL: the size query (parse only: total_bytes, groups, chunks and the framing
+ * verdict).  total_bytes > dst_cap: FOURMC_BS_DST_SMALL, nothing written; it wins over every other verdict.  Otherwise the first
+ * failing chunk in file order wins over the framing verdict (the walk lists only chunks in front of the point where it stopped).
+ * The call never writes outside [d_dst, d_dst + total_bytes); bytes from decoded_bytes on are unspecified.  The decoders may read up
+ * to 64 bytes past a payload: the caller keeps that slack behind the image, as for .4mc.  The chunks go through
+ * fourmc_gpu_lz4_decompress / fourmc_gpu_zstd_decompress, so FOURMC_DECODE, FOURMC_ZDECODE and the launch-splitting limits apply
+ * unchanged.  FOURMC_EINVAL (before any device is looked for): an unknown codec, a NULL status, a NULL d_image with a nonzero
+ * image_bytes.  Synchronizations of `stream`: two (the chunk count that sizes the descriptor table, then the status); the size
+ * query takes one.  The files are not splittable, so one stream is one serial walk on one lane: the parallelism comes from many
+ * chunks and many streams per launch, and this call is the n = 1 case of the next one, run by the same host function. */
+int fourmc_gpu_bstream_decompress(const void* d_image, uint64_t image_bytes, void* d_dst, uint64_t dst_cap, int codec,
+                                  fourmc_bstream_status* status, void* stream);
+/* Many streams of ONE device buffer with one call, their outputs in ONE device buffer.
+ * The one rule.  items[i].status and d_dst[dst_off, dst_off + decoded_bytes) equal what the single call gives for d_images +
+ *   image_off, image_bytes, d_dst + dst_off, dst_cap and the same codec.  A damaged stream changes nothing for its neighbours; two
+ *   items may name the same stream bytes; d_dst NULL is the size query of every item (dst_off, dst_cap and dst_bytes are ignored).
+ * Arguments, as fourmc_gpu_images_decompress checks them, on the host before any device is looked for and with `items` untouched
+ *   on every failure, the codec first: an unknown codec, items NULL with n > 0, d_images NULL with a nonzero image_bytes, a stream
+ *   outside [0, images_bytes), with d_dst an output region outside [0, dst_bytes) or two output regions of nonzero dst_cap that
+ *   overlap: FOURMC_EINVAL.  n == 0: FOURMC_OK.  More than 0x7FFFFFFF chunks in all: FOURMC_EUNSUP.  No device: FOURMC_ENODEV.
+ * Work, whatever n is: the walk twice with one wave per stream (the first run leaves each stream's summary, which come back in one
+ *   read-back; the host's prefix sum over the chunk counts gives each stream its slice of ONE descriptor table, which the second
+ *   run fills), one block decode over all chunks of all streams, one fold with one wave per stream; two synchronizations. */
+typedef struct fourmc_bstream_item {     /* 72 bytes */
+    uint64_t image_off, image_bytes;     /* in : the stream is d_images[image_off, image_off + image_bytes)          */
+    uint64_t dst_off, dst_cap;           /* in : its output region is d_dst[dst_off, dst_off + dst_cap)              */
+    fourmc_bstream_status status;        /* out                                                                       */
+} fourmc_bstream_item;
+int fourmc_gpu_bstreams_decompress(const void* d_images, uint64_t images_bytes, void* d_dst, uint64_t dst_bytes, int codec,
+                                   fourmc_bstream_item* items /*host*/, uint32_t n, void* stream);
+/* a short fixed text for a FOURMC_BS_* verdict ("" for FOURMC_BS_OK).  The words are this library's: no CLI reads these files. */
+const char* fourmc_gpu_bstream_reason_text(int reason);
+
 /* ---- host-buffer conveniences with the reference's per-block signatures ------------------- */
 /* These stage one block through HBM (H2D, one launch, D2H).  They exist so the JNI entry points
  * keep their exact one-call-one-block contract (SURVEY.md §8(b) "Batching constraint").        */
