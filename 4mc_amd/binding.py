@@ -57,6 +57,16 @@ class BstreamItem(C.Structure):
 
 
 assert C.sizeof(BstreamStatus) == 40 and C.sizeof(BstreamItem) == 72
+# struct fourmc_bstream_enc_item (include/fourmc_gpu.h: block streams from a job's write() calls)
+class BstreamEncItem(C.Structure):
+    _fields_ = [("src_off", C.c_uint64), ("src_bytes", C.c_uint64), ("image_off", C.c_uint64), ("image_cap", C.c_uint64),
+                ("writes_off", C.c_uint64), ("n_writes", C.c_uint64), ("write_bytes", C.c_uint32), ("reason", C.c_int32),
+                ("image_bytes", C.c_uint64), ("groups", C.c_uint32), ("chunks", C.c_uint32)]
+
+
+assert C.sizeof(BstreamEncItem) == 72
+# FOURMC_BSW_*: the verdict of compress_bstreams on one stream, by number
+BSTREAM_WRITE_REASONS = ("OK", "SUM", "WRITE", "CAP")
 # FOURMC_BS_*: the verdict of a block-stream decode, by number
 BSTREAM_REASONS = ("OK", "BAD_RAWLEN", "CLEN_UNREADABLE", "BAD_CLEN", "DATA_UNREADABLE", "CORRUPT", "SHAPE", "DST_SMALL")
 # the extensions of the reference's eight block codecs -> (codec, level) for compress_bstream (Lz4Codec.java:162 and its siblings;
@@ -195,6 +205,8 @@ _GPU_API = {
     "fourmc_gpu_bstream_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_bstreams_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_bstream_reason_text": (C.c_char_p, [C.c_int]),
+    "fourmc_gpu_bstreams_compress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "fourmc_gpu_bstream_writes_bound": (C.c_uint64, [C.c_uint64, C.c_int]),
     "fourmc_gpu_image_parse_stats": (None, [C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_decode_blocks": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),

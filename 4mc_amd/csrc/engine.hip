@@ -1199,6 +1199,173 @@ int fourmc_gpu_bstream_compress(const void* d_src, uint64_t src_bytes, void* d_i
     return FOURMC_OK;
 }
 
+// ---- block streams from write() sizes -------------------------------------------------------------------------------------------
+// The most chunks and written groups any schedule over S bytes has (include/fourmc_gpu.h has the argument)
+static uint64_t bsw_max_chunks(uint64_t S, uint32_t M) { const uint64_t r = S % (uint64_t(M) + 2); return 3 * (S / (uint64_t(M) + 2)) + (r < 2 ? r : 2); }
+static uint64_t bsw_max_groups(uint64_t S, uint32_t M) { return 2 * (S / (uint64_t(M) + 1)) + (S % (uint64_t(M) + 1) ? 1 : 0); }
+
+uint64_t fourmc_gpu_bstream_writes_bound(uint64_t src_bytes, int codec)
+{
+    const int zstd = bs_family(codec);
+    if (zstd < 0) return 0;
+    if (!src_bytes) return 4;
+    const uint32_t M = fourmc_gpu_bstream_max_input(codec);
+    const uint64_t C = bsw_max_chunks(src_bytes, M), G = bsw_max_groups(src_bytes, M);
+    const uint64_t over = zstd ? src_bytes / 256 + 64 * C : src_bytes / 255 + 16 * C;
+    if (src_bytes > (~0ull >> 1)) return ~0ull;
+    return src_bytes + over + 4 * C + 4 * G + 4;
+}
+
+// Chunks per round: FOURMC_BSW_ROUND, read at every call (a test sets it between two calls)
+static uint32_t bsw_round()
+{
+    const char* e = getenv("FOURMC_BSW_ROUND");
+    const long v = e && *e ? atol(e) : long(kBsPiece);
+    return uint32_t(v < 1 ? 1 : v > (1 << 20) ? (1 << 20) : v);
+}
+
+// Workspaces.  g_img_ws: the items, the first tile of every stream, the plans and the tile prefixes - what the plan computes and the
+// rounds read.  g_img_stage, sized after the plan's read-back (so that sizing it cannot move the prefixes): the slices, one carry and
+// one length per stream, the summary, the group table, and the descriptors, side entries, offsets and staging of one round.
+int fourmc_gpu_bstreams_compress(const void* d_src, uint64_t src_total, const uint32_t* d_writes, uint64_t writes_total,
+                                 void* d_images, uint64_t images_bytes, int codec, int level,
+                                 fourmc_bstream_enc_item* items, uint32_t n, void* stream)
+{
+    const int zstd = bs_family(codec);
+    if (zstd < 0) return bs_bad_codec("bstreams_compress", codec);
+    if (n == 0) return FOURMC_OK;
+    if (!items) { snprintf(g_err, sizeof g_err, "bstreams_compress: null items"); return FOURMC_EINVAL; }
+    std::vector<uint64_t> tile0(size_t(n) + 1);
+    {
+        std::vector<std::pair<uint64_t, uint64_t>> d;
+        if (d_images) d.reserve(n);
+        uint64_t tiles = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            const fourmc_bstream_enc_item& it = items[i];
+            if (it.src_bytes && !d_src) { snprintf(g_err, sizeof g_err, "bstreams_compress: null source"); return FOURMC_EINVAL; }
+            if (it.n_writes && !d_writes) { snprintf(g_err, sizeof g_err, "bstreams_compress: null write table"); return FOURMC_EINVAL; }
+            if (it.src_off > src_total || it.src_bytes > src_total - it.src_off) {
+                snprintf(g_err, sizeof g_err, "bstreams_compress: the source of stream %u lies beyond the %llu bytes of sources", i, (unsigned long long)src_total);
+                return FOURMC_EINVAL;
+            }
+            if (it.writes_off > writes_total || it.n_writes > writes_total - it.writes_off) {
+                snprintf(g_err, sizeof g_err, "bstreams_compress: the write sizes of stream %u lie beyond the %llu entries of the table", i, (unsigned long long)writes_total);
+                return FOURMC_EINVAL;
+            }
+            tile0[i] = tiles;
+            tiles += it.n_writes / 64 + (it.n_writes % 64 ? 1 : 0);
+            if (!d_images) continue;                          // the size query looks at no region
+            if (it.image_off > images_bytes || it.image_cap > images_bytes - it.image_off) {
+                snprintf(g_err, sizeof g_err, "bstreams_compress: the region of stream %u lies beyond the %llu bytes of images", i, (unsigned long long)images_bytes);
+                return FOURMC_EINVAL;
+            }
+            if (it.image_cap) d.emplace_back(it.image_off, it.image_off + it.image_cap);
+        }
+        tile0[n] = tiles;
+        std::sort(d.begin(), d.end());
+        for (size_t i = 1; i < d.size(); i++)
+            if (d[i].first < d[i - 1].second) {
+                snprintf(g_err, sizeof g_err, "bstreams_compress: image regions overlap at %llu", (unsigned long long)d[i].first);
+                return FOURMC_EINVAL;
+            }
+    }
+    if (zstd && !fourmc_zstd_enc_level_ok(level)) { snprintf(g_err, sizeof g_err, "ZSTD level %d not on the device (levels 1..12 are)", level); return FOURMC_EUNSUP; }
+    if (int r = ensure_device()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t M = fourmc_gpu_bstream_max_input(codec);
+    const uint64_t ntiles = tile0[n];
+    const size_t o_tile0 = align256(size_t(n) * sizeof(fourmc_bstream_enc_item)), o_plans = o_tile0 + align256((size_t(n) + 1) * 8);
+    const size_t o_prefix = o_plans + align256(size_t(n) * sizeof(fourmc_bsw_plan));
+    WsLease ws(&g_img_ws); void* w = nullptr;
+    if (int r = ws.get(s, o_prefix + size_t(ntiles) * 8, &w)) return r;
+    char* base = static_cast<char*>(w);
+    auto* d_items = reinterpret_cast<fourmc_bstream_enc_item*>(base);
+    auto* d_tile0 = reinterpret_cast<uint64_t*>(base + o_tile0);
+    auto* d_plans = reinterpret_cast<fourmc_bsw_plan*>(base + o_plans);
+    auto* d_prefix = reinterpret_cast<uint64_t*>(base + o_prefix);
+    HIP_TRY(hipMemcpyAsync(d_items, items, size_t(n) * sizeof(fourmc_bstream_enc_item), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_tile0, tile0.data(), (size_t(n) + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(fourmc_launch_bsw_sums(d_writes, d_items, d_tile0, n, ntiles, d_prefix, d_plans, s));
+    HIP_TRY(fourmc_launch_bsw_chase(d_writes, d_items, d_tile0, d_prefix, n, M, zstd, d_plans, nullptr, nullptr, s));
+    std::vector<fourmc_bsw_plan> plans(n);
+    HIP_TRY(hipMemcpyAsync(plans.data(), d_plans, size_t(n) * sizeof(fourmc_bsw_plan), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<fourmc_bsw_slice> slices(size_t(n) + 1);
+    fourmc_bsw_slice at = {};
+    for (uint32_t i = 0; i < n; i++) {                   // each encoded stream's share of the chunk numbers, the group table and the staging
+        fourmc_bsw_plan& pl = plans[i];
+        if (pl.reason == FOURMC_BSW_OK && (pl.groups > 0xFFFFFFFFull || pl.chunks > 0x7FFFFFFFull)) {
+            snprintf(g_err, sizeof g_err, "bstreams_compress: stream %u has %llu chunks", i, (unsigned long long)pl.chunks);
+            return FOURMC_EUNSUP;
+        }
+        if (d_images && pl.reason == FOURMC_BSW_OK && items[i].image_cap < pl.worst) pl.reason = FOURMC_BSW_CAP;
+        slices[i] = at;
+        if (pl.reason != FOURMC_BSW_OK) continue;
+        at.chunk0 += pl.chunks; at.stage0 += pl.stage;
+        if (items[i].n_writes) at.group0 += pl.groups;
+        if (at.chunk0 > 0x7FFFFFFFull) { snprintf(g_err, sizeof g_err, "bstreams_compress: more than 0x7FFFFFFF chunks"); return FOURMC_EUNSUP; }
+    }
+    slices[n] = at;
+    auto report = [&](const std::vector<uint64_t>* bytes) {
+        for (uint32_t i = 0; i < n; i++) {
+            const fourmc_bsw_plan& pl = plans[i];
+            const bool planned = pl.reason == FOURMC_BSW_OK || pl.reason == FOURMC_BSW_CAP;
+            items[i].reason = pl.reason;
+            items[i].groups = planned ? uint32_t(pl.groups) : 0; items[i].chunks = planned ? uint32_t(pl.chunks) : 0;
+            items[i].image_bytes = !planned ? 0 : bytes && pl.reason == FOURMC_BSW_OK ? (*bytes)[i] : pl.worst;
+        }
+    };
+    if (!d_images) { report(nullptr); return FOURMC_OK; }
+    const uint32_t round = bsw_round();
+    const uint64_t nc = at.chunk0;
+    const uint32_t piece = uint32_t(nc < round ? nc : round);
+    const uint64_t slot_m = align256(bs_block_bound(zstd, M));
+    const uint64_t stage = at.stage0 < uint64_t(piece) * slot_m ? at.stage0 : uint64_t(piece) * slot_m;
+    const size_t o_carry = align256((size_t(n) + 1) * sizeof(fourmc_bsw_slice)), o_bytes = o_carry + align256(size_t(n) * 8);
+    const size_t o_sum = o_bytes + align256(size_t(n) * 8), o_grp = o_sum + align256(sizeof(fourmc_bstream_enc_summary));
+    const size_t o_blk = o_grp + align256(size_t(at.group0) * sizeof(fourmc_bsw_group)), o_side = o_blk + align256(size_t(piece) * sizeof(fourmc_block));
+    const size_t o_off = o_side + align256(size_t(piece) * sizeof(fourmc_bsw_side)), o_stage = o_off + align256(size_t(piece) * 8);
+    WsLease ws2(&g_img_stage); void* w2 = nullptr;
+    if (int r = ws2.get(s, o_stage + size_t(stage) + kImagesStageSlack, &w2)) return r;
+    char* b2 = static_cast<char*>(w2);
+    auto* d_slices = reinterpret_cast<fourmc_bsw_slice*>(b2);
+    auto* d_carry = reinterpret_cast<uint64_t*>(b2 + o_carry);
+    auto* d_bytes = reinterpret_cast<uint64_t*>(b2 + o_bytes);
+    auto* d_sum = reinterpret_cast<fourmc_bstream_enc_summary*>(b2 + o_sum);
+    auto* d_grp = reinterpret_cast<fourmc_bsw_group*>(b2 + o_grp);
+    auto* d_blk = reinterpret_cast<fourmc_block*>(b2 + o_blk);
+    auto* d_side = reinterpret_cast<fourmc_bsw_side*>(b2 + o_side);
+    auto* d_off = reinterpret_cast<uint64_t*>(b2 + o_off);
+    void* d_stage = b2 + o_stage;
+    HIP_TRY(hipMemcpyAsync(d_plans, plans.data(), size_t(n) * sizeof(fourmc_bsw_plan), hipMemcpyHostToDevice, s));      // with the _CAP verdicts
+    HIP_TRY(hipMemcpyAsync(d_slices, slices.data(), (size_t(n) + 1) * sizeof(fourmc_bsw_slice), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_carry, 0, size_t(n) * 8, s));
+    HIP_TRY(hipMemsetAsync(d_sum, 0, sizeof(fourmc_bstream_enc_summary), s));
+    if (at.group0) HIP_TRY(fourmc_launch_bsw_chase(d_writes, d_items, d_tile0, d_prefix, n, M, zstd, d_plans, d_slices, d_grp, s));
+    for (uint64_t c0 = 0; c0 < nc; c0 += piece) {
+        const uint32_t m = uint32_t(nc - c0 < piece ? nc - c0 : piece);
+        HIP_TRY(fourmc_launch_bsw_desc(d_items, d_plans, d_slices, d_grp, n, M, zstd, codec == FOURMC_CODEC_LZ4_MC, c0, m, d_blk, d_side, s));
+        int r;
+        switch (codec) {
+            case FOURMC_CODEC_LZ4_FAST: r = fourmc_gpu_lz4_compress_fast(d_src, d_stage, d_blk, m, s); break;
+            case FOURMC_CODEC_LZ4_MC:   r = fourmc_gpu_lz4_compress_mc(d_src, d_stage, d_blk, m, s); break;
+            case FOURMC_CODEC_LZ4_HC:   r = fourmc_gpu_lz4_compress_hc(d_src, d_stage, d_blk, m, level, s); break;
+            default:                    r = fourmc_gpu_zstd_compress(d_src, d_stage, d_blk, m, level, s); break;
+        }
+        if (r) return r;
+        HIP_TRY(fourmc_launch_bsw_pack(d_images, d_items, d_blk, d_side, d_off, m, zstd, d_stage, d_carry, d_sum, s));
+    }
+    HIP_TRY(fourmc_launch_bsw_result(d_items, d_plans, d_carry, n, d_images, d_bytes, s));
+    std::vector<uint64_t> bytes(n);
+    fourmc_bstream_enc_summary h;
+    HIP_TRY(hipMemcpyAsync(bytes.data(), d_bytes, size_t(n) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h, d_sum, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h.bad) { snprintf(g_err, sizeof g_err, "bstreams_compress: %llu chunks with a codec result outside [1, bound]", (unsigned long long)h.bad); return FOURMC_EINVAL; }
+    report(&bytes);
+    return FOURMC_OK;
+}
+
 // The decode of n streams: the single call is its n = 1 case.  Workspace (g_img_ws): the items, one summary, one first-descriptor
 // number and one status per stream, then - sized after the first read-back - the descriptors and the side table of every stream.
 // When that grows the buffer its contents are gone: the items and the summaries (the host has both) go up again.

@@ -386,6 +386,44 @@ hipError_t fourmc_launch_bstream_enc_desc(fourmc_block* d_blocks, uint64_t src0,
 /* after the codec: the scan of 8 + csize from d_sum->image_bytes into d_off[0, n) and back into *d_sum, then the pack */
 hipError_t fourmc_launch_bstream_enc_pack(void* d_image, fourmc_block* d_blocks, uint64_t* d_off, uint32_t n, int zstd,
                                           const void* d_staging, fourmc_bstream_enc_summary* d_sum, hipStream_t s);
+/* fourmc_gpu_bstreams_compress: what the plan leaves per stream for the engine's read-back (the engine sends it back with
+ * FOURMC_BSW_CAP set where the region is too small) */
+typedef struct fourmc_bsw_plan {        /* 40 bytes */
+    uint64_t groups, chunks;   /* the written groups and their chunks                                       */
+    uint64_t worst;            /* the exact worst case of the stream's length                               */
+    uint64_t stage;            /* the staging bytes of its chunks: each codec bound rounded up to 256 bytes */
+    int32_t  reason;           /* FOURMC_BSW_*                                                              */
+    uint32_t trailer;          /* 1: the stream ends with BE32(0)                                           */
+} fourmc_bsw_plan;
+/* the engine's prefix sums over the streams that are encoded (n + 1 entries): the first chunk, counted over all streams in file
+ * order, the first entry of the group table and the first staging byte of each */
+typedef struct fourmc_bsw_slice { uint64_t chunk0, group0, stage0; } fourmc_bsw_slice;
+/* a written group of a stream with a table: its first source byte and first staging byte, both counted from the stream's own, its
+ * rawlen (above M: a long group) and its first chunk's number in the stream */
+typedef struct fourmc_bsw_group { uint64_t src, stage; uint32_t rawlen, chunk0; } fourmc_bsw_group;
+/* beside the descriptor of a chunk of a round: its stream, its group's rawlen when it is the group's first chunk (else 0), and
+ * whether the stream's trailer follows it */
+typedef struct fourmc_bsw_side { uint32_t stream, rawlen, trailer, pad; } fourmc_bsw_side;
+/* the tile sums of every table (d_tile0: n + 1 ascending tile numbers, 64 entries a tile) and, per stream with a table, their
+ * inclusive prefixes in place and the verdict in d_plans[i].reason (the other fields 0) */
+hipError_t fourmc_launch_bsw_sums(const uint32_t* d_writes, const fourmc_bstream_enc_item* d_items, const uint64_t* d_tile0, uint32_t n,
+                                  uint64_t ntiles, uint64_t* d_sums, fourmc_bsw_plan* d_plans, hipStream_t s);
+/* d_groups NULL: d_plans[i] = the plan of stream i (a stream with a table keeps a verdict the sums gave it); else the group tables
+ * of the streams with a table whose reason is FOURMC_BSW_OK, at d_slices[i].group0 */
+hipError_t fourmc_launch_bsw_chase(const uint32_t* d_writes, const fourmc_bstream_enc_item* d_items, const uint64_t* d_tile0,
+                                   const uint64_t* d_prefix, uint32_t n, uint32_t max_input, int zstd, fourmc_bsw_plan* d_plans,
+                                   const fourmc_bsw_slice* d_slices, fourmc_bsw_group* d_groups, hipStream_t s);
+/* the descriptors and side entries of chunks c0 .. c0 + m - 1; the staging offsets count from chunk c0's slot */
+hipError_t fourmc_launch_bsw_desc(const fourmc_bstream_enc_item* d_items, const fourmc_bsw_plan* d_plans, const fourmc_bsw_slice* d_slices,
+                                  const fourmc_bsw_group* d_groups, uint32_t n, uint32_t max_input, int zstd, int nolimit, uint64_t c0,
+                                  uint32_t m, fourmc_block* d_blocks, fourmc_bsw_side* d_side, hipStream_t s);
+/* after the codec: the segmented scan of the round's chunks from and back into d_carry[stream], then the pack */
+hipError_t fourmc_launch_bsw_pack(void* d_images, const fourmc_bstream_enc_item* d_items, fourmc_block* d_blocks,
+                                  const fourmc_bsw_side* d_side, uint64_t* d_off, uint32_t m, int zstd, const void* d_staging,
+                                  uint64_t* d_carry, fourmc_bstream_enc_summary* d_sum, hipStream_t s);
+/* d_bytes[i] = the length of stream i (0 for one with a verdict); writes the four bytes of a stream without a chunk */
+hipError_t fourmc_launch_bsw_result(const fourmc_bstream_enc_item* d_items, const fourmc_bsw_plan* d_plans, const uint64_t* d_carry,
+                                    uint32_t n, void* d_images, uint64_t* d_bytes, hipStream_t s);
 #ifdef FOURMC_RESEARCH      /* the research side build exports these two: tools/zstd_timing.py and tools/k7x_prof.py size their read-backs with them */
 #pragma GCC visibility push(default)
 #endif

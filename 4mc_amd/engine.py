@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .binding import (BLOCK_DTYPE, BSTREAM_REASONS, CODEC_LZ4_FAST, BstreamItem, BstreamStatus, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines, ImageRef, ImageSplitItem,
+from .binding import (BLOCK_DTYPE, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, CODEC_LZ4_FAST, BstreamEncItem, BstreamItem, BstreamStatus, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines, ImageRef, ImageSplitItem,
                       ImagesSlice, ImagesSplitItem,
                       ImageRange, ImageRecords, ImageSlice, ImageStatus, check, lib)
 
@@ -212,6 +212,49 @@ def compress_bstream(d_src, d_image, codec=CODEC_LZ4_FAST, level=0, group_bytes=
                                             d_image.numel(), C.byref(out), int(codec), int(level), int(group_bytes), _stream_ptr(stream)),
           "fourmc_gpu_bstream_compress")
     return int(out.value)
+
+
+def _writes_ptr(t):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype in (torch.int32, torch.uint32)):
+        raise EngineError("compress_bstreams d_writes: a contiguous int32 / uint32 CUDA tensor is required (the bits are read as uint32)")
+    return int(t.data_ptr())
+
+
+def bstream_writes_bound(src_bytes, codec=CODEC_LZ4_FAST):
+    """A capacity that holds for the stream of EVERY schedule of write() calls over src_bytes (fourmc_gpu_bstream_writes_bound)."""
+    return int(lib().fourmc_gpu_bstream_writes_bound(int(src_bytes), int(codec)))
+
+
+def compress_bstreams(d_src, items, d_images, codec=CODEC_LZ4_FAST, level=0, d_writes=None, src_total=None, images_bytes=None, stream=None):
+    """Write many block streams with one call, each shaped by its job's write() sizes (fourmc_gpu_bstreams_compress).  `items` is a
+    sequence of (src_off, src_bytes, image_off, image_cap, writes_off, n_writes, write_bytes): n_writes entries of d_writes (a uint32
+    or int32 CUDA tensor) from writes_off on are the stream's write sizes; n_writes 0 is the uniform schedule of write_bytes per
+    write (0: one write of the whole source).  d_images None: the size query (image_bytes = the exact worst case of each schedule).
+    Returns one dict per item: image_bytes, groups, chunks, reason (a FOURMC_BSW_* number) and "name" (its entry of
+    BSTREAM_WRITE_REASONS)."""
+    q = [tuple(int(v) for v in it) for it in items]
+    src = 0 if d_src is None or d_src.numel() == 0 else _dev_ptr(d_src, "compress_bstreams d_src")
+    total = (0 if d_src is None else d_src.numel()) if src_total is None else int(src_total)
+    if d_src is not None and total > d_src.numel():
+        raise EngineError(f"compress_bstreams: src_total {total} lies beyond the tensor's {d_src.numel()} bytes")
+    tab, ntab = 0, 0
+    if d_writes is not None and d_writes.numel():
+        tab, ntab = _writes_ptr(d_writes), d_writes.numel()
+    img, cap = 0, 0
+    if d_images is not None:
+        img = _dev_ptr(d_images, "compress_bstreams d_images")
+        cap = _image_len(d_images, images_bytes, "compress_bstreams")
+        if img == 0:
+            raise EngineError("compress_bstreams: d_images is empty (None asks for the sizes)")
+    arr = (BstreamEncItem * max(len(q), 1))()
+    for i, (so, sb, io, ic, wo, nw, wb) in enumerate(q):
+        a = arr[i]
+        a.src_off, a.src_bytes, a.image_off, a.image_cap, a.writes_off, a.n_writes, a.write_bytes = so, sb, io, ic, wo, nw, wb
+    check(lib().fourmc_gpu_bstreams_compress(src, total, tab, ntab, img, cap, int(codec), int(level), C.cast(arr, C.c_void_p), len(q),
+                                             _stream_ptr(stream)), "fourmc_gpu_bstreams_compress")
+    return [{"image_bytes": int(arr[i].image_bytes), "groups": int(arr[i].groups), "chunks": int(arr[i].chunks), "reason": int(arr[i].reason),
+             "name": BSTREAM_WRITE_REASONS[arr[i].reason] if 0 <= arr[i].reason < len(BSTREAM_WRITE_REASONS) else "?"}
+            for i in range(len(q))]
 
 
 def _bstream_dict(st):

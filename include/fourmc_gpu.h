@@ -624,8 +624,7 @@ int fourmc_gpu_images_align_slices(const void* d_images, uint64_t images_bytes, 
  * Not reproduced.  (a) Foreign chunkings: a stream chunked another way, which BlockDecompressorStream would accept but these
  *   codecs never write, gets FOURMC_BS_SHAPE (or FOURMC_BS_CORRUPT when a chunk holds more than its expected size), never wrong
  *   bytes.  (b) A group cut short by a framing error is not decoded at all, though Hadoop's reader would hand out its leading chunks
- *   before it fails: total_bytes counts whole groups only and nothing is ever written beyond it.  (c) Multi-chunk groups on the
- *   encode side: bstream_compress never writes a piece longer than M.  (d) A many-streams encode, streaming writer and reader
+ *   before it fails: total_bytes counts whole groups only and nothing is ever written beyond it.  (c) Streaming writer and reader
  *   forms, the lines of a block stream, and .zst files (the libzstd pass-through of the file API) are not in this group. */
 enum {
     FOURMC_BS_OK              = 0,
@@ -701,6 +700,84 @@ int fourmc_gpu_bstreams_decompress(const void* d_images, uint64_t images_bytes, 
                                    fourmc_bstream_item* items /*host*/, uint32_t n, void* stream);
 /* a short fixed text for a FOURMC_BS_* verdict ("" for FOURMC_BS_OK).  The words are this library's: no CLI reads these files. */
 const char* fourmc_gpu_bstream_reason_text(int reason);
+
+/* ---- block streams from a job's write() calls, many per call ----------------------------------------------------------------------
+ * bstream_compress above cuts its source at one fixed group_bytes.  A job's stream is shaped by the sizes of its write() calls, and
+ * this call takes those: every stream the writer can write (tests/bstream_model.py restates it) is written here byte for byte, many
+ * streams with one call, all chunks of all streams through the same codec launches.
+ * The rule.  M = fourmc_gpu_bstream_max_input(codec); a stream's write sizes are w_0 .. w_{k-1}.  With the codecs' 4 MiB buffers the
+ *   compressor never saves a user buffer, so the shape depends on the sizes alone.  At write i with nothing accumulated: if w_i > M
+ *   the write is a long group, BE32(w_i) then ceil(w_i / M) chunks, all of M bytes but the last, and the next group starts at i + 1;
+ *   otherwise the group takes writes i .. j for the largest j with w_i + .. + w_j <= M, is written as BE32(sum) BE32(clen) payload,
+ *   and the next group starts at j + 1.  A group whose sum is 0 (zero-length writes in front of a long write, or at the end) is not
+ *   written.  The stream ends with BE32(0) when no group was written at all or the last written group was a long one (only
+ *   zero-length writes may follow it).  Each payload is what the raw codec call writes for the chunk's source bytes with dst_cap =
+ *   the codec's bound (LZ4_compressMC: its "no limit" value), as in bstream_compress.  A stream's data is contiguous in d_src, so
+ *   every chunk is a contiguous source range: nothing is gathered.
+ * Schedules.  n_writes > 0: entries [writes_off, writes_off + n_writes) of d_writes, a table in DEVICE memory (a text job issues
+ *   several write()s per record: a stream may have tens of millions of entries, and a device-resident caller has them already, as
+ *   the line-length table of image_read_lines).  n_writes == 0: the uniform schedule, every write() write_bytes long and the last
+ *   one short; write_bytes 0 is one write() of the whole source (no write at all for an empty source).
+ * Verdicts, per item; an item that gets one writes nothing into its region and costs only itself:
+ *   FOURMC_BSW_SUM    the write sizes do not sum to src_bytes;
+ *   FOURMC_BSW_WRITE  a write size above 0x7FFFFFFF (it wins over _SUM);
+ *   FOURMC_BSW_CAP    image_cap is below the exact worst case of the item's schedule (image_bytes then holds that worst case).
+ *   For _SUM and _WRITE image_bytes, groups and chunks are 0.
+ * The size query.  d_images NULL plans only: groups, chunks and image_bytes = the exact worst case of each item's schedule, which is
+ *   4 per written group, 4 + compressBound(len) per chunk and 4 for the trailer; image_off and image_cap are ignored and _CAP is
+ *   never given.  The written length never exceeds it.
+ * fourmc_gpu_bstream_writes_bound(src_bytes, codec) holds for EVERY schedule over src_bytes, without a table:
+ *     src_bytes + V(src_bytes) + (K + 4) * C + 4 * G + 4
+ *   where compressBound(n) - n <= V(n) + K with V additive over the chunks (LZ4: n / 255 and 16; zstd: n / 256 and 64), and C, G are
+ *   the most chunks and written groups any schedule has.  Two written groups in a row hold more than M bytes together when the first
+ *   is a one-chunk group (the writer only closes it because the next write no longer fits; a long group is more than M by itself),
+ *   and a long group of c chunks holds more than (c - 1) M bytes.  So the densest run of chunks alternates a one-chunk group of 1
+ *   byte with a long group of M + 1 bytes (2 chunks): 3 chunks in M + 2 bytes; every other neighbourhood - two one-chunk groups (2 in
+ *   M + 1), a longer long group (c + 1 in (c - 1) M + 2) - is sparser for M > 1.  The densest run of groups alternates writes of 1
+ *   and M bytes: 2 groups in M + 1 bytes; a long group is 1 group in more than M.  Hence
+ *     C = 3 floor(S / (M + 2)) + min(S mod (M + 2), 2),   G = 2 floor(S / (M + 1)) + min(S mod (M + 1), 1).
+ *   tests/test_bstreams_encode_cpu.py enumerates every schedule of up to 6 writes at M = 3, 4, 5 against these counts.  0 for an
+ *   unknown codec; 4 for src_bytes 0.  Host arithmetic.
+ * Arguments, as fourmc_gpu_images_compress checks them, on the host before any device is looked for and with `items` untouched on
+ *   every failure, the codec first: an unknown codec; items NULL with n > 0; d_src NULL with a nonzero src_bytes or d_writes NULL with
+ *   a nonzero n_writes; a source outside [0, src_total), a table range outside [0, writes_total) or - unless this is the query - an
+ *   image region outside [0, images_bytes); two image regions of nonzero image_cap that overlap: FOURMC_EINVAL.  A zstd level outside
+ *   the device's 1 .. 12: FOURMC_EUNSUP.  n == 0: FOURMC_OK.  No device: FOURMC_ENODEV.  More than 0x7FFFFFFF chunks in all:
+ *   FOURMC_EUNSUP.  A codec result outside [1, bound] fails the call with FOURMC_EINVAL, as in bstream_compress.
+ * Work.  Plan: one wave per 64 table entries sums them (64-bit) and one workgroup per stream turns the tile sums into prefixes (the
+ *   count / finish pattern of the line scan), which also gives _SUM and _WRITE; then one wave per stream chases the groups, each step
+ *   a 64-ary search for the last prefix <= start + M over the tile prefixes and then the entries of one tile, so its serial length is
+ *   the number of groups, not of writes.  The chase runs twice, as the decode walk does: for the counts, which come back in the one
+ *   read-back that sizes everything else, then for the group table.  Uniform schedules are closed form.  Encode: the chunks of all
+ *   streams in file order, in rounds of at most FOURMC_BSW_ROUND chunks (default 512, read at every call): one thread per chunk
+ *   writes its descriptor (its staging slot is its bound rounded up to 256 bytes), the raw codec call runs over the round
+ *   (FOURMC_LZ4_ENCODE=parallel and the launch-splitting limits apply unchanged), a segmented scan with 64-bit carries per stream
+ *   gives every chunk its place and the pack writes group header, chunk header, payload and trailer; a last kernel, one thread per
+ *   stream, leaves the lengths and writes the four bytes of a stream without a chunk.  A round may end inside a stream and inside a
+ *   long group: the carries live on the device.
+ * Synchronizations of `stream`: two (the plan's read-back, the results); the query takes one.
+ * Writes.  Nothing outside [image_off, image_off + image_bytes) of the items that are FOURMC_BSW_OK.  Two items may name the same
+ *   source bytes or table entries.  d_src, d_writes and d_images must not overlap each other (not checked). */
+enum {
+    FOURMC_BSW_OK    = 0,
+    FOURMC_BSW_SUM   = 1,   /* the write sizes do not sum to src_bytes                    */
+    FOURMC_BSW_WRITE = 2,   /* a write size above 0x7FFFFFFF                              */
+    FOURMC_BSW_CAP   = 3    /* image_cap below the exact worst case of the schedule       */
+};
+typedef struct fourmc_bstream_enc_item {   /* 72 bytes */
+    uint64_t src_off, src_bytes;      /* in : d_src[src_off, +src_bytes)                                             */
+    uint64_t image_off, image_cap;    /* in : the stream goes to d_images[image_off, +image_cap)                     */
+    uint64_t writes_off, n_writes;    /* in : entries [writes_off, +n_writes) of d_writes are this stream's write() sizes */
+    uint32_t write_bytes;             /* in : with n_writes == 0: every write() this long, the last one short;
+                                              0 = one write() of the whole source                                    */
+    int32_t  reason;                  /* out: FOURMC_BSW_OK / _SUM / _WRITE / _CAP                                   */
+    uint64_t image_bytes;             /* out: the stream's length (size query: the exact worst case for this schedule) */
+    uint32_t groups, chunks;          /* out                                                                         */
+} fourmc_bstream_enc_item;
+int fourmc_gpu_bstreams_compress(const void* d_src, uint64_t src_total, const uint32_t* d_writes, uint64_t writes_total,
+                                 void* d_images, uint64_t images_bytes, int codec, int level,
+                                 fourmc_bstream_enc_item* items /*host*/, uint32_t n, void* stream);
+uint64_t fourmc_gpu_bstream_writes_bound(uint64_t src_bytes, int codec);   /* host only, any schedule */
 
 /* ---- host-buffer conveniences with the reference's per-block signatures ------------------- */
 /* These stage one block through HBM (H2D, one launch, D2H).  They exist so the JNI entry points

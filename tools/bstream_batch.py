@@ -7,8 +7,14 @@ compress_bstream with the LZ4 fast codec (or --zstd: level 1) into one device bu
   the size query                 decompress_bstreams with no destination: the walk and its read-back alone
 Case 2, one stream of --big-bytes (default 1 GiB) in groups of M: the walk alone (the size query of decompress_bstream: one lane
 chases two dependent reads per group) against the whole decode.
+--encode times the writers instead:
+Case 1, the same k sources as streams of one write() each: one compress_bstreams call against a loop of k compress_bstream calls
+(one synchronization and a one-chunk launch each); the bytes of both are compared.
+Case 2, one stream of --big-bytes with a device table of --write-bytes per write() (default 64: 16 Mi entries for 1 GiB): the plan
+alone (the size query: tile sums, their prefixes, the chase and its read-back) against the whole call, which runs the chase once
+more for the group table; the stream is decoded back and compared with the source.
 Every output is compared with the source.  Prints one JSON line; [median, min, max] ms over --reps after one warm-up call of each.
-    python tools/bstream_batch.py [--streams 256] [--stream-bytes N] [--big-bytes N] [--reps 5] [--zstd]"""
+    python tools/bstream_batch.py [--encode] [--streams 256] [--stream-bytes N] [--big-bytes N] [--write-bytes 64] [--reps 5] [--zstd]"""
 import argparse
 import importlib
 import json
@@ -100,6 +106,60 @@ def one_big(p, base, n, codec, level, reps):
     return res
 
 
+def many_encode(p, base, k, each, codec, level, reps):
+    total = k * each
+    d_src = base.repeat(total // base.numel() + 1)[:total].contiguous()
+    per = (p.bstream_bound(each, codec, 0) + 63) & ~63
+    d_one, d_loop = (torch.zeros(k * per + 4096, dtype=torch.uint8, device="cuda") for _ in range(2))
+    items = [(j * each, each, j * per, per, 0, 0, 0) for j in range(k)]
+    res = {"streams": k, "stream_bytes": each}
+    got = []
+
+    def batch():
+        got[:] = p.compress_bstreams(d_src, items, d_one, codec, level)
+        assert all(st["reason"] == 0 for st in got)
+    res["one_call_ms"] = timed(batch, reps)
+    lens = [0] * k
+
+    def loop():
+        for j in range(k):
+            lens[j] = p.compress_bstream(d_src[j * each:(j + 1) * each], d_loop[j * per:(j + 1) * per], codec, level)
+    res["loop_of_single_calls_ms"] = timed(loop, reps)
+    assert lens == [st["image_bytes"] for st in got]
+    for j in range(k):
+        assert torch.equal(d_one[j * per:j * per + lens[j]], d_loop[j * per:j * per + lens[j]]), j
+    res["compressed_bytes"] = sum(lens)
+    res["size_query_ms"] = timed(lambda: p.compress_bstreams(d_src, items, None, codec, level), reps)
+    res["loop_over_one_call"] = round(res["loop_of_single_calls_ms"][0] / res["one_call_ms"][0], 2)
+    return res
+
+
+def one_big_encode(p, base, n, w, codec, level, reps):
+    d_src = base.repeat(n // base.numel() + 1)[:n].contiguous()
+    nw = -(-n // w)
+    d_writes = torch.full((nw,), w, dtype=torch.int32, device="cuda")
+    if n % w:
+        d_writes[-1] = n % w
+    cap = p.bstream_writes_bound(n, codec)
+    d_stream = torch.zeros(cap + 4096, dtype=torch.uint8, device="cuda")
+    item = [(0, n, 0, cap, 0, nw, 0)]
+    q = p.compress_bstreams(d_src, item, None, codec, level, d_writes=d_writes)[0]
+    res = {"stream_bytes": n, "write_bytes": w, "writes": nw, "groups": q["groups"], "chunks": q["chunks"]}
+    res["plan_alone_ms"] = timed(lambda: p.compress_bstreams(d_src, item, None, codec, level, d_writes=d_writes), reps)
+    got = []
+
+    def encode():
+        got[:] = p.compress_bstreams(d_src, item, d_stream, codec, level, d_writes=d_writes, images_bytes=cap)
+        assert got[0]["reason"] == 0
+    res["encode_ms"] = timed(encode, reps)
+    res["compressed_bytes"] = got[0]["image_bytes"]
+    d_dst = torch.empty(n, dtype=torch.uint8, device="cuda")
+    st = p.decompress_bstream(d_stream, d_dst, codec, image_bytes=got[0]["image_bytes"])
+    assert st["reason"] == 0 and st["groups"] == q["groups"] and torch.equal(d_dst, d_src)
+    res["plan_share_of_encode"] = round(res["plan_alone_ms"][0] / res["encode_ms"][0], 4)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=256)
@@ -107,12 +167,21 @@ def main():
     ap.add_argument("--big-bytes", type=int, default=1 << 30, help="0: skip the one big stream")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--zstd", action="store_true")
+    ap.add_argument("--encode", action="store_true", help="time the writers (compress_bstreams) instead of the readers")
+    ap.add_argument("--write-bytes", type=int, default=64, help="--encode: the write() size of the one big stream's table")
     a = ap.parse_args()
     p = importlib.import_module("4mc_amd")
     arch = p.gpu_init(0)
     codec, level = (p.CODEC_ZSTD, 1) if a.zstd else (p.CODEC_LZ4_FAST, 0)
     base = torch.from_numpy(helpers.corpus(48 * p.BLOCKSIZE)).cuda()
     out = {"arch": arch, "reps": a.reps, "codec": "zstd 1" if a.zstd else "lz4 fast", "note": "[median, min, max] ms"}
+    if a.encode:
+        if a.streams:
+            out["many_streams_encode"] = many_encode(p, base, a.streams, a.stream_bytes or p.bstream_max_input(codec), codec, level, a.reps)
+        if a.big_bytes:
+            out["one_stream_encode"] = one_big_encode(p, base, a.big_bytes, a.write_bytes, codec, level, a.reps)
+        print(json.dumps(out))
+        return
     if a.streams:
         out["many_streams"] = many(p, base, a.streams, a.stream_bytes or p.bstream_max_input(codec), codec, level, a.reps)
     if a.big_bytes:
