@@ -135,9 +135,12 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
 
     // Input ring (32-bit table only; kPiece above).  The bytes of the stream do not depend on the parse: they come in with
     // aligned 16-byte loads, a piece ahead of the cursor, and a dense window reads its 32 (64) bytes per lane from LDS - so its
-    // first round trip is an LDS one and does not queue behind the previous window's record store.  State: pieces rend-2 and
-    // rend-1 are in LDS and piece rend is on its way in `rnext`; rend 0 = no ring, the scoreboard is all ones.  The coordinate
-    // of position p is p + ralign, which makes every piece load aligned in memory.
+    // first round trip is an LDS one and does not queue behind the previous window's record store.  State between two windows:
+    // pieces rend-2 and rend-1 are in LDS and piece rend is on its way in `rnext`; rend 0 = no ring, the scoreboard is all ones.
+    // The window that moves the ring on asks for the next piece itself, behind its candidate gather (nothing leaves a window
+    // between the two places), so the load has the walk, the records, the commit and the next table phase to arrive and is first
+    // waited for a piece later, where it is stored.  The coordinate of position p is p + ralign, which makes every piece load
+    // aligned in memory.
     auto ralign_now = [&]() -> uint32_t {                               // (taken from src where it is used: not one more scalar kept across the walk)
         uint32_t a;
         asm volatile("s_and_b32 %0, %1, 15" : "=s"(a) : "s"(uint32_t(reinterpret_cast<uintptr_t>(src))) : "scc");
@@ -146,21 +149,20 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
     uint8_t* const ring = reinterpret_cast<uint8_t*>(score);
     uint32_t rend = VG(0);
     Q16 rnext{0, 0, 0, 0};
+    // One load, every lane, no wait where it is issued: only bytes of [src, src + n) are read - at the two ends of the block the
+    // nearest 16 of them, which piece_store moves to their place (or drops) a piece later.
     auto piece_load = [&](uint32_t k) -> Q16 {
         const int p = int(k * kPiece + 16u * uint32_t(lane)) - int(ralign_now());
-        Q16 v{0, 0, 0, 0};
-        if (p >= 0 && p + 16 <= n) { const uint4 t = *reinterpret_cast<const uint4*>(src + p); v = Q16{t.x, t.y, t.z, t.w}; }
-        else if (p + 16 > 0 && p < n) {
-            // the two ends of the block: only bytes of [src, src + n) are read - the nearest 16 of them, moved to their place
-            const int pc = min(max(p, 0), n - 16);
-            const U16B t = *reinterpret_cast<const U16B*>(src + pc);
-            unsigned __int128 w = (static_cast<unsigned __int128>(t.b) << 64) | t.a;
-            w = p > pc ? w >> (8 * (p - pc)) : w << (8 * (pc - p));
+        return ld16(src + min(max(p, 0), n - 16));
+    };
+    auto piece_store = [&](uint32_t k, Q16 v) {
+        const int p = int(k * kPiece + 16u * uint32_t(lane)) - int(ralign_now());
+        const int sh = p - min(max(p, 0), n - 16);
+        if (__ballot(sh != 0)) {                                        // an end of the block lies in this piece
+            unsigned __int128 w = (static_cast<unsigned __int128>(u64(v.d2, v.d3)) << 64) | u64(v.d0, v.d1);
+            w = (sh >= 16 || sh <= -16) ? 0 : (sh > 0 ? w >> (8 * sh) : w << (8 * -sh));
             v = Q16{uint32_t(w), uint32_t(w >> 32), uint32_t(w >> 64), uint32_t(w >> 96)};
         }
-        return v;
-    };
-    auto piece_store = [&](uint32_t k, const Q16& v) {
         const uint32_t o = ((k & 1u) << kPieceLog) + 16u * uint32_t(lane);
         *reinterpret_cast<uint4*>(ring + o) = make_uint4(v.d0, v.d1, v.d2, v.d3);
         if (!(k & 1u)) *reinterpret_cast<uint4*>(ring + kRing + o) = make_uint4(v.d0, v.d1, v.d2, v.d3);
@@ -268,22 +270,23 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 const uint32_t pos = sp0 + uint32_t(lane);
                 Q16 q0, q1;                                                              // [pos-4, pos+28)
                 uint32_t rpos = 0;                                                       // where they are in the ring
+                bool ask = false;                                                        // the ring moved: its next piece is owed
                 if (U32TAB) {
                     // The window reads [sp0-4, sp0+124): at most two pieces.  When it reaches piece `rend` the ring moves on by
-                    // the piece in `rnext` (loaded a piece ago: no wait); after a jump past that, or after a sparse batch, it
-                    // starts again at the window (a trip to memory, as every window paid before) - and the next piece is asked for
+                    // the piece in `rnext` (asked for a piece ago: no wait); after a jump past that, or after a sparse batch, it
+                    // starts again at the window's two pieces (one trip to memory for both, as every window paid before).
+                    // Either way the piece after them is asked for further down, once the candidates are in.
                     const uint32_t a0 = sp0 + ralign_now() - 4;
                     const uint32_t c_lo = a0 >> kPieceLog, c_hi = (a0 + 127) >> kPieceLog;
                     if (c_hi >= rend) {
-                        bool have = rend != 0 && c_hi == rend;          // `rnext` is piece k
-                        uint32_t k = have ? rend : c_lo - 1u;
-                        if (have) K2CNT(pt_nrot); else K2CNT(pt_nrel);
-                        do {
-                            if (have) piece_store(k, rnext);
-                            have = true; k++;
-                            rnext = piece_load(k);
-                        } while (k <= c_hi);
-                        rend = VG(k);
+                        if (rend != 0 && c_hi == rend) { K2CNT(pt_nrot); piece_store(rend, rnext); rend = VG(rend + 1); }
+                        else {
+                            K2CNT(pt_nrel);
+                            const Q16 a = piece_load(c_lo), b = piece_load(c_lo + 1);
+                            piece_store(c_lo, a); piece_store(c_lo + 1, b);
+                            rend = VG(c_lo + 2);
+                        }
+                        ask = true;
                     }
                     K2PH(pt_ring);
                     rpos = lds_addr(ring) + ((a0 + uint32_t(lane)) & (kRing - 1));
@@ -302,8 +305,17 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 }
                 if (retest && lane == 0) tab_put(h2, sp0 - 2, ck2);    // the owed refill, ahead of every read of this window
                 const uint32_t ent = tab_get(h);
+                uint32_t tag = 0;
+                if (U32TAB) { atomicMax(&tab32[h], 0x80000000u | uint32_t(63 - lane)); tag = tab32[h]; }   // the first tag round (below)
                 const uint32_t c = U32TAB ? ent >> cbits : ent;
                 const bool pass = !U32TAB || (c + kMaxDist >= pos && (c == 0 || (ent & cmask) == ck));
+                // The candidates' bytes [c-4, c+28) need `ent` alone: the 32-bit table asks for them here, and the tag rounds and the
+                // put-back run while they are on their way; they are first used where the 16-bit table loads them, further down.
+                // Every lane loads (a conditional load would be waited for where its branch ends): one without a candidate
+                // reads at its own position, which the window keeps in range (sp >= 4, sp + 132 <= n).
+                const bool near = pass && c >= 4;
+                Q16 c0{0, 0, 0, 0}, c1{0, 0, 0, 0};
+                if (U32TAB) { const uint8_t* g = src + (near ? c : pos); c0 = ld16(g - 4); c1 = ld16(g + 12); }
                 // Lanes that share a table slot.  32-bit table: the slot itself is the scoreboard - every lane tags it
                 // (atomic max of a value above any entry: the lowest lane wins), the losers tag once more among
                 // themselves, the winner puts the entry back.  That gives, exactly: the first lane of a slot (clean),
@@ -312,8 +324,7 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 // clean, all others dirty.
                 bool dirty, second = false; int pred = 0;
                 if (U32TAB) {
-                    atomicMax(&tab32[h], 0x80000000u | uint32_t(63 - lane));
-                    pred = 63 - int(tab32[h] & 63);
+                    pred = 63 - int(tag & 63);
                     const bool first = pred == lane;
                     dirty = false;
                     if (__ballot(!first)) {
@@ -334,8 +345,8 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 uint32_t info;
                 bool hit = false, slow = false;
                 uint32_t fw = 0, bk = 0;
-                if (pass && c >= 4) {
-                    const Q16 c0 = ld16(src + c - 4), c1 = ld16(src + c + 12);
+                if (near) {
+                    if (!U32TAB) { c0 = ld16(src + c - 4); c1 = ld16(src + c + 12); }
                     hit = c0.d1 == q0.d1;
                     const uint32_t xb = q0.d0 ^ c0.d0;                  // byte 3 (MSB) is position -1
                     bk = xb ? uint32_t(__builtin_clz(xb) >> 3) : 4u;
@@ -373,6 +384,14 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 const unsigned long long m_cond = __ballot(second && (hitA || hit));
                 const unsigned long long m_hit = __ballot(hit) & ~m_cond, m_dirty = __ballot(dirty), m_slow = __ballot(hit && slow);
                 K2PH(pt_gather);
+                if (U32TAB) {
+                    // The ring's next piece.  Every candidate load has been used by now except, possibly, the last 16 bytes of a
+                    // saturated lane: the explicit vmcnt(0) (0x0F70: the other counters at their maximum) leaves nothing older
+                    // than the piece outstanding, so that no wait of the walk stands for it - the piece is first waited for where
+                    // it is stored
+                    __builtin_amdgcn_s_waitcnt(0x0F70);
+                    if (ask) rnext = piece_load(rend);
+                }
                 // The first sequence may own literals from before the window, any number of them: its record needs only
                 // where they begin.  Near the end of the output buffer (what the window can write at most: those literals
                 // and 320 bytes) every sequence goes through the general path, for its exact capacity checks.
