@@ -17,6 +17,7 @@ from .binding import (  # noqa: F401
     CODEC_ZSTD, BLK_BADSUM, BLK_CORRUPT, EngineError, lib, lib_path, research_lib_path, use_research, cli_path, exported_symbols,
     make_blocks, gpu_init, ImageStatus, ImageItem, ImageEncItem, ImageEntry, ImageIndexInfo, ImageRange, IMAGE_ENTRY_DTYPE, ImageSlice, ImageRecords, ImageLines, ImageSplitItem,
     ImageRef, ImagesSplitItem, ImagesSlice, BstreamStatus, BstreamItem, BstreamEncItem, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, bstream_codec,
+    ZstStatus, ZstItem, ZST_REASONS,
 )
 from .engine import (  # noqa: F401
     lz4_decompress, zstd_decompress, zstd_compress, lz4_compress_fast, lz4_compress_hc, lz4_compress_mc, xxh32, encode_blocks, decode_blocks, pack_image, DeviceBatch, release_workspaces,
@@ -24,6 +25,7 @@ from .engine import (  # noqa: F401
     images_read_lines, images_lines_stats, images_align_slices,
     ImageReader,
     bstream_max_input, bstream_bound, compress_bstream, decompress_bstream, decompress_bstreams, compress_bstreams, bstream_writes_bound,
+    decompress_zst, decompress_zsts, zst_stats,
 )
 from .container import (  # noqa: F401
     frame_header, frame_footer, parse_footer, assemble_container, split_container, shard_range,

@@ -69,6 +69,21 @@ assert C.sizeof(BstreamEncItem) == 72
 BSTREAM_WRITE_REASONS = ("OK", "SUM", "WRITE", "CAP")
 # FOURMC_BS_*: the verdict of a block-stream decode, by number
 BSTREAM_REASONS = ("OK", "BAD_RAWLEN", "CLEN_UNREADABLE", "BAD_CLEN", "DATA_UNREADABLE", "CORRUPT", "SHAPE", "DST_SMALL")
+# struct fourmc_zst_status / fourmc_zst_item (include/fourmc_gpu.h: .zst streams)
+class ZstStatus(C.Structure):
+    _fields_ = [("decoded_bytes", C.c_uint64), ("total_bytes", C.c_uint64), ("fail_offset", C.c_uint64),
+                ("frames", C.c_uint32), ("skippable", C.c_uint32), ("blocks", C.c_uint32), ("pad", C.c_uint32),
+                ("reason", C.c_int32), ("codec_result", C.c_int32)]
+
+
+class ZstItem(C.Structure):
+    _fields_ = [("image_off", C.c_uint64), ("image_bytes", C.c_uint64), ("dst_off", C.c_uint64), ("dst_cap", C.c_uint64),
+                ("status", ZstStatus)]
+
+
+assert C.sizeof(ZstStatus) == 48 and C.sizeof(ZstItem) == 80
+# FOURMC_ZST_*: the verdict of a .zst decode, by number
+ZST_REASONS = ("OK", "FRAME", "DST_SMALL")
 # the extensions of the reference's eight block codecs -> (codec, level) for compress_bstream (Lz4Codec.java:162 and its siblings;
 # the levels from Lz4HighCompressor / Lz4UltraCompressor / Zstd*Compressor.compressBytesDirectSpecific)
 _BSTREAM_EXT = {".lz4_fast": (CODEC_LZ4_FAST, 0), ".lz4_mc": (CODEC_LZ4_MC, 0), ".lz4_hc": (CODEC_LZ4_HC, 4), ".lz4_uc": (CODEC_LZ4_HC, 8),
@@ -205,6 +220,12 @@ _GPU_API = {
     "fourmc_gpu_bstream_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_bstreams_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_bstream_reason_text": (C.c_char_p, [C.c_int]),
+    "fourmc_gpu_zst_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_zsts_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "fourmc_gpu_zst_reason_text": (C.c_char_p, [C.c_int]),
+    "fourmc_gpu_zst_stats": (None, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_set_zst_round_blocks": (None, [C.c_uint32]),
+    "fourmc_gpu_get_zst_round_blocks": (C.c_uint32, []),
     "fourmc_gpu_bstreams_compress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_bstream_writes_bound": (C.c_uint64, [C.c_uint64, C.c_int]),
     "fourmc_gpu_image_parse_stats": (None, [C.c_void_p, C.c_void_p]),

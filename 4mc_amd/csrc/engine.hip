@@ -1492,6 +1492,97 @@ const char* fourmc_gpu_bstream_reason_text(int reason)
     }
 }
 
+// ------------------------------------------------------------------------ .zst streams (zst.hip)
+namespace {
+// Table entries per round: the setter's value, else FOURMC_ZST_ROUND_BLOCKS (read at every call), else what 4 GiB of round
+// workspace hold
+uint32_t g_zst_round = 0;
+uint32_t zst_round()
+{
+    long long v = g_zst_round;
+    if (!v) { const char* e = getenv("FOURMC_ZST_ROUND_BLOCKS"); v = e && *e ? atoll(e) : 0; }
+    if (v < 1) v = (long long)((size_t(4) << 30) / fourmc_zst_per_block_bytes());
+    return uint32_t(v > (1 << 24) ? (1 << 24) : v);
+}
+struct ZstLeases { WsLease tab{&g_img_ws}, round{&g_img_stage}, serial; hipStream_t s; };
+int zst_ws(void* ctx, int which, size_t need, void** out)
+{
+    ZstLeases* l = static_cast<ZstLeases*>(ctx);
+    return (which == 0 ? l->tab : which == 1 ? l->round : l->serial).get(l->s, need, out);
+}
+int zsts_run(const void* d_images, void* d_dst, fourmc_zst_item* items, uint32_t n, hipStream_t s)
+{
+    if (int r = ensure_device()) return r;
+    ZstLeases l; l.s = s;
+    return fourmc_zst_run(d_images, d_dst, items, n, zst_round(), zst_ws, &l, g_err, sizeof g_err, s);
+}
+}
+
+void fourmc_gpu_set_zst_round_blocks(uint32_t blocks) { g_zst_round = blocks; }
+uint32_t fourmc_gpu_get_zst_round_blocks(void) { return zst_round(); }
+
+int fourmc_gpu_zst_decompress(const void* d_image, uint64_t image_bytes, void* d_dst, uint64_t dst_cap, fourmc_zst_status* status, void* stream)
+{
+    if (!status || (image_bytes && !d_image)) { snprintf(g_err, sizeof g_err, "zst_decompress: null pointer"); return FOURMC_EINVAL; }
+    fourmc_zst_item it = {};
+    it.image_bytes = image_bytes; it.dst_cap = d_dst ? dst_cap : 0;
+    if (int r = zsts_run(d_image, d_dst, &it, 1, static_cast<hipStream_t>(stream))) return r;
+    *status = it.status;
+    return FOURMC_OK;
+}
+
+int fourmc_gpu_zsts_decompress(const void* d_images, uint64_t images_bytes, void* d_dst, uint64_t dst_bytes, fourmc_zst_item* items,
+                               uint32_t n, void* stream)
+{
+    if (n == 0) return FOURMC_OK;
+    if (!items) { snprintf(g_err, sizeof g_err, "zsts_decompress: null items"); return FOURMC_EINVAL; }
+    {
+        std::vector<std::pair<uint64_t, uint64_t>> d;
+        if (d_dst) d.reserve(n);
+        for (uint32_t i = 0; i < n; i++) {
+            const fourmc_zst_item& it = items[i];
+            if (it.image_bytes && !d_images) { snprintf(g_err, sizeof g_err, "zsts_decompress: null images"); return FOURMC_EINVAL; }
+            if (it.image_off > images_bytes || it.image_bytes > images_bytes - it.image_off) {
+                snprintf(g_err, sizeof g_err, "zsts_decompress: stream %u lies beyond the %llu bytes of streams", i, (unsigned long long)images_bytes);
+                return FOURMC_EINVAL;
+            }
+            if (!d_dst) continue;                             // the size query looks at no destination
+            if (it.dst_off > dst_bytes || it.dst_cap > dst_bytes - it.dst_off) {
+                snprintf(g_err, sizeof g_err, "zsts_decompress: the output region of stream %u lies beyond the %llu bytes of the destination", i,
+                         (unsigned long long)dst_bytes);
+                return FOURMC_EINVAL;
+            }
+            if (it.dst_cap) d.emplace_back(it.dst_off, it.dst_off + it.dst_cap);
+        }
+        std::sort(d.begin(), d.end());
+        for (size_t i = 1; i < d.size(); i++)
+            if (d[i].first < d[i - 1].second) {
+                snprintf(g_err, sizeof g_err, "zsts_decompress: output regions overlap at %llu", (unsigned long long)d[i].first);
+                return FOURMC_EINVAL;
+            }
+    }
+    return zsts_run(d_images, d_dst, items, n, static_cast<hipStream_t>(stream));
+}
+
+const char* fourmc_gpu_zst_reason_text(int reason)
+{
+    switch (reason) {
+        case FOURMC_ZST_OK:        return "";
+        case FOURMC_ZST_FRAME:     return "zstd : frame decoding failed";
+        case FOURMC_ZST_DST_SMALL: return "Destination buffer too small";
+        default:                   return "unknown";
+    }
+}
+
+void fourmc_gpu_zst_stats(unsigned long long* fast_frames, unsigned long long* serial_frames, unsigned long long* fast_blocks)
+{
+    unsigned long long c[3] = {0, 0, 0};
+    if (ensure_device() == FOURMC_OK) (void)fourmc_zst_counts(c);
+    if (fast_frames) *fast_frames = c[0];
+    if (serial_frames) *serial_frames = c[1];
+    if (fast_blocks) *fast_blocks = c[2];
+}
+
 // ------------------------------------------------------------------------ random access into images (image.hip)
 // Workspace of the three calls (g_img_ws): the index summary, then - sized after its read-back - the entries and what the call
 // needs besides.  A buffer that grows loses its contents: everything after the first read-back is recomputed on the device.

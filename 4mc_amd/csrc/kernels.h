@@ -440,6 +440,14 @@ hipError_t fourmc_launch_zstd_encode(const void* d_src, void* d_dst, fourmc_bloc
                                      void* d_work, int container_mode, int level, int serial, hipStream_t stream);
 hipError_t fourmc_launch_xxh32(const void* d_base, fourmc_block* d_blocks, uint32_t n,
                                uint32_t seed, int mode, hipStream_t stream);
+/* .zst streams (zst.hip).  The whole decode of n streams lives there; the engine hands it its workspace registries through `ws`
+ * (which: 0 tables, 1 one round's areas, 2 the serial decoder's literal buffers; a buffer that grows loses its contents) and gets a
+ * FOURMC_* code back, with the text in err */
+typedef int (*fourmc_zst_ws_fn)(void* ctx, int which, size_t need, void** out);
+int        fourmc_zst_run(const void* d_images, void* d_dst, fourmc_zst_item* items, uint32_t n, uint32_t round_blocks,
+                          fourmc_zst_ws_fn ws, void* ws_ctx, char* err, size_t err_cap, hipStream_t s);
+size_t     fourmc_zst_per_block_bytes(void);               /* workspace of one table entry of a round */
+int        fourmc_zst_counts(unsigned long long* c3);      /* fast frames, serial frames, fast blocks since the last call; -1: device error */
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

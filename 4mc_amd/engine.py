@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .binding import (BLOCK_DTYPE, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, CODEC_LZ4_FAST, BstreamEncItem, BstreamItem, BstreamStatus, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines, ImageRef, ImageSplitItem,
+from .binding import (ZST_REASONS, ZstItem, ZstStatus, BLOCK_DTYPE, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, CODEC_LZ4_FAST, BstreamEncItem, BstreamItem, BstreamStatus, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines, ImageRef, ImageSplitItem,
                       ImagesSlice, ImagesSplitItem,
                       ImageRange, ImageRecords, ImageSlice, ImageStatus, check, lib)
 
@@ -294,6 +294,51 @@ def decompress_bstreams(d_images, items, d_dst, codec=CODEC_LZ4_FAST, images_byt
     check(lib().fourmc_gpu_bstreams_decompress(ptr, n, dst, cap, int(codec), C.cast(arr, C.c_void_p), len(q), _stream_ptr(stream)),
           "fourmc_gpu_bstreams_decompress")
     return [_bstream_dict(arr[i].status) for i in range(len(q))]
+
+
+def _zst_dict(st):
+    res = {name: int(getattr(st, name)) for name, _ in ZstStatus._fields_ if name != "pad"}
+    res["name"] = ZST_REASONS[st.reason] if 0 <= st.reason < len(ZST_REASONS) else "?"
+    res["message"] = lib().fourmc_gpu_zst_reason_text(st.reason).decode()
+    return res
+
+
+def decompress_zst(d_image, d_dst=None, image_bytes=None, stream=None):
+    """Decode the .zst file d_image[:image_bytes] (default: the whole tensor) into d_dst (fourmc_gpu_zst_decompress); d_dst None:
+    the size query.  Returns the status as a dict: decoded_bytes, total_bytes, fail_offset, frames, skippable, blocks, reason (a
+    FOURMC_ZST_* number), codec_result, "name" (its entry of ZST_REASONS) and "message"."""
+    n = _image_len(d_image, image_bytes, "decompress_zst")
+    st = ZstStatus()
+    dst, cap = (0, 0) if d_dst is None else (_dev_ptr(d_dst, "decompress_zst d_dst"), d_dst.numel())
+    if d_dst is not None and dst == 0:          # an empty tensor has no address, and to the library NULL is the size query
+        raise EngineError("decompress_zst: d_dst is empty (None asks for the size)")
+    check(lib().fourmc_gpu_zst_decompress(_dev_ptr(d_image, "decompress_zst d_image"), n, dst, cap, C.byref(st), _stream_ptr(stream)),
+          "fourmc_gpu_zst_decompress")
+    return _zst_dict(st)
+
+
+def decompress_zsts(d_images, items, d_dst, images_bytes=None, stream=None):
+    """Decode many .zst files of one buffer with one call (fourmc_gpu_zsts_decompress).  `items` is a sequence of
+    (image_off, image_bytes, dst_off, dst_cap); d_dst None: the size query.  Returns one status dict per item, each what
+    decompress_zst returns for that file alone."""
+    ptr = _dev_ptr(d_images, "decompress_zsts d_images")
+    n = _image_len(d_images, images_bytes, "decompress_zsts")
+    dst, cap = (0, 0) if d_dst is None else (_dev_ptr(d_dst, "decompress_zsts d_dst"), d_dst.numel())
+    if d_dst is not None and dst == 0:
+        raise EngineError("decompress_zsts: d_dst is empty (None asks for the sizes)")
+    q = [tuple(int(v) for v in it) for it in items]
+    arr = (ZstItem * max(len(q), 1))()
+    for i, (io, ib, do, dc) in enumerate(q):
+        arr[i].image_off, arr[i].image_bytes, arr[i].dst_off, arr[i].dst_cap = io, ib, do, dc
+    check(lib().fourmc_gpu_zsts_decompress(ptr, n, dst, cap, C.cast(arr, C.c_void_p), len(q), _stream_ptr(stream)), "fourmc_gpu_zsts_decompress")
+    return [_zst_dict(arr[i].status) for i in range(len(q))]
+
+
+def zst_stats():
+    """{"fast_frames", "serial_frames", "fast_blocks"} of the .zst decodes since the last call on this device (fourmc_gpu_zst_stats)."""
+    c = (C.c_ulonglong * 3)()
+    lib().fourmc_gpu_zst_stats(C.byref(c, 0), C.byref(c, 8), C.byref(c, 16))
+    return {"fast_frames": int(c[0]), "serial_frames": int(c[1]), "fast_blocks": int(c[2])}
 
 
 def _image_len(d_image, image_bytes, what):

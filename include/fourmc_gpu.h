@@ -701,6 +701,55 @@ int fourmc_gpu_bstreams_decompress(const void* d_images, uint64_t images_bytes, 
 /* a short fixed text for a FOURMC_BS_* verdict ("" for FOURMC_BS_OK).  The words are this library's: no CLI reads these files. */
 const char* fourmc_gpu_bstream_reason_text(int reason);
 
+/* ---- .zst streams: the files of ZstCodec (hadoop-4mc/.../ZstCodec.java) and of the zstd tool, decoded in device memory ----
+ * One stream: the contract of the reference's ZSTD_decompress(dst, cap, image, image_bytes) (zstd_decompress.c:1112; the frame loop
+ * :989-1078): concatenated frames and skippable frames, no dictionary, every windowLog the one-shot call takes (up to 31), and -
+ * unlike the block call fourmc_gpu_zstd_decompress - a content checksum is verified (XXH64 of the frame's output, low 32 bits).
+ * ZSTD_decompressStream, which ZstdStreamDecompressor uses, differs in one place: it refuses windowLog > 27.  Deviation, as in the
+ * block call: a frame with a non-zero dictionary ID fails (FOURMC_ZST_FRAME).
+ *
+ * Verdicts, in this order.  d_dst == NULL is the size query: the walk over the headers and the entropy stage run (a .zst frame
+ * need not carry its size), nothing else.  total_bytes > dst_cap: FOURMC_ZST_DST_SMALL, nothing is written, and it wins over every
+ * other verdict.  Otherwise the frames are executed in file order and the first failing frame - header, entropy stage, execution
+ * or checksum - gives FOURMC_ZST_FRAME with codec_result < 0.  Nothing is written outside [d_dst, d_dst + total_bytes), bytes from
+ * decoded_bytes on are unspecified; one exception: a frame only the serial one-wave decoder can judge (below) is decoded by it,
+ * with what follows it in its stream, into [d_dst + total_bytes, d_dst + dst_cap), and a failure there may leave bytes behind.
+ *
+ * How.  Every block of every frame of every stream of a call gets one lane for its entropy stage (Huffman literals, FSE
+ * sequences), whatever the frame's length; then one wave per frame executes the frame's blocks in order.  A frame those stages
+ * decline - an Offset_Value beyond 28 bits (needs windowLog > 27), a Huffman stream that does not end on its mark, a block of more
+ * than 43691 sequences on average over a round, a frame of 2 GiB or more - is handed with the rest of its stream to the serial
+ * decoder, whose result is the verdict; the size query reports such a frame as failing.  The workspace is bounded by the table
+ * entries (blocks) per round: FOURMC_ZST_ROUND_BLOCKS or the setter, default what 4 GiB hold (about 8700); a call of more blocks
+ * runs the entropy stage twice, once for the sizes and once per round in front of its execution.  The decoders may read up to 64
+ * bytes past an image: the caller keeps that slack.  Synchronizations of `stream`: three (block count, sizes, status); the size
+ * query takes two.
+ *
+ * Many streams: the single call is the n = 1 case and runs the same host function; each item's status and bytes equal the single
+ * call's, a damaged stream changes nothing for its neighbours, two items may name the same image bytes.  FOURMC_EINVAL, checked on
+ * the host before any device is looked for, with `items` untouched: NULL items, a NULL d_images with a nonzero image_bytes, an image
+ * outside [0, images_bytes), and - with a destination - an output region outside [0, dst_bytes) or two regions of nonzero dst_cap
+ * that overlap.  n == 0: FOURMC_OK.  More than 0x7FFFFFFF frames or blocks in all: FOURMC_EUNSUP. */
+enum { FOURMC_ZST_OK = 0, FOURMC_ZST_FRAME = 1, FOURMC_ZST_DST_SMALL = 2 };
+typedef struct fourmc_zst_status {      /* 48 bytes */
+    uint64_t decoded_bytes;  /* sum of the sizes of the frames wholly decoded in front of the first failing frame: d_dst[0, decoded_bytes) is good */
+    uint64_t total_bytes;    /* sum of the decoded sizes of the frames in front of the first frame whose header walk or entropy stage fails (all, if none): the size query's answer */
+    uint64_t fail_offset;    /* image offset of the magic number of the failing frame; image_bytes if none */
+    uint32_t frames, skippable, blocks, pad;   /* zstd frames, skippable frames and blocks in front of the failure */
+    int32_t  reason;         /* FOURMC_ZST_* */
+    int32_t  codec_result;   /* 0, or the negative value the frame decoder gave for the failing frame */
+} fourmc_zst_status;
+typedef struct fourmc_zst_item { uint64_t image_off, image_bytes, dst_off, dst_cap; fourmc_zst_status status; } fourmc_zst_item;   /* 80 bytes */
+int fourmc_gpu_zst_decompress (const void* d_image, uint64_t image_bytes, void* d_dst, uint64_t dst_cap, fourmc_zst_status* status, void* stream);
+int fourmc_gpu_zsts_decompress(const void* d_images, uint64_t images_bytes, void* d_dst, uint64_t dst_bytes, fourmc_zst_item* items /*host*/, uint32_t n, void* stream);
+const char* fourmc_gpu_zst_reason_text(int reason);
+/* since the last call, this device: frames the lane-per-block stages decoded, frames handed to the serial decoder, blocks of the
+ * former (a test aid like the execute kernel's counters) */
+void fourmc_gpu_zst_stats(unsigned long long* fast_frames, unsigned long long* serial_frames, unsigned long long* fast_blocks);
+/* Tuning knob: table entries (blocks) per round of the .zst decode; 0: FOURMC_ZST_ROUND_BLOCKS, else the default.  Results are identical. */
+void     fourmc_gpu_set_zst_round_blocks(uint32_t blocks);
+uint32_t fourmc_gpu_get_zst_round_blocks(void);
+
 /* ---- block streams from a job's write() calls, many per call ----------------------------------------------------------------------
  * bstream_compress above cuts its source at one fixed group_bytes.  A job's stream is shaped by the sizes of its write() calls, and
  * this call takes those: every stream the writer can write (tests/bstream_model.py restates it) is written here byte for byte, many
