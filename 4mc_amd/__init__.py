@@ -17,7 +17,7 @@ from .binding import (  # noqa: F401
     CODEC_ZSTD, BLK_BADSUM, BLK_CORRUPT, EngineError, lib, lib_path, research_lib_path, use_research, cli_path, exported_symbols,
     make_blocks, gpu_init, ImageStatus, ImageItem, ImageEncItem, ImageEntry, ImageIndexInfo, ImageRange, IMAGE_ENTRY_DTYPE, ImageSlice, ImageRecords, ImageLines, ImageSplitItem,
     ImageRef, ImagesSplitItem, ImagesSlice, BstreamStatus, BstreamItem, BstreamEncItem, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, bstream_codec,
-    ZstStatus, ZstItem, ZST_REASONS,
+    ZstStatus, ZstItem, ZST_REASONS, ZstwStatus, ZstwItem, ZSTW_REASONS,
 )
 from .engine import (  # noqa: F401
     lz4_decompress, zstd_decompress, zstd_compress, lz4_compress_fast, lz4_compress_hc, lz4_compress_mc, xxh32, encode_blocks, decode_blocks, pack_image, DeviceBatch, release_workspaces,
@@ -26,6 +26,7 @@ from .engine import (  # noqa: F401
     ImageReader,
     bstream_max_input, bstream_bound, compress_bstream, decompress_bstream, decompress_bstreams, compress_bstreams, bstream_writes_bound,
     decompress_zst, decompress_zsts, zst_stats,
+    compress_zst, compress_zsts, zst_bound, zst_codec_level,
 )
 from .container import (  # noqa: F401
     frame_header, frame_footer, parse_footer, assemble_container, split_container, shard_range,

@@ -84,6 +84,21 @@ class ZstItem(C.Structure):
 assert C.sizeof(ZstStatus) == 48 and C.sizeof(ZstItem) == 80
 # FOURMC_ZST_*: the verdict of a .zst decode, by number
 ZST_REASONS = ("OK", "FRAME", "DST_SMALL")
+
+
+# struct fourmc_zstw_status / fourmc_zstw_item (include/fourmc_gpu.h: .zst streams written)
+class ZstwStatus(C.Structure):
+    _fields_ = [("image_bytes", C.c_uint64), ("blocks", C.c_uint32), ("reason", C.c_int32), ("codec_result", C.c_int32), ("pad", C.c_uint32)]
+
+
+class ZstwItem(C.Structure):
+    _fields_ = [("src_off", C.c_uint64), ("src_bytes", C.c_uint64), ("image_off", C.c_uint64), ("image_cap", C.c_uint64),
+                ("level", C.c_int32), ("pad", C.c_int32), ("status", ZstwStatus)]
+
+
+assert C.sizeof(ZstwStatus) == 24 and C.sizeof(ZstwItem) == 64
+# FOURMC_ZSTW_*: the verdict of a .zst encode, by number
+ZSTW_REASONS = ("OK", "DST_SMALL", "LEVEL", "TOO_LONG")
 # the extensions of the reference's eight block codecs -> (codec, level) for compress_bstream (Lz4Codec.java:162 and its siblings;
 # the levels from Lz4HighCompressor / Lz4UltraCompressor / Zstd*Compressor.compressBytesDirectSpecific)
 _BSTREAM_EXT = {".lz4_fast": (CODEC_LZ4_FAST, 0), ".lz4_mc": (CODEC_LZ4_MC, 0), ".lz4_hc": (CODEC_LZ4_HC, 4), ".lz4_uc": (CODEC_LZ4_HC, 8),
@@ -224,6 +239,11 @@ _GPU_API = {
     "fourmc_gpu_zsts_decompress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_zst_reason_text": (C.c_char_p, [C.c_int]),
     "fourmc_gpu_zst_stats": (None, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_zst_bound": (C.c_uint64, [C.c_uint64]),
+    "fourmc_zst_codec_level": (C.c_int, [C.c_int]),
+    "fourmc_gpu_zst_compress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_zsts_compress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "fourmc_gpu_zstw_reason_text": (C.c_char_p, [C.c_int]),
     "fourmc_gpu_set_zst_round_blocks": (None, [C.c_uint32]),
     "fourmc_gpu_get_zst_round_blocks": (C.c_uint32, []),
     "fourmc_gpu_bstreams_compress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),

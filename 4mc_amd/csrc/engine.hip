@@ -1583,6 +1583,107 @@ void fourmc_gpu_zst_stats(unsigned long long* fast_frames, unsigned long long* s
     if (fast_blocks) *fast_blocks = c[2];
 }
 
+// ------------------------------------------------------------------------ .zst streams written (zstd_encode.hip: zst_stream_*_kernel)
+uint64_t fourmc_gpu_zst_bound(uint64_t src_bytes) { return 6 + src_bytes + 3 * (src_bytes / 131072 + 1); }
+int fourmc_zst_codec_level(int configured) { return configured <= 0 || configured >= 23 ? 3 : configured; }
+
+namespace {
+constexpr uint64_t kZstwMaxSource = 0xC0000000ull;
+// The encode of n streams: the single call is its n = 1 case.  Workspace (g_img_ws): the items and the jobs (one upload), then the
+// per-stream encoder areas (the stream's codec workspace).  One synchronization: the items come back with their status.
+int zstw_run(const void* d_src, void* d_images, fourmc_zstw_item* items, uint32_t n, hipStream_t s)
+{
+    std::vector<fourmc_zstw_item> up(items, items + n);
+    std::vector<fourmc_zstw_job> jobs[2];
+    uint64_t work = 0;
+    for (int fam = 1; fam <= 2; fam++)                       // the "fast" jobs first, the "dfast" jobs behind them
+        for (uint32_t i = 0; i < n; i++) {
+            fourmc_zstw_status st = {};
+            const int strat = fourmc_zst_stream_strategy(items[i].level);
+            if (!strat) st.reason = FOURMC_ZSTW_LEVEL;
+            else if (items[i].src_bytes > kZstwMaxSource) st.reason = FOURMC_ZSTW_TOO_LONG;
+            if (fam == 1) up[i].status = st;
+            if (st.reason != FOURMC_ZSTW_OK || strat != fam) continue;
+            fourmc_zstw_job j; j.item = i; j.level = items[i].level; j.work_off = work;
+            work += align256(fourmc_zstd_enc_work_bytes(1, items[i].level));
+            jobs[fam - 1].push_back(j);
+        }
+    const uint32_t nf = uint32_t(jobs[0].size()), nd = uint32_t(jobs[1].size());
+    if (nf + nd) {
+        if (int r = ensure_device()) return r;
+        const size_t o_jobs = align256(size_t(n) * sizeof(fourmc_zstw_item)), head = o_jobs + align256(size_t(nf + nd) * sizeof(fourmc_zstw_job));
+        std::vector<char> stage(head);
+        memcpy(stage.data(), up.data(), size_t(n) * sizeof(fourmc_zstw_item));
+        if (nf) memcpy(stage.data() + o_jobs, jobs[0].data(), size_t(nf) * sizeof(fourmc_zstw_job));
+        if (nd) memcpy(stage.data() + o_jobs + size_t(nf) * sizeof(fourmc_zstw_job), jobs[1].data(), size_t(nd) * sizeof(fourmc_zstw_job));
+        WsLease ws(&g_img_ws), cw; void* w = nullptr; void* d_work = nullptr;
+        if (int r = ws.get(s, head, &w)) return r;
+        if (int r = lease_codec_ws(cw, s, size_t(work), &d_work)) return r;
+        char* base = static_cast<char*>(w);
+        HIP_TRY(hipMemcpyAsync(base, stage.data(), head, hipMemcpyHostToDevice, s));
+        HIP_TRY(fourmc_launch_zst_stream(d_src, d_images, reinterpret_cast<fourmc_zstw_item*>(base), reinterpret_cast<const fourmc_zstw_job*>(base + o_jobs),
+                                         nf, nd, d_work, s));
+        HIP_TRY(hipMemcpyAsync(up.data(), base, size_t(n) * sizeof(fourmc_zstw_item), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    for (uint32_t i = 0; i < n; i++) items[i].status = up[i].status;
+    return FOURMC_OK;
+}
+}
+
+int fourmc_gpu_zsts_compress(const void* d_src, uint64_t src_total, void* d_images, uint64_t images_bytes, fourmc_zstw_item* items, uint32_t n, void* stream)
+{
+    if (n == 0) return FOURMC_OK;
+    if (!items) { snprintf(g_err, sizeof g_err, "zsts_compress: null items"); return FOURMC_EINVAL; }
+    {
+        std::vector<std::pair<uint64_t, uint64_t>> d;
+        d.reserve(n);
+        for (uint32_t i = 0; i < n; i++) {
+            const fourmc_zstw_item& it = items[i];
+            const bool read = it.src_bytes <= kZstwMaxSource;            // (a source beyond the limit is refused unread: only its descriptor exists)
+            if (read && it.src_bytes && !d_src) { snprintf(g_err, sizeof g_err, "zsts_compress: null source"); return FOURMC_EINVAL; }
+            if (it.image_cap && !d_images) { snprintf(g_err, sizeof g_err, "zsts_compress: null images"); return FOURMC_EINVAL; }
+            if (read && (it.src_off > src_total || it.src_bytes > src_total - it.src_off)) {
+                snprintf(g_err, sizeof g_err, "zsts_compress: the source of stream %u lies beyond the %llu bytes of sources", i, (unsigned long long)src_total);
+                return FOURMC_EINVAL;
+            }
+            if (it.image_off > images_bytes || it.image_cap > images_bytes - it.image_off) {
+                snprintf(g_err, sizeof g_err, "zsts_compress: the region of stream %u lies beyond the %llu bytes of images", i, (unsigned long long)images_bytes);
+                return FOURMC_EINVAL;
+            }
+            if (it.image_cap) d.emplace_back(it.image_off, it.image_off + it.image_cap);
+        }
+        std::sort(d.begin(), d.end());
+        for (size_t i = 1; i < d.size(); i++)
+            if (d[i].first < d[i - 1].second) {
+                snprintf(g_err, sizeof g_err, "zsts_compress: image regions overlap at %llu", (unsigned long long)d[i].first);
+                return FOURMC_EINVAL;
+            }
+    }
+    return zstw_run(d_src, d_images, items, n, static_cast<hipStream_t>(stream));
+}
+
+int fourmc_gpu_zst_compress(const void* d_src, uint64_t src_bytes, void* d_image, uint64_t image_cap, int level, fourmc_zstw_status* status, void* stream)
+{
+    if (!status) { snprintf(g_err, sizeof g_err, "zst_compress: null status"); return FOURMC_EINVAL; }
+    fourmc_zstw_item it = {};
+    it.src_bytes = src_bytes; it.image_cap = image_cap; it.level = level;
+    if (int r = fourmc_gpu_zsts_compress(d_src, src_bytes, d_image, image_cap, &it, 1, stream)) return r;
+    *status = it.status;
+    return FOURMC_OK;
+}
+
+const char* fourmc_gpu_zstw_reason_text(int reason)
+{
+    switch (reason) {
+        case FOURMC_ZSTW_OK:        return "";
+        case FOURMC_ZSTW_DST_SMALL: return "Destination buffer too small";
+        case FOURMC_ZSTW_LEVEL:     return "zstd : level not written on the device (1 to 4 are)";
+        case FOURMC_ZSTW_TOO_LONG:  return "zstd : source beyond 3 GiB";
+        default:                    return "unknown";
+    }
+}
+
 // ------------------------------------------------------------------------ random access into images (image.hip)
 // Workspace of the three calls (g_img_ws): the index summary, then - sized after its read-back - the entries and what the call
 // needs besides.  A buffer that grows loses its contents: everything after the first read-back is recomputed on the device.

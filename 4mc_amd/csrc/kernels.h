@@ -438,6 +438,13 @@ size_t     fourmc_zstd_enc_work_bytes(uint32_t n, int level);
 int        fourmc_zstd_enc_level_ok(int level);                 /* 1: the device has every strategy the level's rows name (levels 1..12) */
 hipError_t fourmc_launch_zstd_encode(const void* d_src, void* d_dst, fourmc_block* d_blocks, uint32_t n,
                                      void* d_work, int container_mode, int level, int serial, hipStream_t stream);
+/* streamed .zst frames (zstd_encode.hip): one wave per job.  d_jobs holds the n_fast jobs of the "fast" levels, then the n_dfast jobs
+ * of the "dfast" levels; a job names its item, its level and its slice of d_work (fourmc_zstd_enc_work_bytes(1, level) bytes).  The
+ * kernels write each job's item status on the device. */
+typedef struct fourmc_zstw_job { uint32_t item; int32_t level; uint64_t work_off; } fourmc_zstw_job;
+int        fourmc_zst_stream_strategy(int level);              /* 1 fast, 2 dfast, 0: not a level of the streamed kernels */
+hipError_t fourmc_launch_zst_stream(const void* d_src, void* d_images, fourmc_zstw_item* d_items, const fourmc_zstw_job* d_jobs,
+                                    uint32_t n_fast, uint32_t n_dfast, void* d_work, hipStream_t stream);
 hipError_t fourmc_launch_xxh32(const void* d_base, fourmc_block* d_blocks, uint32_t n,
                                uint32_t seed, int mode, hipStream_t stream);
 /* .zst streams (zst.hip).  The whole decode of n streams lives there; the engine hands it its workspace registries through `ws`

@@ -3241,7 +3241,625 @@ void zstd_encode_tree_kernel(const uint8_t* __restrict__ src_base, uint8_t* dst_
     zstd_encode_one<true, 0>(L, src_base, dst_base, blocks, nblocks, work_base, container_mode, level, serial);
 }
 
+// ------------------------------------------------------------------------------------------------ streamed frames (.zst, ZstCodec)
+// What ZSTD_initCStream(level) + ZSTD_compressStream + ZSTD_endStream write.  The streaming compressor keeps its input in a ring
+// of windowSize + blockSize bytes (zstd_compress.c:1591-1594) and compresses it in blocks of 128 KiB; block k lies at ring offset
+// (k mod m) * 128 KiB with m = windowSize / 128 KiB + 1, and the ring wraps in front of every block k = c * m, c >= 1
+// (:5517-5519).  The window state the reference has at block k (start position p, end position e; indices are positions + 2):
+//   * ZSTD_window_update (zstd_compress_internal.h:1177-1212): at a wrap the block is not contiguous with the last one, the prefix
+//     so far becomes the external dictionary: dictLimit = index of the wrap point = c * m * 128 KiB + 2 (it stays there for the
+//     cycle's m blocks), lowLimit = the old dictLimit.  The overlap rule (:1204-1210) then lifts lowLimit over the old bytes the new
+//     block replaces in the ring: to the index of p + len - (W + 128 KiB).
+//   * ZSTD_window_enforceMaxDist (:1086-1122, called with the block's START, zstd_compress.c:4015): lowLimit >= p + 2 - W, which is
+//     never below what the overlap rule gives, and dictLimit follows lowLimit up.  So lowLimit = max(2, p + 2 - W).
+//   * ZSTD_matchState_dictMode: external-dictionary mode while lowLimit < dictLimit, i.e. for k >= m and k mod m != m - 1.
+//   * The ext-dict parsers use dictStartIndex = ZSTD_getLowestMatchIndex(endIndex) = e + 2 - W and prefixStartIndex = max(dictLimit,
+//     dictStartIndex), and hand the block to the prefix-only parser when the two are equal (zstd_fast.c:735-737,
+//     zstd_double_fast.c:621-623): a full block k mod m == m - 2.  The prefix-only parser's lower bound is then
+//     ZSTD_getLowestPrefixIndex(endIndex) = e + 2 - W, which is what fast_block / dfast_block compute from `end` alone.
+// So: the ext-dict parser runs iff k >= m and e - W < (k / m) * m * 128 KiB; every other block is the prefix parser's.
+// In device memory the source is contiguous (the byte after the ring's last one is the stream's next byte), so both segments
+// are read at their stream positions and ZSTD_count_2segments is a plain forward count: only the decisions differ.
+// No index reaches ZSTD_CURRENT_MAX (sources end at 3 GiB): the overflow correction never runs.  ZSTD_buildSeqStore's
+// nextToUpdate rules (:2890-2896, :4017-4018) move a cursor neither "fast" nor "dfast" reads: nothing to apply for these two.
+
+// backward catch-up of a table match: ip, m step back while ip > anchor, m > low and the bytes in front are equal
+__device__ __forceinline__ uint32_t catch_up(const uint8_t* s, uint32_t& ip, uint32_t& m, uint32_t anchor, uint32_t low, int lane)
+{
+    uint32_t back = 0;
+    for (;;) {
+        const uint32_t room = min(ip - anchor, m - low);
+        const bool same = uint32_t(lane) < room && s[ip - 1 - lane] == s[m - 1 - lane];
+        const unsigned long long bad = ~__ballot(same);
+        const uint32_t k = bad ? uint32_t(__builtin_ctzll(bad)) : 64u;
+        ip -= k; m -= k; back += k;
+        if (k < 64) return back;
+    }
+}
+
+// ZSTD_compressBlock_fast_extDict_generic (zstd_fast.c:684-935) over s[start, end); dict_idx = dictStartIndex, pfx_idx =
+// prefixStartIndex (dict_idx < pfx_idx).  The batched search of fast_block: lane j speculates pair j (positions b, b + 1, repcode
+// test at b + sj) against the table as it stands, a ballot picks the first event in serial order, lanes up to it commit their
+// table writes, a lane that shares a slot with an earlier lane cuts the batch (LDS scoreboard).  One sequence per batch.
+__device__ __forceinline__ uint32_t fast_block_ext(ZLds& L, SeqStore& S, uint32_t* tab, const Params& P, uint32_t rep[3],
+                                                   const uint8_t* s, uint32_t start, uint32_t end, uint32_t dict_idx, uint32_t pfx_idx, int lane)
+{
+    start = U(start); end = U(end); dict_idx = U(dict_idx); pfx_idx = U(pfx_idx);
+    const uint32_t hlog = U(P.hlog), mls = U(P.mml);
+    const uint32_t step0 = U(P.tlen > 1 ? P.tlen + 1 : 2);
+    const int64_t ilimit = int64_t(end) - 8;
+    uint32_t anchor = start, ip0 = start;
+    uint32_t rep1 = U(rep[0]), rep2 = U(rep[1]), saved1 = 0, saved2 = 0;
+    {
+        const uint32_t max_rep = ip0 + 2 - dict_idx;                               // :739-743 (>=, and no step over the first position)
+        if (rep2 >= max_rep) { saved2 = rep2; rep2 = 0; }
+        if (rep1 >= max_rep) { saved1 = rep1; rep1 = 0; }
+    }
+    for (;;) {                                                                   // _start: one search, one sequence
+        if (int64_t(ip0) + step0 + 1 >= ilimit) break;                           // ip3 >= ilimit
+        uint32_t B = ip0, SJ = step0, V = step0, NS = ip0 + 128, width = 16;
+        int ev_kind = 0;                                                         // 1 repcode, 2 hit at b, 3 hit at b + 1, 4 end of block
+        uint32_t ev_b = 0, ev_s = 0, ev_idx = 0;
+        for (;;) {
+            uint32_t b = B, sj = SJ, v = V, ns = NS;
+            uint32_t nb_ = 0, nsj = 0, nv = 0, nns = 0;
+            if (SJ == V && B + V * (width + 1) < NS) {
+                b = B + V * uint32_t(lane);                                      // no step change inside this batch
+            } else {
+                for (uint32_t i = 0; i < width; i++) {
+                    nb_ = b + sj; nsj = v; nns = ns; nv = v;
+                    if (nb_ + v >= ns) { nv = v + 1; nns = ns + 128; }
+                    if (uint32_t(lane) > i) { b = nb_; sj = nsj; v = nv; ns = nns; }
+                }
+            }
+            nb_ = b + sj; nsj = v; nns = ns; nv = v;
+            if (nb_ + v >= ns) { nv = v + 1; nns = ns + 128; }
+            const bool act = uint32_t(lane) < width;
+            const bool term = int64_t(nb_) + 1 + int64_t(nsj) >= ilimit;         // this pair's iteration ends the block
+            const bool inb = int64_t(b) + 1 + int64_t(sj) < ilimit;              // (speculative lanes may lie beyond the block: their reads stay inside the input)
+            const uint32_t rb = inb ? b : start;
+            const uint64_t w0 = ld8(s + rb), w1 = ld8(s + rb + 1);
+            const uint32_t ip2 = inb ? b + sj : start;
+            const uint32_t rix = ip2 + 2 - rep1;                                 // repIndex; :772-777: not within 3 bytes in front of the prefix start, nor at it
+            const bool rok = act && inb && rep1 > 0 && uint32_t(pfx_idx - rix) >= 4 && rix >= 2 && rix < ip2 + 2;
+            const uint32_t r_cur = ld4(s + ip2), r_rep = ld4(s + (rok ? rix - 2 : ip2));
+            const uint32_t h0 = zhash(w0, hlog, mls), h1 = zhash(w1, hlog, mls);
+            uint32_t i0 = 0, i1 = 0; bool shared = false;
+            if (act && inb) {
+                i0 = tld(tab, h0); i1 = (h1 == h0) ? b + 2 : tld(tab, h1);
+                uint32_t* const sc0 = &L.score[h0 & 1023]; uint32_t* const sc1 = &L.score[h1 & 1023];
+                atomicMin(sc0, uint32_t(lane)); atomicMin(sc1, uint32_t(lane));
+                shared = (*sc0 != uint32_t(lane)) || (*sc1 != uint32_t(lane));
+                *sc0 = 0xFFFFFFFFu; *sc1 = 0xFFFFFFFFu;
+            }
+            const bool ok0 = act && inb && i0 >= dict_idx && i0 < b + 2, ok1 = act && inb && i1 >= dict_idx && i1 < b + 3;   // :798, :826 (an entry is always behind its reader)
+            const uint32_t c0 = ld4(s + (ok0 ? i0 - 2 : 0)), c1 = ld4(s + (ok1 ? i1 - 2 : 0));
+            int kind = 0;
+            if (act && inb) {
+                if (rok && r_cur == r_rep) kind = 1;
+                else if (ok0 && c0 == uint32_t(w0)) kind = 2;
+                else if (ok1 && c1 == uint32_t(w1)) kind = 3;
+                else if (term) kind = 4;
+            }
+            const unsigned long long cutm = __ballot(act && (shared || !inb)) & ~1ull;     // lane 0 never conflicts with an earlier lane
+            const int cut = cutm ? __builtin_ctzll(cutm) : int(width);
+            const unsigned long long evm = __ballot(kind != 0) & ((cut >= 64) ? ~0ull : ((1ull << cut) - 1));
+            if (evm) {
+                const int J = __builtin_ctzll(evm);
+                if (lane <= J) { tab[h0] = b + 2; tab[h1] = b + 3; }             // on every way out of the pair both positions are in the table (:781, :823, :906-908)
+                ev_kind = int(rl(uint32_t(kind), J)); ev_b = rl(b, J); ev_s = rl(sj, J);
+                ev_idx = ev_kind == 2 ? rl(i0, J) : rl(i1, J);
+                break;
+            }
+            if (lane < cut) { tab[h0] = b + 2; tab[h1] = b + 3; }
+            if (cut < int(width)) { B = rl(b, cut); SJ = rl(sj, cut); V = rl(v, cut); NS = rl(ns, cut); }
+            else { B = rl(nb_, width - 1); SJ = rl(nsj, width - 1); V = rl(nv, width - 1); NS = rl(nns, width - 1); }
+            width = min(64u, width * 2);
+        }
+        if (ev_kind == 4) break;                                                 // _cleanup
+        uint32_t match0, mlen, off_base, cur0, fa;
+        if (ev_kind == 1) {                                                      // :784-794
+            cur0 = ev_b + 2;
+            ip0 = ev_b + ev_s; match0 = ip0 - rep1; fa = ip0 + 4;
+            mlen = (s[ip0 - 1] == s[match0 - 1]) ? 1u : 0u;
+            mlen = U(mlen);
+            ip0 -= mlen; match0 -= mlen; off_base = 1; mlen += 4;
+        } else {                                                                 // _offset :875-892
+            ip0 = ev_kind == 3 ? ev_b + 1 : ev_b;
+            cur0 = ip0 + 2; fa = ip0 + 4;
+            match0 = ev_idx - 2;
+            rep2 = rep1; rep1 = ip0 - match0; off_base = rep1 + 3;
+            const uint32_t low = (ev_idx < pfx_idx ? dict_idx : pfx_idx) - 2;     // the catch-up stays in the segment the match starts in
+            mlen = 4 + catch_up(s, ip0, match0, anchor, low, lane);
+        }
+        mlen += count_fwd(s, fa, fa - (ip0 - match0), end, lane);                // _match (ZSTD_count_2segments over contiguous bytes)
+        store_seq(S, s, anchor, ip0 - anchor, off_base, mlen, lane);
+        ip0 += mlen; anchor = ip0;
+        if (ev_kind == 3 && ev_b + ev_s < ip0) {                                 // :906-908, ip1 = the pair's ip2 (the other exits wrote b + 1 above)
+            const uint32_t q = ev_b + ev_s; const uint32_t h = zhash(ld8(s + q), hlog, mls);
+            if (lane == 0) tab[h] = q + 2;
+        }
+        if (int64_t(ip0) <= ilimit) {                                            // :911-932
+            const uint32_t h_a = zhash(ld8(s + cur0), hlog, mls), h_b = zhash(ld8(s + ip0 - 2), hlog, mls);
+            if (lane == 0) { tab[h_a] = cur0 + 2; tab[h_b] = ip0; }
+            while (int64_t(ip0) <= ilimit) {
+                const uint32_t rix2 = ip0 + 2 - rep2;
+                if (!((uint32_t(pfx_idx - 1 - rix2) >= 3) & (rep2 > 0))) break;
+                if (ld4(s + rix2 - 2) != ld4(s + ip0)) break;
+                const uint32_t rlen = count_fwd(s, ip0 + 4, rix2 + 2, end, lane) + 4;
+                const uint32_t t = rep2; rep2 = rep1; rep1 = t;
+                store_seq(S, s, anchor, 0, 1, rlen, lane);
+                const uint32_t h = zhash(ld8(s + ip0), hlog, mls);
+                if (lane == 0) tab[h] = ip0 + 2;
+                ip0 += rlen; anchor = ip0;
+            }
+        }
+    }
+    saved2 = (saved1 != 0 && rep1 != 0) ? saved1 : saved2;                      // :866-870
+    rep[0] = rep1 ? rep1 : saved1;
+    rep[1] = rep2 ? rep2 : saved2;
+    return end - anchor;
+}
+
+// ZSTD_compressBlock_doubleFast_extDict_generic (zstd_double_fast.c:592-734) over s[start, end).  Lane j speculates position j of
+// the running search (step ((ip - anchor) >> 8) + 1): the repcode test at ip + 1, the long (8-byte) and the short probe; first
+// event / commit / scoreboard-cut rules as in fast_block_ext.
+__device__ __forceinline__ uint32_t dfast_block_ext(ZLds& L, SeqStore& S, uint32_t* tl, uint32_t* ts, const Params& P, uint32_t rep[3],
+                                                    const uint8_t* s, uint32_t start, uint32_t end, uint32_t dict_idx, uint32_t pfx_idx, int lane)
+{
+    start = U(start); end = U(end); dict_idx = U(dict_idx); pfx_idx = U(pfx_idx);
+    const uint32_t hl_log = U(P.hlog), hs_log = U(P.clog), mls = U(P.mml);
+    const int64_t ilimit = int64_t(end) - 8;
+    uint32_t anchor = start, ip = start;
+    uint32_t rep1 = U(rep[0]), rep2 = U(rep[1]);
+    auto HL = [&](uint64_t v) -> uint32_t { return uint32_t((v * 0xCF1BBCDCB7A56463ull) >> (64 - hl_log)); };
+    while (int64_t(ip) < ilimit) {                                               // one search, one sequence
+        uint32_t P0 = ip, width = 16;
+        int ev_kind = 0;                                                         // 1 repcode at p + 1, 2 long hit, 3 short hit, 4 end of block
+        uint32_t ev_p = 0, ev_l = 0, ev_s = 0;
+        for (;;) {
+            uint32_t p = P0, np;
+            if (P0 + 64 - anchor < 256) p = P0 + uint32_t(lane);                 // the step stays 1 inside this batch
+            else for (uint32_t i = 0; i < width; i++) { np = p + ((p - anchor) >> 8) + 1; if (uint32_t(lane) > i) p = np; }
+            np = p + ((p - anchor) >> 8) + 1;
+            const bool act = uint32_t(lane) < width;
+            const bool inb = int64_t(p) < ilimit;                                // (a lane at or beyond ilimit is where the loop ends)
+            const uint32_t rp = inb ? p : start;
+            const uint64_t w = ld8(s + rp), w1 = ld8(s + rp + 1);
+            const uint32_t hL = HL(w), hS = zhash(w, hs_log, mls);
+            uint32_t eL = 0, eS = 0; bool shared = false;
+            if (act && inb) {
+                eL = tld(tl, hL); eS = tld(ts, hS);
+                uint32_t* const sc0 = &L.score[hL & 511]; uint32_t* const sc1 = &L.score[512 + (hS & 511)];
+                atomicMin(sc0, uint32_t(lane)); atomicMin(sc1, uint32_t(lane));
+                shared = (*sc0 != uint32_t(lane)) || (*sc1 != uint32_t(lane));
+                *sc0 = 0xFFFFFFFFu; *sc1 = 0xFFFFFFFFu;
+            }
+            const uint32_t rix = rp + 3 - rep1;                                  // :638, :644-645
+            const bool rok = act && inb && (uint32_t(pfx_idx - 1 - rix) >= 3) && rep1 <= rp + 3 - dict_idx;
+            const bool okL = act && inb && eL > dict_idx && eL < p + 2, okS = act && inb && eS > dict_idx && eS < p + 2;   // :652, :663 (an entry is always behind its reader)
+            const uint32_t r_rep = ld4(s + (rok ? rix - 2 : 0));
+            const uint64_t cL = ld8(s + (okL ? eL - 2 : 0));
+            const uint32_t cS = ld4(s + (okS ? eS - 2 : 0));
+            int kind = 0;
+            if (act) {
+                if (!inb) kind = 4;
+                else if (rok && r_rep == uint32_t(w1)) kind = 1;
+                else if (okL && cL == w) kind = 2;
+                else if (okS && cS == uint32_t(w)) kind = 3;
+            }
+            const unsigned long long cutm = __ballot(act && shared) & ~1ull;     // lane 0 never conflicts with an earlier lane
+            const int cut = cutm ? __builtin_ctzll(cutm) : int(width);
+            const unsigned long long evm = __ballot(kind != 0) & ((cut >= 64) ? ~0ull : ((1ull << cut) - 1));
+            if (evm) {
+                const int J = __builtin_ctzll(evm);
+                ev_kind = int(rl(uint32_t(kind), J));
+                if (lane < J || (lane == J && ev_kind != 4)) { tl[hL] = p + 2; ts[hS] = p + 2; }     // :642
+                ev_p = rl(p, J); ev_l = rl(eL, J); ev_s = rl(eS, J);
+                break;
+            }
+            if (lane < cut) { tl[hL] = p + 2; ts[hS] = p + 2; }
+            P0 = cut < int(width) ? rl(p, cut) : rl(np, width - 1);
+            width = min(64u, width * 2);
+        }
+        if (ev_kind == 4) break;
+        const uint32_t curr = ev_p + 2;
+        uint32_t mlen;
+        ip = ev_p;
+        if (ev_kind == 1) {                                                      // :646-650
+            const uint32_t m = ev_p + 1 - rep1;
+            mlen = count_fwd(s, ip + 5, m + 4, end, lane) + 4;
+            ip++;
+            store_seq(S, s, anchor, ip - anchor, 1, mlen, lane);
+        } else {
+            uint32_t m, midx, offset;
+            if (ev_kind == 2) {                                                  // :652-661
+                midx = ev_l; m = midx - 2;
+                mlen = count_fwd(s, ip + 8, m + 8, end, lane) + 8;
+                offset = curr - midx;
+            } else {                                                             // :663-686: a long match at ip + 1 is preferred
+                const uint64_t w1 = ld8(s + ip + 1);
+                const uint32_t h3 = HL(w1);
+                const uint32_t i3 = tld(tl, h3);
+                if (lane == 0) tl[h3] = curr + 1;
+                if (i3 > dict_idx && i3 < curr + 1 && ld8(s + i3 - 2) == w1) {
+                    midx = i3; m = midx - 2;
+                    mlen = count_fwd(s, ip + 9, m + 8, end, lane) + 8;
+                    ip++;
+                    offset = curr + 1 - midx;
+                } else {
+                    midx = ev_s; m = midx - 2;
+                    mlen = count_fwd(s, ip + 4, m + 4, end, lane) + 4;
+                    offset = curr - midx;
+                }
+            }
+            const uint32_t low = (midx < pfx_idx ? dict_idx : pfx_idx) - 2;      // the catch-up stays in the segment the match starts in
+            mlen += catch_up(s, ip, m, anchor, low, lane);
+            rep2 = rep1; rep1 = offset;
+            store_seq(S, s, anchor, ip - anchor, offset + 3, mlen, lane);
+        }
+        ip += mlen; anchor = ip;
+        if (int64_t(ip) <= ilimit) {                                             // :697-726
+            const uint64_t wa = ld8(s + curr), wb = ld8(s + ip - 2), wc = ld8(s + ip - 1);       // (index curr + 2 is position curr)
+            if (lane == 0) { tl[HL(wa)] = curr + 2; tl[HL(wb)] = ip; ts[zhash(wa, hs_log, mls)] = curr + 2; ts[zhash(wc, hs_log, mls)] = ip + 1; }
+            while (int64_t(ip) <= ilimit) {
+                const uint32_t cur2 = ip + 2, rix2 = cur2 - rep2;
+                if (!((uint32_t(pfx_idx - 1 - rix2) >= 3) & (rep2 <= cur2 - dict_idx))) break;
+                if (ld4(s + rix2 - 2) != ld4(s + ip)) break;
+                const uint32_t rlen = count_fwd(s, ip + 4, rix2 + 2, end, lane) + 4;
+                const uint32_t t = rep2; rep2 = rep1; rep1 = t;
+                store_seq(S, s, anchor, 0, 1, rlen, lane);
+                const uint64_t wi = ld8(s + ip);
+                if (lane == 0) { ts[zhash(wi, hs_log, mls)] = cur2; tl[HL(wi)] = cur2; }
+                ip += rlen; anchor = ip;
+            }
+        }
+    }
+    rep[0] = rep1; rep[1] = rep2;                                                // :728-730
+    return end - anchor;
+}
+
+// The prefix-only parsers with the reference's repeat-offset limit.  ZSTD_compressBlock_fast_noDict_generic (zstd_fast.c:190-196)
+// and ZSTD_compressBlock_doubleFast_noDict_generic (zstd_double_fast.c:145-152) keep a carried repeat offset up to
+// curr - ZSTD_getLowestPrefixIndex(curr), which is measured from window.dictLimit: up to the whole window in a block whose dictLimit
+// is its start - window (the last block before a wrap).  fast_block / dfast_block measure from the block's prefix start (end -
+// window) and drop offsets above window - block length.  A streamed block that carries an offset between the two limits is parsed
+// here: a wave-uniform transcription of the reference loops (one position at a time: a few blocks of a long stream at most).
+__device__ __forceinline__ void carried_reps(uint32_t cur, uint32_t dict_idx, uint32_t wsize, uint32_t& rep1, uint32_t& rep2, uint32_t& saved1, uint32_t& saved2)
+{
+    const uint32_t low = cur - dict_idx > wsize ? cur - wsize : dict_idx;
+    const uint32_t max_rep = cur - low;
+    if (rep2 > max_rep) { saved2 = rep2; rep2 = 0; }
+    if (rep1 > max_rep) { saved1 = rep1; rep1 = 0; }
+}
+
+__device__ __forceinline__ uint32_t fast_block_carry(SeqStore& S, uint32_t* tab, const Params& P, uint32_t rep[3], const uint8_t* s,
+                                                     uint32_t start, uint32_t end, uint32_t dict_idx, int lane)
+{
+    start = U(start); end = U(end); dict_idx = U(dict_idx);
+    const uint32_t hlog = U(P.hlog), wsize = 1u << U(P.wlog), mls = U(P.mml);
+    const uint32_t step0 = U(P.tlen > 1 ? P.tlen + 1 : 2);
+    const uint32_t prefix_idx = end > wsize ? end + 2 - wsize : 2, prefix = prefix_idx - 2;
+    const int64_t ilimit = int64_t(end) - 8;
+    uint32_t anchor = start, ip0 = start + (start == prefix ? 1u : 0u);
+    uint32_t rep1 = U(rep[0]), rep2 = U(rep[1]), saved1 = 0, saved2 = 0;
+    carried_reps(ip0 + 2, dict_idx, wsize, rep1, rep2, saved1, saved2);
+    for (;;) {
+        uint32_t step = step0, next_step = ip0 + 128, ip1 = ip0 + 1, ip2 = ip0 + step, ip3 = ip2 + 1, cur0 = 0;
+        if (int64_t(ip3) >= ilimit) break;
+        uint32_t h0 = zhash(ld8(s + ip0), hlog, mls), h1 = zhash(ld8(s + ip1), hlog, mls);
+        uint32_t idx = tld(tab, h0);
+        int kind = 0;                                            // 1 repcode, 2 hash hit
+        for (;;) {
+            const uint32_t rval = ld4(s + ip2 - rep1);
+            cur0 = ip0 + 2;
+            if (lane == 0) tab[h0] = cur0;
+            if ((ld4(s + ip2) == rval) & (rep1 > 0)) { if (lane == 0) tab[h1] = ip1 + 2; kind = 1; break; }
+            if (idx >= prefix_idx && idx < cur0 && ld4(s + idx - 2) == ld4(s + ip0)) { if (lane == 0) tab[h1] = ip1 + 2; kind = 2; break; }
+            idx = U(tld(tab, h1)); h0 = h1; h1 = zhash(ld8(s + ip2), hlog, mls);
+            ip0 = ip1; ip1 = ip2; ip2 = ip3;
+            cur0 = ip0 + 2;
+            if (lane == 0) tab[h0] = cur0;
+            if (idx >= prefix_idx && idx < cur0 && ld4(s + idx - 2) == ld4(s + ip0)) { if (step <= 4 && lane == 0) tab[h1] = ip1 + 2; kind = 2; break; }
+            idx = U(tld(tab, h1)); h0 = h1; h1 = zhash(ld8(s + ip2), hlog, mls);
+            ip0 = ip1; ip1 = ip2; ip2 = ip0 + step; ip3 = ip1 + step;
+            if (ip2 >= next_step) { step++; next_step += 128; }
+            if (int64_t(ip3) >= ilimit) break;
+        }
+        if (kind == 0) break;                                    // _cleanup
+        uint32_t match0, mlen, off_base;
+        if (kind == 1) {
+            ip0 = ip2; match0 = ip0 - rep1;
+            mlen = U((s[ip0 - 1] == s[match0 - 1]) ? 1u : 0u);
+            ip0 -= mlen; match0 -= mlen; off_base = 1; mlen += 4;
+        } else {
+            match0 = idx - 2;
+            rep2 = rep1; rep1 = ip0 - match0; off_base = rep1 + 3;
+            mlen = 4 + catch_up(s, ip0, match0, anchor, prefix, lane);
+        }
+        mlen += count_fwd(s, ip0 + mlen, match0 + mlen, end, lane);
+        store_seq(S, s, anchor, ip0 - anchor, off_base, mlen, lane);
+        ip0 += mlen; anchor = ip0;
+        after_match(S, tab, P, s, ip0, anchor, cur0, rep1, rep2, end, ilimit, lane);
+    }
+    saved2 = (saved1 != 0 && rep1 != 0) ? saved1 : saved2;
+    rep[0] = rep1 ? rep1 : saved1;
+    rep[1] = rep2 ? rep2 : saved2;
+    return end - anchor;
+}
+
+__device__ __forceinline__ uint32_t dfast_block_carry(SeqStore& S, uint32_t* tl, uint32_t* ts, const Params& P, uint32_t rep[3], const uint8_t* s,
+                                                      uint32_t start, uint32_t end, uint32_t dict_idx, int lane)
+{
+    start = U(start); end = U(end); dict_idx = U(dict_idx);
+    const uint32_t hl_log = U(P.hlog), hs_log = U(P.clog), wsize = 1u << U(P.wlog), mls = U(P.mml);
+    const uint32_t prefix_idx = end > wsize ? end + 2 - wsize : 2, prefix = prefix_idx - 2;
+    const int64_t ilimit = int64_t(end) - 8;
+    uint32_t anchor = start, ip = start + (start == prefix ? 1u : 0u);
+    uint32_t rep1 = U(rep[0]), rep2 = U(rep[1]), saved1 = 0, saved2 = 0;
+    auto HL = [&](uint64_t v) -> uint32_t { return uint32_t((v * 0xCF1BBCDCB7A56463ull) >> (64 - hl_log)); };
+    carried_reps(ip + 2, dict_idx, wsize, rep1, rep2, saved1, saved2);
+    for (;;) {                                                   // one iteration per sequence (zstd_double_fast.c:155-303)
+        uint32_t step = 1, next_step = ip + 256, ip1 = ip + 1;
+        if (int64_t(ip1) > ilimit) break;
+        uint32_t hl0 = HL(ld8(s + ip)), idxl0 = U(tld(tl, hl0)), hl1 = 0, idxl1 = 0, idxs0 = 0, curr = 0;
+        int kind = 0;                                            // 1 repcode, 2 long, 3 short (then long at ip1)
+        for (;;) {
+            const uint64_t w = ld8(s + ip);
+            const uint32_t hs0 = zhash(w, hs_log, mls);
+            idxs0 = U(tld(ts, hs0));
+            curr = ip + 2;
+            if (lane == 0) { tl[hl0] = curr; ts[hs0] = curr; }
+            if ((rep1 > 0) && ld4(s + ip + 1 - rep1) == ld4(s + ip + 1)) { kind = 1; break; }
+            hl1 = HL(ld8(s + ip1));
+            if (idxl0 > prefix_idx && idxl0 < curr && ld8(s + idxl0 - 2) == w) { kind = 2; break; }
+            idxl1 = U(tld(tl, hl1));
+            if (idxs0 > prefix_idx && idxs0 < curr && ld4(s + idxs0 - 2) == uint32_t(w)) { kind = 3; break; }
+            if (ip1 >= next_step) { step++; next_step += 256; }
+            ip = ip1; ip1 += step;
+            hl0 = hl1; idxl0 = idxl1;
+            if (int64_t(ip1) > ilimit) break;
+        }
+        if (kind == 0) break;                                    // _cleanup
+        uint32_t mlen;
+        if (kind == 1) {
+            mlen = count_fwd(s, ip + 5, ip + 5 - rep1, end, lane) + 4;
+            ip++;
+            store_seq(S, s, anchor, ip - anchor, 1, mlen, lane);
+        } else {
+            uint32_t m, offset;
+            if (kind == 2) { m = idxl0 - 2; mlen = count_fwd(s, ip + 8, m + 8, end, lane) + 8; offset = ip - m; }
+            else if (idxl1 > prefix_idx && idxl1 < ip1 + 2 && ld8(s + idxl1 - 2) == ld8(s + ip1)) {
+                ip = ip1; m = idxl1 - 2; mlen = count_fwd(s, ip + 8, m + 8, end, lane) + 8; offset = ip - m;
+            } else { m = idxs0 - 2; mlen = count_fwd(s, ip + 4, m + 4, end, lane) + 4; offset = ip - m; }
+            mlen += catch_up(s, ip, m, anchor, prefix, lane);
+            rep2 = rep1; rep1 = offset;
+            if (step < 4 && lane == 0) tl[hl1] = ip1 + 2;         // :260-269
+            store_seq(S, s, anchor, ip - anchor, offset + 3, mlen, lane);
+        }
+        ip += mlen; anchor = ip;
+        if (int64_t(ip) <= ilimit) {                             // :278-302
+            const uint64_t wa = ld8(s + curr), wb = ld8(s + ip - 2), wc = ld8(s + ip - 1);
+            if (lane == 0) { tl[HL(wa)] = curr + 2; tl[HL(wb)] = ip; ts[zhash(wa, hs_log, mls)] = curr + 2; ts[zhash(wc, hs_log, mls)] = ip + 1; }
+            while (int64_t(ip) <= ilimit && rep2 > 0 && ld4(s + ip) == ld4(s + ip - rep2)) {
+                const uint32_t rlen = count_fwd(s, ip + 4, ip + 4 - rep2, end, lane) + 4;
+                const uint32_t t = rep2; rep2 = rep1; rep1 = t;
+                const uint64_t wi = ld8(s + ip);
+                if (lane == 0) { ts[zhash(wi, hs_log, mls)] = ip + 2; tl[HL(wi)] = ip + 2; }
+                store_seq(S, s, anchor, 0, 1, rlen, lane);
+                ip += rlen; anchor = ip;
+            }
+        }
+    }
+    saved2 = (saved1 != 0 && rep1 != 0) ? saved1 : saved2;
+    rep[0] = rep1 ? rep1 : saved1;
+    rep[1] = rep2 ? rep2 : saved2;
+    return end - anchor;
+}
+
+// One streamed frame: header without content size, full 128 KiB blocks none of which is the last, then ZSTD_endStream's block: the
+// rest of the source, or the empty 3-byte block when nothing is left (the empty source included: its ZSTD_compressStream call, of
+// zero bytes, has started the frame with an unknown size by the time ZSTD_endStream runs).  Parameters are the level's row for an
+// unknown source size.  kFast: 1 fast, 2 dfast.
+// err: 0 or a negative ZSTD error number (the image does not fit in cap).
+template <int kFast>
+__device__ __forceinline__ void zstd_stream_frame(ZLds& L, const uint8_t* src, uint32_t n, uint8_t* dst, uint32_t cap, uint8_t* work, int level, int lane,
+                                                  uint32_t& out_bytes, uint32_t& out_blocks, int& err)
+{
+    Params P;
+    {
+        const LevelRow r = kLevelRowsDev[level - 1][0];
+        P.wlog = U(r.wlog); P.clog = U(r.clog); P.hlog = U(r.hlog); P.slog = U(r.slog); P.mml = U(r.mml); P.tlen = U(r.tlen); P.strat = uint32_t(kFast);
+    }
+    uint32_t* const tab = reinterpret_cast<uint32_t*>(work + kStoreBytes);
+    uint32_t* tab_s = tab;                                                                                          // dfast: short-hash table
+    if constexpr (kFast == 2) tab_s = reinterpret_cast<uint32_t*>(work + kStoreBytes + (size_t(4) << max(P.hlog, 17u)));
+    SeqStore S;
+    S.ll = reinterpret_cast<uint32_t*>(work); S.ml = S.ll + kSeqCap; S.off = S.ml + kSeqCap;
+    S.llc = work + kOffCodes; S.ofc = S.llc + kCodeBytes; S.mlc = S.ofc + kCodeBytes;
+    S.lit = work + kOffLit + kLitPad;
+#ifdef Z1_PROF
+    for (int i = 0; i < 20; i++) S.prof[i] = 0;
+#endif
+    FseCt* const prevfse = reinterpret_cast<FseCt*>(work + kOffPrev);
+    uint8_t* const tmp = work + kOffTmp;
+    out_bytes = 0; out_blocks = 0; err = 0;
+    if (cap < 6) { err = kErrTooSmall; return; }
+    {
+        const uint64_t v = 0xFD2FB528ull | (uint64_t((P.wlog - 10) << 3) << 40);
+        if (lane < 6) dst[lane] = uint8_t(v >> (8 * lane));
+    }
+    uint32_t o = 6;
+    {   // hash tables = 0, same-slot scoreboard = empty, literal tables = none
+        uint4* t4 = reinterpret_cast<uint4*>(tab);
+        const uint32_t n16 = (4u << P.hlog) / 16;
+        for (uint32_t i = lane; i < n16; i += 64) t4[i] = make_uint4(0, 0, 0, 0);
+        if (kFast == 2) {
+            uint4* s4 = reinterpret_cast<uint4*>(tab_s);
+            const uint32_t m16 = (4u << P.clog) / 16;
+            for (uint32_t i = lane; i < m16; i += 64) s4[i] = make_uint4(0, 0, 0, 0);
+        }
+        for (int i = lane; i < 1024; i += 64) L.score[i] = 0xFFFFFFFFu;
+        for (int i = lane; i < 256; i += 64) { L.huf[0][i] = 0; L.huf[1][i] = 0; }
+    }
+    Entropy pe, ne;
+    pe.huf_repeat = kRepNone; pe.rep[0] = 1; pe.rep[1] = 4; pe.rep[2] = 8;
+    pe.fse_repeat[0] = pe.fse_repeat[1] = pe.fse_repeat[2] = kRepNone;
+    ne = pe;
+    int cur = 0;
+    bool first = true;
+    const uint32_t wsize = 1u << P.wlog, ring_blocks = (wsize >> 17) + 1;
+    uint32_t pos = 0, k = 0, wrap = 0, in_cycle = 0;                             // wrap: the position where the ring last wrapped; in_cycle = k mod ring_blocks
+    while (pos < n) {
+        const uint32_t len = min(n - pos, kSub);
+        const uint32_t last = len < kSub ? 1u : 0u;                              // (a full block is compressed before the end is known)
+        int c = 0;
+        if (cap - o < 3) { err = kErrTooSmall; return; }                         // (the streaming reference never fails on output: only what the block takes is asked for)
+        // The reference compresses into a buffer of the block's bound; here the attempt is made in place with at most 64 bytes more
+        // than the block stored raw takes (an attempt that needs more ends as a raw block either way).  What it may leave behind the
+        // raw block's end is put back: the bytes behind an image stay as they were.  With less room than that left (the region is
+        // exactly the bound, or smaller) a block of up to 4 KiB is attempted in the unused end of the sequence store (it has at most
+        // 1366 sequences) and copied: the bit writers ask for 8 spare bytes, which a short block that barely compresses has not in
+        // place.  A longer block is accepted only 66 bytes and more below its length, so its own length is room enough.
+        uint8_t* const out = dst + o + 3;
+        const bool side = cap - o - 3 < len + 64 && len <= 4096;
+        uint8_t* const aout = side ? reinterpret_cast<uint8_t*>(S.off) + kSeqBytes - 8192 : out;
+        const uint32_t bcap = side ? len + 64 : min(cap - o - 3, len + 64);
+        const bool kept = len + uint32_t(lane) < cap - o - 3;
+        const uint8_t keep = kept ? out[len + lane] : uint8_t(0);
+        const bool kept1 = 1 + uint32_t(lane) < cap - o - 3;                      // behind an RLE block's one byte: the attempt it replaces was up to 24 bytes long
+        const uint8_t keep1 = kept1 ? out[1 + lane] : uint8_t(0);
+        if (in_cycle == ring_blocks) { in_cycle = 0; wrap = pos; }
+        const uint32_t end = pos + len;
+        const bool ext = wrap > 0 && end - wsize < wrap;                          // (see the window state above)
+        bool tables_built = false;
+        if (len >= 7 && !side && cap - o - 3 < 64) { err = kErrTooSmall; return; }   // (a long block with next to no room left: the region is far below the bound)
+        if (len >= 7) {
+            S.nseq = 0; S.nlit = 0;
+            ne.rep[0] = pe.rep[0]; ne.rep[1] = pe.rep[1]; ne.rep[2] = pe.rep[2];
+            uint32_t tail;
+            bool carry = false;                                                  // a carried repeat offset the reference keeps and fast_block / dfast_block drop
+            uint32_t dict_idx = 2;
+            if (!ext) {
+                const uint32_t low_idx = pos > wsize ? pos + 2 - wsize : 2;      // window.lowLimit, which window.dictLimit follows up
+                dict_idx = max(wrap + 2, low_idx);
+                const uint32_t prefix_idx = end > wsize ? end + 2 - wsize : 2;
+                const uint32_t cur_idx = pos + 2 + (pos + 2 == prefix_idx ? 1u : 0u);
+                const uint32_t ref_max = cur_idx - (cur_idx - dict_idx > wsize ? cur_idx - wsize : dict_idx);
+                const uint32_t dev_max = cur_idx - (cur_idx - prefix_idx > wsize ? cur_idx - wsize : prefix_idx);
+                carry = (ne.rep[0] > dev_max && ne.rep[0] <= ref_max) || (ne.rep[1] > dev_max && ne.rep[1] <= ref_max);
+            }
+            if constexpr (kFast == 1) tail = ext ? fast_block_ext(L, S, tab, P, ne.rep, src, pos, end, end + 2 - wsize, wrap + 2, lane)
+                                           : carry ? fast_block_carry(S, tab, P, ne.rep, src, pos, end, dict_idx, lane)
+                                                   : fast_block(L, S, tab, P, ne.rep, src, pos, end, n, false, lane);
+            else tail = ext ? dfast_block_ext(L, S, tab, tab_s, P, ne.rep, src, pos, end, end + 2 - wsize, wrap + 2, lane)
+                      : carry ? dfast_block_carry(S, tab, tab_s, P, ne.rep, src, pos, end, dict_idx, lane)
+                              : dfast_block(L, S, tab, tab_s, P, ne.rep, src, pos, end, false, lane);
+            gather_literals(S, src, pos, lane);
+            copy_bytes(S.lit + S.nlit, src + pos + len - tail, tail, lane);
+            S.nlit += tail;
+            const bool suspect = S.nseq == 0 || S.nlit / S.nseq >= 20;
+            const int lsz = compress_literals(L, cur, pe, ne, aout, bcap, S.lit, S.nlit, suspect, P.strat, lane);
+            c = lsz;
+            if (lsz >= 0) {
+                const int ssz = encode_sequences(L, aout + lsz, bcap - uint32_t(lsz), S, P.strat, pe, ne, prevfse, tmp, tables_built, lane);
+                c = ssz <= 0 ? ssz : lsz + ssz;
+            }
+            if (c == kErrTooSmall && len <= bcap) c = 0;
+            if (c < 0) { err = c; return; }
+            if (c > 0 && uint32_t(c) >= len - ((len >> 6) + 2)) c = 0;
+            if (!first && c < 25 && is_rle(src + pos, len, lane)) {
+                if (cap - o < 4) { err = kErrTooSmall; return; }
+                c = 1; if (lane == 0) out[0] = src[pos];
+            }
+            if (c > 1 && side) {
+                if (uint32_t(c) > cap - o - 3) { err = kErrTooSmall; return; }
+                copy_bytes(out, aout, uint32_t(c), lane);
+            }
+            if (c > 1) { cur ^= 1; pe = ne; }                                     // ZSTD_blockState_confirmRepcodesAndEntropyTables (fast / dfast never reuse FSE tables)
+            if (kept) out[len + lane] = keep;
+            if (c == 1 && kept1) out[1 + lane] = keep1;
+        }
+        if (c == 0) {
+            const uint32_t h = last + (len << 3);
+            if (len + 3 > cap - o) { err = kErrTooSmall; return; }
+            if (lane < 3) dst[o + lane] = uint8_t(h >> (8 * lane));
+            copy_bytes(dst + o + 3, src + pos, len, lane);
+            o += 3 + len;
+        } else {
+            const uint32_t h = c == 1 ? last + (1u << 1) + (len << 3) : last + (2u << 1) + (uint32_t(c) << 3);
+            if (lane < 3) dst[o + lane] = uint8_t(h >> (8 * lane));
+            o += 3 + uint32_t(c);
+        }
+        pos += len; first = false; k++; in_cycle++;
+    }
+    if ((n & (kSub - 1)) == 0) {                                                 // ZSTD_endStream with nothing buffered: ZSTD_writeEpilogue's empty raw last block
+        if (cap - o < 3) { err = kErrTooSmall; return; }
+        if (lane < 3) dst[o + lane] = lane == 0 ? uint8_t(1) : uint8_t(0);
+        o += 3; k++;
+    }
+    out_bytes = o; out_blocks = k;
+}
+
+template <int kFast>
+__device__ __forceinline__ void zst_stream_one(ZLds& L, const uint8_t* __restrict__ src_base, uint8_t* img_base, fourmc_zstw_item* items,
+                                               const fourmc_zstw_job* jobs, uint32_t njobs, uint8_t* work_base)
+{
+    const uint32_t b = blockIdx.x;
+    if (b >= njobs) return;
+    const int lane = threadIdx.x;
+    const fourmc_zstw_job job = jobs[b];
+    // (the descriptor arrives through vector loads: pin what is derived from it to scalar registers, as zstd_encode_one does)
+    fourmc_zstw_item* const it = items + U(job.item);
+    const int level = Ui(job.level);
+    const uint32_t n = U(uint32_t(it->src_bytes));
+    const uint64_t cap64 = U64(it->image_cap);
+    const uint32_t cap = cap64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(cap64);  // (an image is shorter than 4 GiB: the source ends at 3 GiB)
+    const uint8_t* src = src_base + U64(it->src_off);
+    uint8_t* dst = img_base + U64(it->image_off);
+    uint32_t bytes, blocks; int err;
+    zstd_stream_frame<kFast>(L, src, n, dst, cap, work_base + U64(job.work_off), level, lane, bytes, blocks, err);
+    if (lane == 0) {
+        it->status.image_bytes = err ? 0 : bytes; it->status.blocks = err ? 0 : blocks;
+        it->status.reason = err ? FOURMC_ZSTW_DST_SMALL : FOURMC_ZSTW_OK; it->status.codec_result = err; it->status.pad = 0;
+    }
+}
+
+// one wave per stream of a "fast" level (1, 2)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void zst_stream_fast_kernel(const uint8_t* __restrict__ src_base, uint8_t* img_base, fourmc_zstw_item* items, const fourmc_zstw_job* jobs, uint32_t njobs, uint8_t* work_base)
+{
+    __shared__ ZLds L;
+    zst_stream_one<1>(L, src_base, img_base, items, jobs, njobs, work_base);
+}
+
+// one wave per stream of a "dfast" level (3, 4)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void zst_stream_dfast_kernel(const uint8_t* __restrict__ src_base, uint8_t* img_base, fourmc_zstw_item* items, const fourmc_zstw_job* jobs, uint32_t njobs, uint8_t* work_base)
+{
+    __shared__ ZLds L;
+    zst_stream_one<2>(L, src_base, img_base, items, jobs, njobs, work_base);
+}
+
 } // namespace
+
+// the strategy of a level's row for an unknown source size: 1 fast, 2 dfast, 0 for a level the streamed kernels do not take
+extern "C" int fourmc_zst_stream_strategy(int level)
+{
+    if (level < 1 || level > kMaxLevel) return 0;
+    const uint32_t st = kLevelRows[level - 1][0].strat;
+    return st == 1 || st == 2 ? int(st) : 0;
+}
+
+extern "C" hipError_t fourmc_launch_zst_stream(const void* d_src, void* d_images, fourmc_zstw_item* d_items, const fourmc_zstw_job* d_jobs,
+                                               uint32_t n_fast, uint32_t n_dfast, void* d_work, hipStream_t stream)
+{
+    const uint8_t* s8 = static_cast<const uint8_t*>(d_src); uint8_t* d8 = static_cast<uint8_t*>(d_images); uint8_t* w8 = static_cast<uint8_t*>(d_work);
+    // the jobs of the fast levels come first in d_jobs, the dfast ones behind them
+    if (n_fast) hipLaunchKernelGGL(zst_stream_fast_kernel, dim3(n_fast), dim3(64), 0, stream, s8, d8, d_items, d_jobs, n_fast, w8);
+    if (n_dfast) hipLaunchKernelGGL(zst_stream_dfast_kernel, dim3(n_dfast), dim3(64), 0, stream, s8, d8, d_items, d_jobs + n_fast, n_dfast, w8);
+    return hipGetLastError();
+}
 
 extern "C" int fourmc_zstd_enc_level_ok(int level) { return level >= 1 && level <= kMaxLevel; }
 extern "C" size_t fourmc_zstd_enc_work_bytes(uint32_t n, int level) { return size_t(n) * (kStoreBytes + table_bytes(level)); }

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .binding import (ZST_REASONS, ZstItem, ZstStatus, BLOCK_DTYPE, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, CODEC_LZ4_FAST, BstreamEncItem, BstreamItem, BstreamStatus, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines, ImageRef, ImageSplitItem,
+from .binding import (ZST_REASONS, ZSTW_REASONS, ZstItem, ZstStatus, ZstwItem, ZstwStatus, BLOCK_DTYPE, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, CODEC_LZ4_FAST, BstreamEncItem, BstreamItem, BstreamStatus, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines, ImageRef, ImageSplitItem,
                       ImagesSlice, ImagesSplitItem,
                       ImageRange, ImageRecords, ImageSlice, ImageStatus, check, lib)
 
@@ -339,6 +339,49 @@ def zst_stats():
     c = (C.c_ulonglong * 3)()
     lib().fourmc_gpu_zst_stats(C.byref(c, 0), C.byref(c, 8), C.byref(c, 16))
     return {"fast_frames": int(c[0]), "serial_frames": int(c[1]), "fast_blocks": int(c[2])}
+
+
+def zst_bound(n):
+    """Capacity that holds the .zst image of every source of n bytes (fourmc_gpu_zst_bound)."""
+    return int(lib().fourmc_gpu_zst_bound(int(n)))
+
+
+def zst_codec_level(v):
+    """The level ZstCodec hands to zstd for a configured io.compress.zst.compression.level of v (fourmc_zst_codec_level)."""
+    return int(lib().fourmc_zst_codec_level(int(v)))
+
+
+def _zstw_dict(st):
+    res = {name: int(getattr(st, name)) for name, _ in ZstwStatus._fields_ if name != "pad"}
+    res["name"] = ZSTW_REASONS[st.reason] if 0 <= st.reason < len(ZSTW_REASONS) else "?"
+    res["message"] = lib().fourmc_gpu_zstw_reason_text(st.reason).decode()
+    return res
+
+
+def compress_zst(d_src, d_image, level=1, src_bytes=None, stream=None):
+    """Write the .zst file of d_src[:src_bytes] (default: the whole tensor) into d_image, whose length is the capacity
+    (fourmc_gpu_zst_compress): the bytes of ZSTD_initCStream(level), ZSTD_compressStream, ZSTD_endStream.  Returns the status as a
+    dict: image_bytes, blocks, reason (a FOURMC_ZSTW_* number), codec_result, "name" (its entry of ZSTW_REASONS) and "message"."""
+    n = _image_len(d_src, src_bytes, "compress_zst")
+    st = ZstwStatus()
+    src = _dev_ptr(d_src, "compress_zst d_src") if d_src.numel() else 0
+    check(lib().fourmc_gpu_zst_compress(src, n, _dev_ptr(d_image, "compress_zst d_image"), d_image.numel(), int(level), C.byref(st),
+                                        _stream_ptr(stream)), "fourmc_gpu_zst_compress")
+    return _zstw_dict(st)
+
+
+def compress_zsts(d_src, items, d_images, src_total=None, stream=None):
+    """Write many .zst files with one call (fourmc_gpu_zsts_compress).  `items` is a sequence of (src_off, src_bytes, image_off,
+    image_cap, level); levels may differ.  Returns one status dict per item, each what compress_zst returns for that stream alone."""
+    n = _image_len(d_src, src_total, "compress_zsts")
+    src = _dev_ptr(d_src, "compress_zsts d_src") if d_src.numel() else 0
+    q = [tuple(int(v) for v in it) for it in items]
+    arr = (ZstwItem * max(len(q), 1))()
+    for i, (so, sb, io, ic, lv) in enumerate(q):
+        arr[i].src_off, arr[i].src_bytes, arr[i].image_off, arr[i].image_cap, arr[i].level = so, sb, io, ic, lv
+    check(lib().fourmc_gpu_zsts_compress(src, n, _dev_ptr(d_images, "compress_zsts d_images"), d_images.numel(), C.cast(arr, C.c_void_p),
+                                         len(q), _stream_ptr(stream)), "fourmc_gpu_zsts_compress")
+    return [_zstw_dict(arr[i].status) for i in range(len(q))]
 
 
 def _image_len(d_image, image_bytes, what):

@@ -750,6 +750,58 @@ void fourmc_gpu_zst_stats(unsigned long long* fast_frames, unsigned long long* s
 void     fourmc_gpu_set_zst_round_blocks(uint32_t blocks);
 uint32_t fourmc_gpu_get_zst_round_blocks(void);
 
+/* ---- .zst streams written in device memory: the part files of ZstCodec, many with one call ----
+ * The image written for (src, level) is, byte for byte, what the reference's C calls give: ZSTD_initCStream(cs, level), then
+ * ZSTD_compressStream over the whole source with no flush and no pledged size, then ZSTD_endStream (jniZStreamCompressor.c:86-137).
+ * One frame: no content size, a window descriptor, no checksum, no dictionary ID; every block but the last is a full 128 KiB block;
+ * the last block is ZSTD_endStream's: the rest of the source, or - after a source that is a non-zero multiple of 128 KiB - an empty
+ * 3-byte block.  The empty source gives header + empty block, 9 bytes: the reference of the tests (tests/zst_model.py zstcodec)
+ * makes its ZSTD_compressStream call with zero bytes, which starts the frame with an unknown size; a caller that goes from
+ * ZSTD_initCStream straight to ZSTD_endStream gets the pledged-size-0 header 20 00 instead, which is not written here.  The bytes do
+ * not depend on how a writer cuts its input into compressStream calls (tests/test_zst_write_cpu.py shows it on the reference).
+ * Levels.  `level` is what ZSTD_initCStream gets: 1 and 2 (strategy "fast", window 512 KiB and 1 MiB), 3 and 4 ("dfast", 2 MiB), the
+ *   parameter rows for an unknown source size.  fourmc_zst_codec_level maps the value configured for ZstCodec
+ *   (io.compress.zst.compression.level) as ZstCodec.java:118-122 does: <= 0 or >= 23 becomes 3, every other value is itself.  Levels
+ *   5 .. 22 get FOURMC_ZSTW_LEVEL (their match finders have no external-dictionary mode on the device), any other value too.
+ * Length.  A source above 0xC0000000 bytes (3 GiB) gets FOURMC_ZSTW_TOO_LONG: below it no index reaches the reference's overflow
+ *   correction, which is not reproduced.
+ * Capacity.  fourmc_gpu_zst_bound(n) = 6 + n + 3 * (n / 131072 + 1) holds every image (all blocks stored raw, plus the empty last
+ *   block): with image_cap >= the bound every source is written, the sources of 1 and 2 bytes and those with a last block of 1 or 2
+ *   bytes included.  image_cap may be smaller: an image that does not fit gets FOURMC_ZSTW_DST_SMALL with codec_result = the
+ *   encoder's error (-70), image_bytes 0, the bytes of its region unspecified.  Below the bound an image is written for certain when
+ *   image_cap >= its length + 131075 (one more raw block); with less room a block that would have fit compressed may be refused.
+ *   Never are other bytes than the reference's reported as written.
+ * Verdicts per item; a refused item (_LEVEL, _TOO_LONG: decided on the host, nothing of it reaches the device) or a failing one
+ *   costs only itself.  Nothing is written outside [image_off, image_off + image_cap) of an item.
+ * Arguments, checked on the host before any device is looked for, with `items` untouched: items NULL with n > 0; d_src NULL with a
+ *   nonzero src_bytes; d_images NULL with a nonzero image_cap; a source outside [0, src_total) (sources of _TOO_LONG items are not
+ *   looked at: they are never read); an image region outside [0, images_bytes); two regions of nonzero image_cap that overlap:
+ *   FOURMC_EINVAL.  n == 0: FOURMC_OK.  Two items may name the same source bytes.
+ * Work.  A stream is one chain (every block's parse depends on the tables and repeat offsets the blocks before it left), so one wave
+ *   runs one stream and the parallelism is the number of streams: one launch per strategy present ("fast": levels 1, 2; "dfast": 3,
+ *   4), one upload (items and jobs), one read-back (the items with their status).  Workspace per stream: what the block encoder
+ *   takes for one block of its level.  Synchronizations of `stream`: one.  The single call is the n = 1 case of the same function.
+ * What ZstdStreamCompressor.java does differently (read from its code, :195-270, with CompressorStream.finish; no JVM ran): with no
+ *   input at all compress() returns at :227-232 before endStream is ever called, so the Java writer emits zero bytes; and when the
+ *   total input is a non-zero multiple of ZSTD_CStreamInSize() = 131072 its direct buffer is empty at finish(), the same return
+ *   fires and the frame is left without its last block.  The device always writes the terminated frame: in the second case the
+ *   Java bytes plus 01 00 00.  The readers (zstd -d, ZstdStreamDecompressor, fourmc_gpu_zst_decompress) take both. */
+enum { FOURMC_ZSTW_OK = 0, FOURMC_ZSTW_DST_SMALL = 1, FOURMC_ZSTW_LEVEL = 2, FOURMC_ZSTW_TOO_LONG = 3 };
+typedef struct fourmc_zstw_status {     /* 24 bytes */
+    uint64_t image_bytes;    /* length of the image; 0 unless FOURMC_ZSTW_OK */
+    uint32_t blocks;         /* blocks of the frame, the empty last one included */
+    int32_t  reason;         /* FOURMC_ZSTW_* */
+    int32_t  codec_result;   /* 0, or the negative ZSTD error number of FOURMC_ZSTW_DST_SMALL */
+    uint32_t pad;
+} fourmc_zstw_status;
+typedef struct fourmc_zstw_item { uint64_t src_off, src_bytes, image_off, image_cap; int32_t level, pad; fourmc_zstw_status status; } fourmc_zstw_item;   /* 64 bytes */
+uint64_t fourmc_gpu_zst_bound(uint64_t src_bytes);   /* 6 + src_bytes + 3 * (src_bytes / 131072 + 1): every block raw, plus the empty last block */
+int fourmc_zst_codec_level(int configured);          /* ZstCodec.java:118-122: <= 0 or >= 23 -> 3 */
+int fourmc_gpu_zst_compress (const void* d_src, uint64_t src_bytes, void* d_image, uint64_t image_cap, int level, fourmc_zstw_status* status, void* stream);
+int fourmc_gpu_zsts_compress(const void* d_src, uint64_t src_total, void* d_images, uint64_t images_bytes, fourmc_zstw_item* items /*host*/, uint32_t n, void* stream);
+/* a short fixed text for a FOURMC_ZSTW_* verdict ("" for FOURMC_ZSTW_OK) */
+const char* fourmc_gpu_zstw_reason_text(int reason);
+
 /* ---- block streams from a job's write() calls, many per call ----------------------------------------------------------------------
  * bstream_compress above cuts its source at one fixed group_bytes.  A job's stream is shaped by the sizes of its write() calls, and
  * this call takes those: every stream the writer can write (tests/bstream_model.py restates it) is written here byte for byte, many
