@@ -96,7 +96,7 @@ void fourmc_gpu_set_zstd_decode_split(int on);
 int  fourmc_gpu_get_zstd_decode_split(void);
 /* Statistics (read-only, not part of the reference boundary): one-block host calls made so far (the LZ4_* / ZSTD_* twins and the
  * JNI entry points: one call = one block) and the launches that served them - calls that arrive while a launch is in flight
- * share the next one (engine.hip: host_one), so launches < calls under concurrency. */
+ * share the next one (engine_host.hip: host_one), so launches < calls under concurrency. */
 void fourmc_gpu_one_block_stats(unsigned long long* calls, unsigned long long* launches);
 /* The engine keeps one device workspace per stream and reuses it (the segment-parallel LZ4 decode of 8192 blocks needs 92 GB, the zstd
  * level-12 encoder 48 MiB per block).  This frees them all, synchronizing each stream first; the next call allocates again. */
