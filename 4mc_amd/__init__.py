@@ -16,13 +16,14 @@ from .binding import (  # noqa: F401
     BLOCK_DTYPE, BLOCKSIZE, MAGIC_4MC, MAGIC_4MZ, CODEC_LZ4_FAST, CODEC_LZ4_MC, CODEC_LZ4_HC,
     CODEC_ZSTD, BLK_BADSUM, BLK_CORRUPT, EngineError, lib, lib_path, research_lib_path, use_research, cli_path, exported_symbols,
     make_blocks, gpu_init, ImageStatus, ImageItem, ImageEncItem, ImageEntry, ImageIndexInfo, ImageRange, IMAGE_ENTRY_DTYPE, ImageSlice, ImageRecords, ImageLines, ImageSplitItem,
-    ImageRef, ImagesSplitItem, ImagesSlice, BstreamStatus, BstreamItem, BstreamEncItem, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, bstream_codec,
+    ImageRef, ImagesSplitItem, ImagesSlice, ImageLineEntry, ImageLineInfo, ImageLinesAt, IMAGE_LINE_ENTRY_DTYPE, BstreamStatus, BstreamItem, BstreamEncItem, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, bstream_codec,
     ZstStatus, ZstItem, ZST_REASONS, ZstwStatus, ZstwItem, ZSTW_REASONS,
 )
 from .engine import (  # noqa: F401
     lz4_decompress, zstd_decompress, zstd_compress, lz4_compress_fast, lz4_compress_hc, lz4_compress_mc, xxh32, encode_blocks, decode_blocks, pack_image, DeviceBatch, release_workspaces,
     compress_image, compress_images, decompress_image, decompress_images, image_bound, image_parse_stats, image_index, image_decode_blocks, image_read, image_align_slices, image_read_records, image_read_lines, image_read_lines_batch, image_lines_batch_stats, ImageWriter,
     images_read_lines, images_lines_stats, images_align_slices,
+    image_line_index, image_read_lines_at, image_lines_at_stats,
     ImageReader,
     bstream_max_input, bstream_bound, compress_bstream, decompress_bstream, decompress_bstreams, compress_bstreams, bstream_writes_bound,
     decompress_zst, decompress_zsts, zst_stats,

@@ -163,6 +163,22 @@ class ImagesSlice(C.Structure):
     _fields_ = [("image", C.c_uint32), ("pad", C.c_uint32), ("s", ImageSlice)]
 
 
+# struct fourmc_image_line_entry / fourmc_image_line_info / fourmc_image_lines_at (include/fourmc_gpu.h: lines by number)
+class ImageLineEntry(C.Structure):
+    _fields_ = [("ends_before", C.c_uint64), ("ends", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ImageLineInfo(C.Structure):
+    _fields_ = [("result", C.c_int64), ("lines", C.c_uint64), ("ends", C.c_uint64), ("total_bytes", C.c_uint64),
+                ("nblocks", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class ImageLinesAt(C.Structure):
+    _fields_ = [("result", C.c_int64), ("served", C.c_uint64), ("blocks_staged", C.c_uint64), ("rounds", C.c_uint64)]
+
+
+IMAGE_LINE_ENTRY_DTYPE = np.dtype([("ends_before", "<u8"), ("ends", "<u4"), ("flags", "<u4")])
+assert C.sizeof(ImageLineEntry) == 16 and C.sizeof(ImageLineInfo) == 40 and C.sizeof(ImageLinesAt) == 32 and IMAGE_LINE_ENTRY_DTYPE.itemsize == 16
 assert C.sizeof(ImageRef) == 16 and C.sizeof(ImagesSplitItem) == 96 and C.sizeof(ImagesSlice) == 56
 assert C.sizeof(ImageSlice) == 48 and C.sizeof(ImageRecords) == 40 and C.sizeof(ImageLines) == 40 and C.sizeof(ImageSplitItem) == 88
 IMAGE_ENTRY_DTYPE = np.dtype([("image_off", "<u8"), ("data_off", "<u8"), ("usize", "<u4"), ("csize", "<u4"),
@@ -260,6 +276,10 @@ _GPU_API = {
     "fourmc_gpu_image_read_lines_batch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                                     C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_image_lines_batch_stats": (None, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_image_line_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_image_read_lines_at": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                 C.c_uint32, C.c_uint8, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fourmc_gpu_image_lines_at_stats": (None, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_images_read_lines": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
                                                C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_images_lines_stats": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -357,6 +357,44 @@ hipError_t fourmc_launch_lines_batch_finish(const fourmc_lines_span* d_spans, ui
 hipError_t fourmc_launch_lines_batch_write(const fourmc_lines_span* d_spans, const uint64_t* d_first_tile, uint32_t ns,
                                            const uint64_t* d_cnt, uint64_t ntiles, uint64_t longest, uint32_t max_line_len,
                                            const fourmc_records_state* d_st, hipStream_t s);
+/* Lines by number (lineat.hip, fourmc_gpu_image_line_index / _image_read_lines_at).  Blocks are staged one per slot of `stride`
+ * bytes (a multiple of 16, the staging 16-byte aligned), block d_list[j] - or first + j where there is no list - in slot j. */
+/* what the index's count launch leaves per block: its line ends with a CR in its last byte counted as one, and
+ * info bit 0: the last byte is CR, bit 1: the first byte is LF, bit 2: the block is damaged, bit 3: the last byte is LF,
+ * bits 8..31: the offset just behind its last end other than a CR in its last byte (0: none) */
+typedef struct fourmc_lineat_blk { uint32_t cnt, info; } fourmc_lineat_blk;
+typedef struct fourmc_lineat_sum { int64_t result; uint64_t lines, ends, total; } fourmc_lineat_sum;
+/* one request between the rounds: its line's start (~0: not known before bp has been staged), the blocks holding end k - 1 and
+ * end k, and the ranks of those ends inside them (je ~0u: the final unterminated line, which ends with the content) */
+typedef struct fourmc_lineat_req { uint64_t start; uint32_t bp, be, js, je; } fourmc_lineat_req;    /* 24 bytes */
+typedef struct fourmc_lineat_counts { uint32_t needed, served; } fourmc_lineat_counts;
+hipError_t fourmc_launch_lineat_desc(const fourmc_image_entry* d_ent, const uint32_t* d_list, uint32_t first, uint32_t m, uint64_t stride,
+                                     fourmc_block* d_desc, hipStream_t s);
+/* a workgroup per staged block first + j: d_blk[first + j] */
+hipError_t fourmc_launch_lineat_block_count(const void* d_stage, uint64_t stride, const fourmc_image_entry* d_ent, uint32_t first,
+                                            const fourmc_block* d_desc, uint32_t m, fourmc_lineat_blk* d_blk, hipStream_t s);
+/* one workgroup over all blocks: the seams, the flags, the 64-bit prefix; the entries (when d_index and nb + 1 <= cap) and *d_sum */
+hipError_t fourmc_launch_lineat_index_finish(const fourmc_image_entry* d_ent, const fourmc_lineat_blk* d_blk, uint32_t nb, uint64_t total,
+                                             fourmc_image_line_entry* d_index, uint64_t cap, fourmc_lineat_sum* d_sum, hipStream_t s);
+/* every status = code, every text_len = 0 */
+hipError_t fourmc_launch_lineat_fill(int32_t* d_status, uint32_t* d_text_len, uint32_t n, int32_t code, hipStream_t s);
+/* one lane per request: d_req[i], status 0 (-3: no such line) and text_len 0, and d_flags[b] = 1 for the blocks it needs; then a
+ * wave per refused request pads its row.  L = min(row_bytes, max_line_len).  d_flags (nb words) must be zero. */
+hipError_t fourmc_launch_lineat_locate(const fourmc_image_entry* d_ent, uint32_t nb, uint64_t total, const fourmc_image_line_entry* d_index,
+                                       const uint64_t* d_lines, uint32_t n, uint32_t L, fourmc_lineat_req* d_req, uint32_t* d_flags,
+                                       uint8_t* d_rows, uint32_t row_bytes, uint8_t pad, uint32_t* d_text_len, int32_t* d_status, hipStream_t s);
+/* the marked blocks in ascending order into d_list, their number into d_counts->needed */
+hipError_t fourmc_launch_lineat_compact(const uint32_t* d_flags, uint32_t nb, uint32_t* d_list, fourmc_lineat_counts* d_counts, hipStream_t s);
+/* per round of m staged blocks: the line ends of every 16 KiB tile, FOURMC_BLOCKSIZE / FOURMC_RECORDS_TILE words per slot */
+hipError_t fourmc_launch_lineat_tiles(const void* d_stage, uint64_t stride, const fourmc_image_entry* d_ent, const uint32_t* d_list, uint32_t m,
+                                      uint32_t* d_tcnt, hipStream_t s);
+/* a wave per request: resolve what this round's blocks can, copy what lies in them, finish the request in the round of be */
+hipError_t fourmc_launch_lineat_resolve(const void* d_stage, uint64_t stride, const fourmc_image_entry* d_ent, const fourmc_image_line_entry* d_index,
+                                        const uint32_t* d_list, const fourmc_block* d_desc, uint32_t m, const uint32_t* d_tcnt,
+                                        fourmc_lineat_req* d_req, uint32_t n, uint32_t max_line_len, uint8_t* d_rows, uint32_t row_bytes,
+                                        uint8_t pad, uint32_t* d_text_len, int32_t* d_status, hipStream_t s);
+/* d_counts->served += the requests with status 1 */
+hipError_t fourmc_launch_lineat_served(const int32_t* d_status, uint32_t n, fourmc_lineat_counts* d_counts, hipStream_t s);
 /* Hadoop block streams (bstream.hip, fourmc_gpu_bstream_*): what run 1 of the walk leaves per stream for the engine's read-back */
 typedef struct fourmc_bstream_walk {    /* 40 bytes */
     uint64_t chunks;        /* chunks of the well-formed groups, in file order, before the walk stopped */

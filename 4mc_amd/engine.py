@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .binding import (ZST_REASONS, ZSTW_REASONS, ZstItem, ZstStatus, ZstwItem, ZstwStatus, BLOCK_DTYPE, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, CODEC_LZ4_FAST, BstreamEncItem, BstreamItem, BstreamStatus, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines, ImageRef, ImageSplitItem,
+from .binding import (ZST_REASONS, ZSTW_REASONS, ZstItem, ZstStatus, ZstwItem, ZstwStatus, BLOCK_DTYPE, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, CODEC_LZ4_FAST, BstreamEncItem, BstreamItem, BstreamStatus, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines, ImageLineInfo, ImageLinesAt, ImageRef, ImageSplitItem,
                       ImagesSlice, ImagesSplitItem,
                       ImageRange, ImageRecords, ImageSlice, ImageStatus, check, lib)
 
@@ -541,6 +541,62 @@ def image_lines_batch_stats():
     g, r, d = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
     lib().fourmc_gpu_image_lines_batch_stats(C.byref(g), C.byref(r), C.byref(d))
     return int(g.value), int(r.value), int(d.value)
+
+
+def image_line_index(d_image, image_bytes=None, stream=None):
+    """The line index of the single-stream image d_image[:image_bytes] (fourmc_gpu_image_line_index): the whole image is decoded
+    once, in groups, and nothing of it is kept.  Returns (index, info): the index as an int64 CUDA tensor of shape [nblocks + 1, 2]
+    (16 bytes an entry: ends_before, then ends and flags; view its bytes through IMAGE_LINE_ENTRY_DTYPE on the host), None when
+    the image cannot be indexed or a block is damaged; info as a dict (result, lines, ends, total_bytes, nblocks)."""
+    ptr = _dev_ptr(d_image, "image_line_index d_image")
+    n = _image_len(d_image, image_bytes, "image_line_index")
+    head = ImageIndexInfo()
+    check(lib().fourmc_gpu_image_index(ptr, n, 0, 0, C.byref(head), _stream_ptr(stream)), "fourmc_gpu_image_index")
+    entries = max(int(head.nblocks), 0) + 1
+    index = torch.zeros((entries, 2), dtype=torch.int64, device=d_image.device)
+    info = ImageLineInfo()
+    check(lib().fourmc_gpu_image_line_index(ptr, n, _ptr(index), entries, C.byref(info), _stream_ptr(stream)), "fourmc_gpu_image_line_index")
+    res = {name: int(getattr(info, name)) for name, _ in ImageLineInfo._fields_ if name != "pad"}
+    return (index if res["result"] == 0 else None), res
+
+
+def image_read_lines_at(d_image, index, d_lines, row_bytes, max_line_len=0x7FFFFFFF, pad=0, image_bytes=None, stream=None):
+    """Lines by their numbers (fourmc_gpu_image_read_lines_at): `index` is image_line_index's tensor, `d_lines` an int64 CUDA tensor
+    of line numbers (it never visits the host; duplicates are fine).  Only the blocks those lines touch are decoded.  Returns a dict:
+    rows, a uint8 tensor [n, row_bytes] (row i: the first min(text_len[i], row_bytes) bytes of line d_lines[i]'s text, then `pad`);
+    text_len (int32: the text's length cut at max_line_len, so text_len > row_bytes says the row is a prefix); status (int32: 1
+    written, -3 no such line, -4 a block the line needs is damaged); out, the call's struct as a dict (result, served,
+    blocks_staged, rounds)."""
+    ptr = _dev_ptr(d_image, "image_read_lines_at d_image")
+    nbytes = _image_len(d_image, image_bytes, "image_read_lines_at")
+    if not (isinstance(index, torch.Tensor) and index.is_cuda and index.is_contiguous() and index.dtype == torch.int64 and index.dim() == 2
+            and index.shape[1] == 2):
+        raise EngineError("image_read_lines_at index: image_line_index's int64 CUDA tensor of shape [nblocks + 1, 2] is required")
+    if not (isinstance(d_lines, torch.Tensor) and d_lines.is_cuda and d_lines.is_contiguous() and d_lines.dtype == torch.int64 and d_lines.dim() == 1):
+        raise EngineError("image_read_lines_at d_lines: a contiguous one-dimensional int64 CUDA tensor is required")
+    if not 1 <= int(row_bytes) <= 0xFFFFFFFF:
+        raise EngineError("image_read_lines_at row_bytes: 1 .. 0xFFFFFFFF")
+    if not 0 <= int(max_line_len) <= 0x7FFFFFFF:
+        raise EngineError("image_read_lines_at max_line_len: 0 .. 0x7FFFFFFF")
+    n = d_lines.numel()
+    if n > 0xFFFFFFFF:
+        raise EngineError("image_read_lines_at d_lines: at most 0xFFFFFFFF requests")
+    rows = torch.empty((n, int(row_bytes)), dtype=torch.uint8, device=d_image.device)
+    text_len = torch.empty(n, dtype=torch.int32, device=d_image.device)
+    status = torch.empty(n, dtype=torch.int32, device=d_image.device)
+    out = ImageLinesAt()
+    check(lib().fourmc_gpu_image_read_lines_at(ptr, nbytes, _ptr(index), index.shape[0], _ptr(d_lines) if n else 0, n, int(max_line_len),
+                                               _ptr(rows) if n else 0, int(row_bytes), int(pad) & 0xFF, _ptr(text_len) if n else 0,
+                                               _ptr(status) if n else 0, C.byref(out), _stream_ptr(stream)), "fourmc_gpu_image_read_lines_at")
+    return {"rows": rows, "text_len": text_len, "status": status,
+            "out": {name: int(getattr(out, name)) for name, _ in ImageLinesAt._fields_}}
+
+
+def image_lines_at_stats():
+    """(rounds, block_decodes, blocks_staged) image_read_lines_at has run, made and staged so far in this process."""
+    r, d, b = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
+    lib().fourmc_gpu_image_lines_at_stats(C.byref(r), C.byref(d), C.byref(b))
+    return int(r.value), int(d.value), int(b.value)
 
 
 def _image_refs(images, who):

@@ -527,6 +527,78 @@ int fourmc_gpu_image_read_lines_batch(const void* d_image, uint64_t image_bytes,
  * it has run and the container block-decode calls it has made (one per tail round, one per group with a body block). */
 void fourmc_gpu_image_lines_batch_stats(unsigned long long* groups, unsigned long long* tail_rounds, unsigned long long* block_decodes);
 
+/* ---- lines by number -------------------------------------------------------------------------------------------------------
+ * The calls above hand out lines by split.  A consumer that samples (a shuffled text dataset, a join that fetches rows by id,
+ * NLineInputFormat-style cuts by line count) wants line k, and would have to decode and scan the whole image and keep the decoded
+ * copy to get it.  Here a small per-image LINE INDEX is built once, and a read decodes only the blocks its lines touch.
+ * The line rule is fourmc_gpu_image_read_lines': with D[0, T) the decoded content, a LINE END is a position p that ends a line; E is
+ * their number; lines = E + (T > 0 and T - 1 is no line end); line 0 starts at 0, line k > 0 one past end k - 1; line k ends at end
+ * k, or at T for the final unterminated line.
+ *
+ * fourmc_gpu_image_line_index.  Entry b, b < nblocks, of the index:
+ *   ends_before   the line ends in D[0, data_off[b]);
+ *   ends          the line ends inside block b;
+ *   flags bit 0   the block's last byte is a CR that ends nothing, because the next content byte is LF;
+ *         bit 1   the block's first byte is an LF whose previous content byte is CR, so its terminator is 2 bytes long;
+ *         bits 8..31   the offset in the block just behind its last line end (0: it has none; usize: its last byte is one) - where
+ *                 the line that leaves the block starts, which lets a read decode of a long line no block it will not copy from.
+ *   Entry nblocks is the sentinel {E, 0, 0}.  The seam rules look past blocks of usize 0, which fourmc_gpu_image_index accepts.
+ * info->result, in order of precedence: the index codes (info.nblocks < 0, else info.framing != 0, as in the random-access group;
+ *   nothing else of *info is then meaningful); -4 a block failed its XXH32, failed to decode or decoded to a size other than its
+ *   usize (nothing is written to d_index); -5 nblocks + 1 > index_cap with d_index not NULL (lines and ends are filled in, nothing is
+ *   written to d_index); else 0.  d_index NULL is a pure count.
+ * Work.  The image is decoded once, in groups of at most FOURMC_LINES_AT_GROUP blocks (env, read at every call; default 256,
+ *   clamped to 1..4096, like FOURMC_SPLIT_GROUP), each block into a staging slot of 4 MiB + 64 bytes kept with the stream.  Per
+ *   group: one descriptor launch, one container decode, one count launch (a workgroup per block; a CR in the block's last byte
+ *   counts as an end, and the launch records whether the last byte is CR or LF and the first LF).  One finish launch over all
+ *   blocks then subtracts the CR LF seams, sets the flags and writes the 64-bit prefix, so no group needs its neighbour's bytes.
+ *   Synchronizations of `stream`: 2 (the index summary, the result).
+ *
+ * fourmc_gpu_image_read_lines_at.  d_lines[0, n) are line numbers IN DEVICE MEMORY (a torch.randperm slice never visits the host).
+ *   Request i writes row i = d_rows[i * row_bytes, (i + 1) * row_bytes): d_text_len[i] = min(text length, max_line_len), exactly what
+ *   fourmc_gpu_image_read_lines puts in its d_text_len for that line; the row holds the first min(d_text_len[i], row_bytes) bytes of
+ *   the text, then `pad` up to row_bytes; a caller sees truncation as d_text_len[i] > row_bytes.  Fixed-stride rows on purpose: every
+ *   destination is known before any block is decoded, so rounds are independent and no block is decoded twice.
+ * d_status[i]: 1 written; -3 line >= lines (the row is all pad, text_len 0); -4 a block the request needed was damaged (the row is
+ *   unspecified, text_len 0; requests that do not need the block are unaffected).  Duplicate line numbers are allowed.
+ * out->result: the index code if the image cannot be indexed (every status then gets that code and every text_len 0); else the
+ *   number of requests with status 1, which is also out->served.  blocks_staged / rounds: the blocks this call decoded and the
+ *   rounds it took.
+ * The one rule.  For every k < lines, row k and text_len k equal line k of fourmc_gpu_image_read_lines(0, image_bytes, max_line_len)
+ *   on the same image: d_dst[d_starts[k], + min(d_text_len[k], row_bytes)) and d_text_len[k].
+ * Blocks a request needs, from the index and the footer entries alone (L = min(row_bytes, max_line_len)): bp, the block holding end
+ *   k - 1 (block 0 for k = 0); be, the block holding end k (the last block with bytes for the final unterminated line); and, when
+ *   be > bp, every block j between them with data_off[j] < s + L, where s = data_off[bp] + flags[bp] >> 8 is the line's start.
+ *   Blocks of a long line beyond its first L bytes are not decoded, except be.
+ * index_entries must equal nblocks + 1 (else FOURMC_EINVAL, after the index summary has been read).  The kernels clamp whatever they
+ *   read from d_index: an index that belongs to another image may give wrong rows, but never an access outside the call's regions.
+ *   Nothing is written outside d_rows[0, n * row_bytes), d_text_len[0, n) and d_status[0, n).
+ * Work.  A locate launch (one lane per request: binary searches over the index, marks the needed blocks), a scan that compacts
+ *   the marked blocks in ascending order, one read-back of their count.  Then rounds of at most FOURMC_LINES_AT_GROUP needed
+ *   blocks, each round: one descriptor launch, one container decode, one per-tile count launch over the staged blocks (16 KiB
+ *   tiles), one resolve-and-copy launch (a wave per request: rank / select over the tile counts and the 16-bit masks for the
+ *   line's start and end, the copy of the piece of its text that lies in this round's blocks, the pad and the status in the round
+ *   of be).  Synchronizations of `stream`: 3 (the index summary, the count of needed blocks, the result).
+ * Arguments, checked on the host before any device is looked for, each FOURMC_EINVAL with the outputs untouched: d_image NULL;
+ *   info / out NULL; d_lines, d_rows, d_text_len or d_status NULL with n > 0; d_index NULL for read_lines_at; row_bytes == 0;
+ *   max_line_len > 0x7FFFFFFF; n * row_bytes overflowing 64 bits.  n == 0 returns FOURMC_OK.  No device: FOURMC_ENODEV.
+ * Not here: the many-images form; packed output; a one-byte-delimiter form; the index inside the file (the format has no place). */
+typedef struct fourmc_image_line_entry { uint64_t ends_before; uint32_t ends; uint32_t flags; } fourmc_image_line_entry; /* 16 bytes */
+typedef struct fourmc_image_line_info  { int64_t result; uint64_t lines, ends, total_bytes; uint32_t nblocks, pad; } fourmc_image_line_info; /* 40 */
+int fourmc_gpu_image_line_index(const void* d_image, uint64_t image_bytes,
+                                fourmc_image_line_entry* d_index, uint64_t index_cap,
+                                fourmc_image_line_info* info /*host*/, void* stream);
+typedef struct fourmc_image_lines_at { int64_t result; uint64_t served, blocks_staged, rounds; } fourmc_image_lines_at;   /* 32 bytes */
+int fourmc_gpu_image_read_lines_at(const void* d_image, uint64_t image_bytes,
+                                   const fourmc_image_line_entry* d_index, uint64_t index_entries,
+                                   const uint64_t* d_lines /*device*/, uint32_t n, uint32_t max_line_len,
+                                   void* d_rows, uint32_t row_bytes, uint8_t pad,
+                                   uint32_t* d_text_len, int32_t* d_status,
+                                   fourmc_image_lines_at* out /*host*/, void* stream);
+/* Statistics (read-only): the rounds fourmc_gpu_image_read_lines_at has run so far in this process, the container block-decode calls
+ * it has made and the blocks it has staged. */
+void fourmc_gpu_image_lines_at_stats(unsigned long long* rounds, unsigned long long* block_decodes, unsigned long long* blocks_staged);
+
 /* ---- the lines of the splits of MANY images with one call --------------------------------------------------------------------
  * A Hadoop dataset is a directory of part files of a few blocks each (the case fourmc_gpu_images_decompress and _images_compress
  * were built for).  image_read_lines_batch takes the splits of ONE image: a job with a thousand part files in HBM makes a thousand
