@@ -120,10 +120,83 @@ int     orc_codec_zstd_decode(void* ctx, const uint8_t* src, int n, uint8_t* dst
 
 /* ZSTD_compress(dst, cap, src, n, level) for the 4mz encode path (zstd_enc_port.c) -
  * native/zstd/compress/zstd_compress.c:4806 as called by native/4mc.c:467.  Returns the frame size,
- * a negative ZSTD error number (-70 = dstSize_tooSmall), or ORC_ZSTD_UNSUPPORTED for levels the
- * port does not restate (only level 1 / strategy "fast" so far). */
+ * a negative ZSTD error number (-70 = dstSize_tooSmall), or ORC_ZSTD_UNSUPPORTED for a level outside
+ * 1..12 (the port restates every row of clevels.h for those twelve: fast, dfast, greedy, lazy, lazy2,
+ * btlazy2 and btopt).
+ *
+ * orc_zstd_compress_ex is the same call with an orc_trace (NULL: none, and nothing is computed for it).  The
+ * rules of orc_trace hold: a row is written whole or not at all, n[] counts also what found no room.  Tables
+ * (int32 rows; positions are offsets into the input):
+ *   ORC_TR_EMIT    one row per stored sequence and one for the last literals of every inner block (match length 0,
+ *                  off_base 0): inner block, start of the literals, literal length, off_base as stored (1..3: a
+ *                  repeat offset, which with literal length 0 names the next one: 1 -> rep2, 2 -> rep3,
+ *                  3 -> rep1 - 1), match length.  The rows of one block add up to its length.
+ *   ORC_TR_BLOCK   (the slot of ORC_TR_CAND) one row per inner block, ORC_ZBLK_* names its words.
+ *   ORC_TR_SEARCH  one row per search of the lazy family: ORC_ZSEARCH_HC / _ROW / _BT, ip, candidates compared,
+ *                  ORC_END_* (why the walk ended), the winner's number in the walk (-1: none), its length.
+ *                  btopt, one row per call of the match collector: ORC_ZSEARCH_OPT, ip, matches returned, 1 when the
+ *                  longest is beyond sufficient_len, 1 when the 3-byte hash table gave one, the longest length.
+ *   ORC_TR_ARM     ORC_ZARM_*, ip, a value (each arm says which). */
 #define ORC_ZSTD_UNSUPPORTED (-1000)
+enum { ORC_ZTR_SEARCH_WORDS = 6, ORC_ZTR_BLOCK_WORDS = 28, ORC_ZTR_ARM_WORDS = 3, ORC_ZTR_EMIT_WORDS = 5 };
+enum { ORC_TR_BLOCK = ORC_TR_CAND };
+enum { ORC_ZSEARCH_HC = 0, ORC_ZSEARCH_ROW = 1, ORC_ZSEARCH_BT = 2, ORC_ZSEARCH_OPT = 3 };
+enum { ORC_END_INPUT = 4 };                 /* the match ran to the end of the input: the walk stops there */
+enum {  /* words of a BLOCK row */
+    ORC_ZBLK_NUMBER = 0, ORC_ZBLK_START, ORC_ZBLK_LEN, ORC_ZBLK_STRATEGY /* 1 fast .. 7 btopt */, ORC_ZBLK_NSEQ, ORC_ZBLK_NLIT,
+    ORC_ZBLK_LIT_TYPE,      /* 0 raw, 1 rle, 2 Huffman with its table, 3 treeless; -1: no literals section was written */
+    ORC_ZBLK_LIT_STREAMS,   /* 1 or 4 for a Huffman attempt, 0 where none was made */
+    ORC_ZBLK_HUF_DROPPED,   /* ORC_ZHUF_* */
+    ORC_ZBLK_LL_TYPE, ORC_ZBLK_LL_RULE, ORC_ZBLK_OF_TYPE, ORC_ZBLK_OF_RULE, ORC_ZBLK_ML_TYPE, ORC_ZBLK_ML_RULE,   /* 0 predefined, 1 rle, 2 fse, 3 repeat (-1: no sequences); ORC_ZSEL_* */
+    ORC_ZBLK_OUTCOME,       /* ORC_ZOUT_* */
+    ORC_ZBLK_REP_IN,        /* rep[0..2] on entry */
+    ORC_ZBLK_REP_OUT = ORC_ZBLK_REP_IN + 3,   /* rep[0..2] on exit (the third moves in btopt alone) */
+    ORC_ZBLK_PARAMS = ORC_ZBLK_REP_OUT + 3    /* the row of the level table that ran, after the clamps: windowLog, chainLog, hashLog, searchLog, minMatch, targetLength */
+};
+enum { ORC_ZHUF_KEPT = 0, ORC_ZHUF_TOO_SMALL /* below the 63 / 6 byte floor: no attempt */, ORC_ZHUF_NO_GAIN /* attempt not smaller than n - minGain, or refused by the histogram */,
+       ORC_ZHUF_ONE_SYMBOL /* -> rle */ };
+enum { ORC_ZSEL_ONE_SYMBOL = 1 /* rle, or predefined for at most two sequences */, ORC_ZSEL_REPEAT_SMALL /* fast .. greedy: a valid table and fewer than 1000 sequences */,
+       ORC_ZSEL_PREDEF_FEW /* fast .. greedy: too few sequences or too flat for a table */, ORC_ZSEL_FSE_DEFAULT /* fast .. greedy: otherwise */,
+       ORC_ZSEL_COST_PREDEF, ORC_ZSEL_COST_REPEAT, ORC_ZSEL_COST_FSE /* lazy and above: the cheapest of the three estimates */ };
+enum { ORC_ZOUT_COMPRESSED = 0, ORC_ZOUT_RAW_NOT_SMALLER /* not below len - (len >> 6) - 2 */, ORC_ZOUT_RAW_TOO_SMALL /* dstSize_tooSmall with len <= the block's capacity */,
+       ORC_ZOUT_RLE, ORC_ZOUT_RAW_SHORT /* fewer than 7 bytes: no attempt */, ORC_ZOUT_REFUSED /* the frame ends with an error here */ };
+enum {  /* fast and dfast; value */
+    ORC_ZARM_F_HIT_IP0 = 1,         /* hash hit at ip0; step */
+    ORC_ZARM_F_HIT_IP1,             /* hash hit at ip1; step */
+    ORC_ZARM_F_REP_IP2,             /* repeat offset 1 at ip2; step */
+    ORC_ZARM_D_REP_IP1,             /* dfast: repeat offset 1 at ip + 1; step */
+    ORC_ZARM_D_LONG,                /* dfast: the 8-byte table hit at ip; step */
+    ORC_ZARM_D_SHORT,               /* dfast: the short table hit, the long table at ip + 1 did not; step */
+    ORC_ZARM_D_SHORT_THEN_LONG,     /* dfast: the short table hit and the long table at ip + 1 took over; step */
+    ORC_ZARM_STEP_UP,               /* the search step grew; the new step */
+    ORC_ZARM_CATCHUP,               /* ip = the match's start after the backward walk; bytes walked back */
+    ORC_ZARM_REP2_AFTER,            /* a repeat-offset-2 match right after a match; the iteration, from 1 */
+    ORC_ZARM_REP_ZEROED,            /* block start: repeat offsets beyond the window put aside; 1 = rep1, 2 = rep2, 3 = both */
+    ORC_ZARM_REP_RESTORED,          /* block end (ip = its end): put back; same bits */
+    ORC_ZARM_START_NEAR_REP,        /* a block after the first: its first match starts less than max(rep1, rep2) + 4 past the block's start (the offsets as the block got them); that maximum */
+    ORC_ZARM_END_BEHIND_ILIMIT,     /* a match ended behind ilimit: no table refill, no repeat loop; bytes left to the block's end */
+    ORC_ZARM_OUT_OF_WINDOW,         /* every strategy but btlazy2 / btopt: a candidate holding ip's four bytes refused because it lies below the window; its distance */
+    /* greedy, lazy, lazy2, btlazy2 */
+    ORC_ZARM_L_REP_IP1 = 20,        /* repeat offset 1 at ip + 1 found (greedy: taken at once); its length */
+    ORC_ZARM_L_SEARCH_WINS,         /* the search at ip beat it (or stood alone); its length */
+    ORC_ZARM_L_D1_REP, ORC_ZARM_L_D1_SEARCH, ORC_ZARM_L_D2_REP, ORC_ZARM_L_D2_SEARCH,   /* an improvement at depth 1 / 2, by repeat offset / by search; its length */
+    ORC_ZARM_L_CATCHUP,             /* as ORC_ZARM_CATCHUP */
+    ORC_ZARM_L_REP_LOOP,            /* as ORC_ZARM_REP2_AFTER */
+    ORC_ZARM_L_STEP_GROWN,          /* no match and the step to the next search is above 1; the step */
+    ORC_ZARM_L_NTU_LIMIT,           /* block start, greedy and above (the fast finders keep no next_to_update): it lay more than 384 behind and moved up; the gap closed to (<= 192) */
+    ORC_ZARM_BT_BATCH_FULL,         /* btlazy2: the stack of unsorted candidates reached nb_compares; that number */
+    ORC_ZARM_ROW_WRAPS,             /* row finder: an insert moved a row's head from 0 onto its last entry and that entry was in use: the row's inserts have gone round; entries per row */
+    ORC_ZARM_ROW_CACHE_AT_BLOCK,    /* row finder, a block after the first: the 8-entry hash cache is filled from next_to_update; 100000 + (block start - that position): above 100000 the cache starts with hashes of the previous block's last positions */
+    /* btopt */
+    ORC_ZARM_O_PREDEF = 40,         /* block start: predefined prices (at most 1024 bytes); the block's length */
+    ORC_ZARM_O_STATS,               /* block start: first-block statistics; the block's length */
+    ORC_ZARM_O_IMMEDIATE,           /* a match beyond sufficient_len taken at once; its length */
+    ORC_ZARM_O_ARRAY_FULL,          /* cur + length reached the price array's end (4096); cur + length */
+    ORC_ZARM_O_LL0_SHIFT,           /* a repeat-offset arrival with no literals before it: off_base names the next offset; off_base */
+    ORC_ZARM_O_NOT_GREEDY           /* the series' first sequence is not the longest match found at its start; the length given up */
+};
 int64_t orc_zstd_compress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, int level);
+int64_t orc_zstd_compress_ex(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, int level, orc_trace* trace);
 int     orc_codec_zstd1(void* ctx, const uint8_t* src, int n, uint8_t* dst, int cap);
 
 /* codec adaptors with the orc_block_codec_fn shape (ctx unused) */

@@ -544,7 +544,8 @@ static int64_t huf_compress(uint8_t* dst, size_t cap, const uint8_t* src, size_t
 }
 
 /* ------------------------------------------------------------------------------------------------ literals */
-typedef struct { huf_ct huf; int huf_repeat; uint32_t rep[3]; fse_ct fse[3]; int fse_repeat[3]; /* ll, of, ml */ } zentropy;
+typedef struct { huf_ct huf; int huf_repeat; uint32_t rep[3]; fse_ct fse[3]; int fse_repeat[3]; /* ll, of, ml */
+                 int32_t note[9]; /* for the trace's BLOCK row alone: literals type, streams, ORC_ZHUF_*, then type and ORC_ZSEL_* of ll, of, ml */ } zentropy;
 
 static int64_t raw_literals(uint8_t* dst, size_t cap, const uint8_t* src, size_t n, int rle)
 {
@@ -566,13 +567,17 @@ static int64_t compress_literals(const zentropy* prev, zentropy* next, uint8_t* 
     int single = n < 256, repeat = prev->huf_repeat, type = 2;
     int64_t c;
     next->huf = prev->huf; next->huf_repeat = prev->huf_repeat;
+    next->note[0] = 0; next->note[1] = 0; next->note[2] = ORC_ZHUF_TOO_SMALL;
     if (n <= (size_t)(prev->huf_repeat == REP_VALID ? 6 : 63)) return raw_literals(dst, cap, src, n, 0);
     if (cap < lh + 1) return ERR_TOOSMALL;
     if (repeat == REP_VALID && lh == 3) single = 1;
+    next->note[1] = single ? 1 : 4; next->note[2] = ORC_ZHUF_NO_GAIN;
     c = huf_compress(dst + lh, cap - lh, src, n, !single, &next->huf, &repeat, strat < 4 /* ZSTD_lazy */ && n <= 1024, suspect);
     if (repeat != REP_NONE) type = 3;
     if (c <= 0 || (size_t)c >= n - min_gain) { next->huf = prev->huf; return raw_literals(dst, cap, src, n, 0); }
+    next->note[0] = 1; next->note[2] = ORC_ZHUF_ONE_SYMBOL;
     if (c == 1) { next->huf = prev->huf; return raw_literals(dst, cap, src, n, 1); }
+    next->note[0] = type; next->note[2] = ORC_ZHUF_KEPT;
     if (type == 2) next->huf_repeat = REP_CHECK;
     if (lh == 3) { const uint32_t v = (uint32_t)type + ((uint32_t)!single << 2) + ((uint32_t)n << 4) + ((uint32_t)c << 14); dst[0] = (uint8_t)v; dst[1] = (uint8_t)(v >> 8); dst[2] = (uint8_t)(v >> 16); }
     else if (lh == 4) { const uint32_t v = (uint32_t)type + (2u << 2) + ((uint32_t)n << 4) + ((uint32_t)c << 18); memcpy(dst, &v, 4); }
@@ -654,14 +659,16 @@ static size_t fse_bit_cost(const fse_ct* ct, const uint32_t* count, unsigned max
 
 /* ZSTD_selectEncodingType (zstd_compress_sequences.c:153-239), no dictionary: 0 basic, 1 rle, 2 compressed, 3 repeat */
 static int select_type(int* repeat, const uint32_t* count, unsigned max, size_t most, size_t nseq, uint32_t fse_log,
-                       const fse_ct* prev, const int16_t* def_norm, uint32_t def_log, int def_ok, uint32_t strat)
+                       const fse_ct* prev, const int16_t* def_norm, uint32_t def_log, int def_ok, uint32_t strat, int32_t* rule)
 {
+    *rule = ORC_ZSEL_ONE_SYMBOL;
     if (most == nseq) { *repeat = REP_NONE; return (def_ok && nseq <= 2) ? 0 : 1; }
+    *rule = ORC_ZSEL_FSE_DEFAULT;
     if (strat < 4) {                                               /* < ZSTD_lazy */
         if (def_ok) {
             const size_t dyn_min = (((size_t)1 << def_log) * (10 - strat)) >> 3;
-            if (*repeat == REP_VALID && nseq < 1000) return 3;
-            if (nseq < dyn_min || most < (nseq >> (def_log - 1))) { *repeat = REP_NONE; return 0; }
+            if (*repeat == REP_VALID && nseq < 1000) { *rule = ORC_ZSEL_REPEAT_SMALL; return 3; }
+            if (nseq < dyn_min || most < (nseq >> (def_log - 1))) { *repeat = REP_NONE; *rule = ORC_ZSEL_PREDEF_FEW; return 0; }
         }
     } else {
         size_t basic = COST_ERR, rep = COST_ERR, nc, comp = 0;
@@ -683,8 +690,9 @@ static int select_type(int* repeat, const uint32_t* count, unsigned max, size_t 
             }
             comp = (nc << 3) + (comp >> 8);
         }
-        if (basic <= rep && basic <= comp) { *repeat = REP_NONE; return 0; }
-        if (rep <= comp) return 3;
+        if (basic <= rep && basic <= comp) { *repeat = REP_NONE; *rule = ORC_ZSEL_COST_PREDEF; return 0; }
+        if (rep <= comp) { *rule = ORC_ZSEL_COST_REPEAT; return 3; }
+        *rule = ORC_ZSEL_COST_FSE;
     }
     *repeat = REP_CHECK;
     return 2;
@@ -719,6 +727,7 @@ static int64_t encode_sequences(uint8_t* dst, size_t cap, const zseq* seq, size_
     size_t o = 0, last_count = 0;
     fse_ct* const ll = &ne->fse[0]; fse_ct* const of = &ne->fse[1]; fse_ct* const ml = &ne->fse[2];
     uint32_t count[64];
+    for (int k = 3; k < 9; k++) ne->note[k] = -1;
     if (cap < 4) return ERR_TOOSMALL;
     if (nseq < 128) dst[o++] = (uint8_t)nseq;
     else if (nseq < 0x7F00) { dst[o++] = (uint8_t)((nseq >> 8) + 0x80); dst[o++] = (uint8_t)nseq; }
@@ -732,21 +741,24 @@ static int64_t encode_sequences(uint8_t* dst, size_t cap, const zseq* seq, size_
         size_t most;
         max = 35; most = hist(count, &max, llc, nseq);
         ne->fse_repeat[0] = pe->fse_repeat[0];
-        tll = select_type(&ne->fse_repeat[0], count, max, most, nseq, 9, &pe->fse[0], kLLNorm, 6, 1, strat);
+        tll = select_type(&ne->fse_repeat[0], count, max, most, nseq, 9, &pe->fse[0], kLLNorm, 6, 1, strat, &ne->note[4]);
+        ne->note[3] = tll;
         r = build_seq_table(dst + o, cap - o, ll, &pe->fse[0], 9, tll, count, max, llc, nseq, kLLNorm, 6, 35);
         if (r < 0) return r;
         if (tll == 2) last_count = (size_t)r;
         o += (size_t)r;
         max = 31; most = hist(count, &max, ofc, nseq);
         ne->fse_repeat[1] = pe->fse_repeat[1];
-        tof = select_type(&ne->fse_repeat[1], count, max, most, nseq, 8, &pe->fse[1], kOFNorm, 5, max <= 28, strat);
+        tof = select_type(&ne->fse_repeat[1], count, max, most, nseq, 8, &pe->fse[1], kOFNorm, 5, max <= 28, strat, &ne->note[6]);
+        ne->note[5] = tof;
         r = build_seq_table(dst + o, cap - o, of, &pe->fse[1], 8, tof, count, max, ofc, nseq, kOFNorm, 5, 28);
         if (r < 0) return r;
         if (tof == 2) last_count = (size_t)r;
         o += (size_t)r;
         max = 52; most = hist(count, &max, mlc, nseq);
         ne->fse_repeat[2] = pe->fse_repeat[2];
-        tml = select_type(&ne->fse_repeat[2], count, max, most, nseq, 9, &pe->fse[2], kMLNorm, 6, 1, strat);
+        tml = select_type(&ne->fse_repeat[2], count, max, most, nseq, 9, &pe->fse[2], kMLNorm, 6, 1, strat, &ne->note[8]);
+        ne->note[7] = tml;
         r = build_seq_table(dst + o, cap - o, ml, &pe->fse[2], 9, tml, count, max, mlc, nseq, kMLNorm, 6, 52);
         if (r < 0) return r;
         if (tml == 2) last_count = (size_t)r;
@@ -788,7 +800,19 @@ typedef struct {
     zparams   p;
     zseq*     seq;  size_t nseq;
     uint8_t*  lit;  size_t nlit;
+    orc_trace* tr;  int32_t blk;  /* the trace (NULL: none) and the inner block's number */
 } zmatch;
+
+/* trace rows (oracle.h: ORC_ZTR_*): nothing but these three helpers writes one, and none of them touches the encoder's state */
+static void ztr_arm(const zmatch* m, int arm, size_t ip, size_t v)
+{ if (m->tr) { const int32_t row[ORC_ZTR_ARM_WORDS] = {arm, (int32_t)ip, (int32_t)v}; orc_tr_put(m->tr, ORC_TR_ARM, row, ORC_ZTR_ARM_WORDS); } }
+static void ztr_emit(const zmatch* m, size_t at, size_t ll, uint32_t off_base, size_t ml)
+{ if (m->tr) { const int32_t row[ORC_ZTR_EMIT_WORDS] = {m->blk, (int32_t)at, (int32_t)ll, (int32_t)off_base, (int32_t)ml}; orc_tr_put(m->tr, ORC_TR_EMIT, row, ORC_ZTR_EMIT_WORDS); } }
+static void ztr_search(const zmatch* m, int kind, size_t ip, uint32_t a, int b, int c, size_t len)
+{ if (m->tr) { const int32_t row[ORC_ZTR_SEARCH_WORDS] = {kind, (int32_t)ip, (int32_t)a, b, c, (int32_t)len}; orc_tr_put(m->tr, ORC_TR_SEARCH, row, ORC_ZTR_SEARCH_WORDS); } }
+/* a candidate below the window that holds the probe's four bytes: the refusal is what keeps the frame decodable */
+static void ztr_out_of_window(const zmatch* m, const uint8_t* s, uint32_t idx, size_t ip)
+{ if (m->tr && idx >= 2 && rd32(s + idx - 2) == rd32(s + ip)) ztr_arm(m, ORC_ZARM_OUT_OF_WINDOW, ip, ip + 2 - idx); }
 
 static uint32_t zhash(const uint8_t* p, uint32_t hlog, uint32_t mls)
 {
@@ -812,6 +836,7 @@ static void store_seq(zmatch* m, const uint8_t* s, size_t anchor, size_t ll, uin
     memcpy(m->lit + m->nlit, s + anchor, ll); m->nlit += ll;
     m->seq[m->nseq].ll = (uint32_t)ll; m->seq[m->nseq].ml = (uint32_t)(ml - 3); m->seq[m->nseq].off = off_base;
     m->nseq++;
+    ztr_emit(m, anchor, ll, off_base, ml);
 }
 
 /* ZSTD_compressBlock_fast_noDict_generic over s[start, end); returns the last-literals length */
@@ -836,6 +861,7 @@ static size_t fast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t st
         const uint32_t max_rep = cur - low;
         if (rep2 > max_rep) { saved2 = rep2; rep2 = 0; }
         if (rep1 > max_rep) { saved1 = rep1; rep1 = 0; }
+        if (saved1 | saved2) ztr_arm(m, ORC_ZARM_REP_ZEROED, ip0, (saved1 != 0) + 2 * (saved2 != 0));
     }
     for (;;) {                                     /* _start */
         step = step0; next_step = ip0 + 128;
@@ -853,17 +879,21 @@ static size_t fast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t st
                 ip0 -= mlen; match0 -= mlen;
                 off_base = 1; mlen += 4;
                 tab[h1] = (uint32_t)ip1 + 2;
+                ztr_arm(m, ORC_ZARM_F_REP_IP2, ip2, step);
+                ztr_arm(m, ORC_ZARM_CATCHUP, ip0, mlen - 4);
                 goto match;
             }
-            if (idx >= prefix_idx && rd32(s + idx - 2) == rd32(s + ip0)) { tab[h1] = (uint32_t)ip1 + 2; goto offset; }
+            if (idx >= prefix_idx && rd32(s + idx - 2) == rd32(s + ip0)) { tab[h1] = (uint32_t)ip1 + 2; ztr_arm(m, ORC_ZARM_F_HIT_IP0, ip0, step); goto offset; }
+            if (idx < prefix_idx) ztr_out_of_window(m, s, idx, ip0);
             idx = tab[h1]; h0 = h1; h1 = zhash(s + ip2, hlog, mls);
             ip0 = ip1; ip1 = ip2; ip2 = ip3;
             cur0 = (uint32_t)ip0 + 2;
             tab[h0] = cur0;
-            if (idx >= prefix_idx && rd32(s + idx - 2) == rd32(s + ip0)) { if (step <= 4) tab[h1] = (uint32_t)ip1 + 2; goto offset; }
+            if (idx >= prefix_idx && rd32(s + idx - 2) == rd32(s + ip0)) { if (step <= 4) tab[h1] = (uint32_t)ip1 + 2; ztr_arm(m, ORC_ZARM_F_HIT_IP1, ip0, step); goto offset; }
+            if (idx < prefix_idx) ztr_out_of_window(m, s, idx, ip0);
             idx = tab[h1]; h0 = h1; h1 = zhash(s + ip2, hlog, mls);
             ip0 = ip1; ip1 = ip2; ip2 = ip0 + step; ip3 = ip1 + step;
-            if (ip2 >= next_step) { step++; next_step += 128; }
+            if (ip2 >= next_step) { step++; next_step += 128; ztr_arm(m, ORC_ZARM_STEP_UP, ip0, step); }
             if ((int64_t)ip3 >= ilimit) goto cleanup;
         }
     offset:
@@ -872,11 +902,15 @@ static size_t fast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t st
         off_base = rep1 + 3;
         mlen = 4;
         while (ip0 > anchor && match0 > prefix && s[ip0 - 1] == s[match0 - 1]) { ip0--; match0--; mlen++; }
+        ztr_arm(m, ORC_ZARM_CATCHUP, ip0, mlen - 4);
     match:
         mlen += count_eq(s, ip0 + mlen, match0 + mlen, end);
+        if (!m->nseq && start > 0 && ip0 - start < (size_t)(rep[0] > rep[1] ? rep[0] : rep[1]) + 4) ztr_arm(m, ORC_ZARM_START_NEAR_REP, ip0, rep[0] > rep[1] ? rep[0] : rep[1]);
         store_seq(m, s, anchor, ip0 - anchor, off_base, mlen);
         ip0 += mlen; anchor = ip0;
+        if ((int64_t)ip0 > ilimit) ztr_arm(m, ORC_ZARM_END_BEHIND_ILIMIT, ip0, end - ip0);
         if ((int64_t)ip0 <= ilimit) {
+            uint32_t turn = 0;
             tab[zhash(s + cur0, hlog, mls)] = cur0 + 2;                  /* position cur0 - 2 + 2 */
             tab[zhash(s + ip0 - 2, hlog, mls)] = (uint32_t)ip0;          /* index of ip0 - 2 */
             if (rep2 > 0)
@@ -884,6 +918,7 @@ static size_t fast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t st
                     const size_t rlen = count_eq(s, ip0 + 4, ip0 + 4 - rep2, end) + 4;
                     const uint32_t t = rep2; rep2 = rep1; rep1 = t;
                     tab[zhash(s + ip0, hlog, mls)] = (uint32_t)ip0 + 2;
+                    ztr_arm(m, ORC_ZARM_REP2_AFTER, ip0, ++turn);
                     ip0 += rlen;
                     store_seq(m, s, anchor, 0, 1, rlen);
                     anchor = ip0;
@@ -892,6 +927,7 @@ static size_t fast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t st
     }
 cleanup:
     saved2 = (saved1 != 0 && rep1 != 0) ? saved1 : saved2;
+    if ((saved1 && !rep1) || (saved2 && !rep2)) ztr_arm(m, ORC_ZARM_REP_RESTORED, end, (saved1 && !rep1) + 2 * (saved2 && !rep2));
     rep[0] = rep1 ? rep1 : saved1;
     rep[1] = rep2 ? rep2 : saved2;
     return end - anchor;
@@ -918,6 +954,7 @@ static size_t dfast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t s
         const uint32_t max_rep = c - low;
         if (rep2 > max_rep) { saved2 = rep2; rep2 = 0; }
         if (rep1 > max_rep) { saved1 = rep1; rep1 = 0; }
+        if (saved1 | saved2) ztr_arm(m, ORC_ZARM_REP_ZEROED, ip, (saved1 != 0) + 2 * (saved2 != 0));
     }
     for (;;) {
         step = 1; next_step = ip + 256; ip1 = ip + step;
@@ -931,6 +968,8 @@ static size_t dfast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t s
             if ((rep1 > 0) & (rd32(s + ip + 1 - rep1) == rd32(s + ip + 1))) {
                 mlen = count_eq(s, ip + 1 + 4, ip + 1 + 4 - rep1, end) + 4;
                 ip++;
+                ztr_arm(m, ORC_ZARM_D_REP_IP1, ip, step);
+                if (!m->nseq && start > 0 && ip - start < (size_t)(rep[0] > rep[1] ? rep[0] : rep[1]) + 4) ztr_arm(m, ORC_ZARM_START_NEAR_REP, ip, rep[0] > rep[1] ? rep[0] : rep[1]);
                 store_seq(m, s, anchor, ip - anchor, 1, mlen);
                 goto stored;
             }
@@ -938,33 +977,43 @@ static size_t dfast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t s
             if (idxl0 > prefix_idx && rd64(s + idxl0 - 2) == rd64(s + ip)) {
                 match = idxl0 - 2;
                 mlen = count_eq(s, ip + 8, match + 8, end) + 8;
+                ztr_arm(m, ORC_ZARM_D_LONG, ip, step);
                 goto found;
             }
+            if (idxl0 <= prefix_idx) ztr_out_of_window(m, s, idxl0, ip);
             idxl1 = tl[hl1];
             if (idxs0 > prefix_idx && rd32(s + idxs0 - 2) == rd32(s + ip)) {
                 if (idxl1 > prefix_idx && rd64(s + idxl1 - 2) == rd64(s + ip1)) {      /* _search_next_long */
+                    ztr_arm(m, ORC_ZARM_D_SHORT_THEN_LONG, ip, step);
                     ip = ip1; match = idxl1 - 2;
                     mlen = count_eq(s, ip + 8, match + 8, end) + 8;
                 } else {
+                    ztr_arm(m, ORC_ZARM_D_SHORT, ip, step);
                     match = idxs0 - 2;
                     mlen = count_eq(s, ip + 4, match + 4, end) + 4;
                 }
                 goto found;
             }
-            if (ip1 >= next_step) { step++; next_step += 256; }
+            if (idxs0 <= prefix_idx) ztr_out_of_window(m, s, idxs0, ip);
+            if (ip1 >= next_step) { step++; next_step += 256; ztr_arm(m, ORC_ZARM_STEP_UP, ip, step); }
             ip = ip1; ip1 += step;
             hl0 = hl1; idxl0 = idxl1;
             if ((int64_t)ip1 > ilimit) goto cleanup;
         }
     found:
         offset = (uint32_t)(ip - match);
+        { const size_t ip_found = ip;
         while (ip > anchor && match > prefix && s[ip - 1] == s[match - 1]) { ip--; match--; mlen++; }
+        ztr_arm(m, ORC_ZARM_CATCHUP, ip, ip_found - ip); }
         rep2 = rep1; rep1 = offset;
         if (step < 4) tl[hl1] = (uint32_t)ip1 + 2;
+        if (!m->nseq && start > 0 && ip - start < (size_t)(rep[0] > rep[1] ? rep[0] : rep[1]) + 4) ztr_arm(m, ORC_ZARM_START_NEAR_REP, ip, rep[0] > rep[1] ? rep[0] : rep[1]);
         store_seq(m, s, anchor, ip - anchor, offset + 3, mlen);
     stored:
         ip += mlen; anchor = ip;
+        if ((int64_t)ip > ilimit) ztr_arm(m, ORC_ZARM_END_BEHIND_ILIMIT, ip, end - ip);
         if ((int64_t)ip <= ilimit) {
+            uint32_t turn = 0;
             const uint32_t ins = cur + 2;                               /* index; its position is ins - 2 = cur */
             tl[HL(cur)] = ins;
             tl[HL(ip - 2)] = (uint32_t)ip;
@@ -975,6 +1024,7 @@ static size_t dfast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t s
                 const uint32_t t = rep2; rep2 = rep1; rep1 = t;
                 ts[zhash(s + ip, hs_log, mls)] = (uint32_t)ip + 2;
                 tl[HL(ip)] = (uint32_t)ip + 2;
+                ztr_arm(m, ORC_ZARM_REP2_AFTER, ip, ++turn);
                 store_seq(m, s, anchor, 0, 1, rlen);
                 ip += rlen; anchor = ip;
             }
@@ -983,6 +1033,7 @@ static size_t dfast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t s
 cleanup:
 #undef HL
     saved2 = (saved1 != 0 && rep1 != 0) ? saved1 : saved2;
+    if ((saved1 && !rep1) || (saved2 && !rep2)) ztr_arm(m, ORC_ZARM_REP_RESTORED, end, (saved1 && !rep1) + 2 * (saved2 && !rep2));
     rep[0] = rep1 ? rep1 : saved1;
     rep[1] = rep2 ? rep2 : saved2;
     return end - anchor;
@@ -1018,6 +1069,7 @@ static void row_insert(zmatch* m, uint32_t hash, uint32_t idx)
     const uint32_t rowlog = lz_rowlog(m), mask = (1u << rowlog) - 1, rel = (hash >> 8) << rowlog;
     uint8_t* const tag_row = m->tags + 2 * (size_t)rel;
     const uint32_t pos = (tag_row[0] - 1u) & mask;
+    if (!tag_row[0] && m->table[rel + pos]) ztr_arm(m, ORC_ZARM_ROW_WRAPS, idx - 2, mask + 1);      /* the head goes from 0 to the row's last entry, which is in use: the inserts have gone round */
     tag_row[0] = (uint8_t)pos;
     tag_row[16 + pos] = (uint8_t)hash;
     m->table[rel + pos] = idx;
@@ -1047,6 +1099,7 @@ static size_t row_search(zmatch* m, const uint8_t* s, size_t ip, size_t end, uin
     const uint32_t rowlog = lz_rowlog(m), entries = 1u << rowlog, mask = entries - 1;
     uint32_t attempts = 1u << (m->p.slog < rowlog ? m->p.slog : rowlog);
     uint32_t cand[64], ncand = 0;
+    int why = ORC_END_CHAIN, winner = -1;
     size_t ml = 3;
     row_update(m, s, curr);
     {
@@ -1056,12 +1109,14 @@ static size_t row_search(zmatch* m, const uint8_t* s, size_t ip, size_t end, uin
         for (uint32_t i = 0; i < entries && attempts > 0; i++) {        /* newest first: the rotated SSE match mask */
             const uint32_t pos = (head + i) & mask;
             if (tag_row[16 + pos] != tag) continue;
-            if (m->table[rel + pos] < low) break;
+            if (m->table[rel + pos] < low) { why = ORC_END_LOWEST; ztr_out_of_window(m, s, m->table[rel + pos], ip); break; }
             cand[ncand++] = m->table[rel + pos];
             attempts--;
         }
+        if (!attempts) why = ORC_END_ATTEMPTS;
         {   /* the current position goes in as well (:1229-1234) */
             const uint32_t pos = (tag_row[0] - 1u) & mask;
+            if (!tag_row[0] && m->table[rel + pos]) ztr_arm(m, ORC_ZARM_ROW_WRAPS, ip, entries);
             tag_row[0] = (uint8_t)pos; tag_row[16 + pos] = (uint8_t)tag;
             m->table[rel + pos] = m->next_to_update++;
         }
@@ -1070,8 +1125,9 @@ static size_t row_search(zmatch* m, const uint8_t* s, size_t ip, size_t end, uin
         const size_t match = cand[k] - 2;
         size_t cur = 0;
         if (s[match + ml] == s[ip + ml]) cur = count_eq(s, ip, match, end);
-        if (cur > ml) { ml = cur; *ofb = curr - cand[k] + 3; if (ip + cur == end) break; }
+        if (cur > ml) { ml = cur; *ofb = curr - cand[k] + 3; winner = (int)k; if (ip + cur == end) break; }
     }
+    ztr_search(m, ORC_ZSEARCH_ROW, ip, ncand, why, winner, ml);
     return ml;
 }
 
@@ -1080,7 +1136,8 @@ static size_t hc_search(zmatch* m, const uint8_t* s, size_t ip, size_t end, uint
     const uint32_t curr = (uint32_t)ip + 2, low = lz_low_limit(m, curr), mls = lz_mls(m);
     const uint32_t chain_size = 1u << m->p.clog, cmask = chain_size - 1;
     const uint32_t min_chain = curr > chain_size ? curr - chain_size : 0;
-    uint32_t attempts = 1u << m->p.slog, idx = m->next_to_update, mi;
+    uint32_t attempts = 1u << m->p.slog, idx = m->next_to_update, mi, walked = 0;
+    int why = 0, winner = -1;
     size_t ml = 3;
     for (; idx < curr; idx++) {                                       /* ZSTD_insertAndFindFirstIndex_internal */
         const uint32_t h = zhash(s + idx - 2, m->p.hlog, mls);
@@ -1093,10 +1150,13 @@ static size_t hc_search(zmatch* m, const uint8_t* s, size_t ip, size_t end, uint
         const size_t match = mi - 2;
         size_t cur = 0;
         if (s[match + ml] == s[ip + ml]) cur = count_eq(s, ip, match, end);
-        if (cur > ml) { ml = cur; *ofb = curr - mi + 3; if (ip + cur == end) break; }
-        if (mi <= min_chain) break;
+        walked++;
+        if (cur > ml) { ml = cur; *ofb = curr - mi + 3; winner = (int)walked - 1; if (ip + cur == end) { why = ORC_END_INPUT; break; } }
+        if (mi <= min_chain) { why = ORC_END_CHAIN; break; }
         mi = m->small[mi & cmask];
     }
+    if (!why) { why = attempts ? ORC_END_LOWEST : ORC_END_ATTEMPTS; if (attempts) ztr_out_of_window(m, s, mi, ip); }
+    ztr_search(m, ORC_ZSEARCH_HC, ip, walked, why, winner, ml);
     return ml;
 }
 
@@ -1157,6 +1217,7 @@ static size_t bt_search(zmatch* m, const uint8_t* s, size_t ip, size_t end, uint
         next_cand = bt + 2 * (mi & bt_mask); unsorted = next_cand + 1;
         nb_candidates--;
     }
+    if (nb_candidates <= 1 && mi > unsort_limit && *unsorted == DUBT_UNSORTED) ztr_arm(m, ORC_ZARM_BT_BATCH_FULL, ip, nb_compares);
     if (mi > unsort_limit && *unsorted == DUBT_UNSORTED) *next_cand = *unsorted = 0;   /* nullify the last one if still unsorted */
     mi = previous;
     while (mi) {                                                      /* batch sort the stacked candidates */
@@ -1167,7 +1228,8 @@ static size_t bt_search(zmatch* m, const uint8_t* s, size_t ip, size_t end, uint
     }
     {   /* find the longest match, inserting curr into the tree */
         size_t common_smaller = 0, common_larger = 0, best = 0;
-        uint32_t dummy, *smaller = bt + 2 * (curr & bt_mask), *larger = smaller + 1, match_end_idx = curr + 8 + 1;
+        uint32_t dummy, *smaller = bt + 2 * (curr & bt_mask), *larger = smaller + 1, match_end_idx = curr + 8 + 1, walked = 0;
+        int why = 0, winner = -1;
         mi = m->table[h];
         m->table[h] = curr;
         for (; nb_compares && mi > window_low; --nb_compares) {
@@ -1175,21 +1237,24 @@ static size_t bt_search(zmatch* m, const uint8_t* s, size_t ip, size_t end, uint
             const size_t match = mi - 2;
             size_t ml = common_smaller < common_larger ? common_smaller : common_larger;
             ml += count_eq(s, ip + ml, match + ml, end);
+            walked++;
             if (ml > best) {
                 if (ml > match_end_idx - mi) match_end_idx = mi + (uint32_t)ml;
-                if (4 * (int)(ml - best) > (int)(hibit(curr - mi + 1) - hibit(*ofb))) { best = ml; *ofb = curr - mi + 3; }
-                if (ip + ml == end) break;                            /* equal: drop, to keep the tree consistent */
+                if (4 * (int)(ml - best) > (int)(hibit(curr - mi + 1) - hibit(*ofb))) { best = ml; *ofb = curr - mi + 3; winner = (int)walked - 1; }
+                if (ip + ml == end) { why = ORC_END_INPUT; break; }   /* equal: drop, to keep the tree consistent */
             }
             if (s[match + ml] < s[ip + ml]) {
                 *smaller = mi; common_smaller = ml;
-                if (mi <= bt_low) { smaller = &dummy; break; }
+                if (mi <= bt_low) { smaller = &dummy; why = ORC_END_CHAIN; break; }
                 smaller = next + 1; mi = next[1];
             } else {
                 *larger = mi; common_larger = ml;
-                if (mi <= bt_low) { larger = &dummy; break; }
+                if (mi <= bt_low) { larger = &dummy; why = ORC_END_CHAIN; break; }
                 larger = next; mi = next[0];
             }
         }
+        if (!why) why = nb_compares ? ORC_END_LOWEST : ORC_END_ATTEMPTS;
+        ztr_search(m, ORC_ZSEARCH_BT, ip, walked, why, winner, best);
         *smaller = *larger = 0;
         m->next_to_update = match_end_idx - 8;                        /* skip repetitive patterns */
         return best;
@@ -1212,61 +1277,66 @@ static size_t lazy_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t st
         const uint32_t max_rep = c - low;
         if (rep2 > max_rep) { saved2 = rep2; rep2 = 0; }
         if (rep1 > max_rep) { saved1 = rep1; rep1 = 0; }
+        if (saved1 | saved2) ztr_arm(m, ORC_ZARM_REP_ZEROED, ip, (saved1 != 0) + 2 * (saved2 != 0));
     }
-    if (use_row) row_fill_cache(m, s, m->next_to_update, ilimit);
+    if (use_row) { if (start > 0) ztr_arm(m, ORC_ZARM_ROW_CACHE_AT_BLOCK, start, (size_t)((int64_t)start + 2 - (int64_t)m->next_to_update + 100000)); row_fill_cache(m, s, m->next_to_update, ilimit); }
     while ((int64_t)ip < ilimit) {
         size_t ml = 0, at = ip + 1;
         uint32_t ofb = 1;
         if ((rep1 > 0) & (rd32(s + ip + 1 - rep1) == rd32(s + ip + 1))) {
             ml = count_eq(s, ip + 1 + 4, ip + 1 + 4 - rep1, end) + 4;
+            ztr_arm(m, ORC_ZARM_L_REP_IP1, ip + 1, ml);
             if (depth == 0) goto store;
         }
         {
             uint32_t found = 999999999;
             const size_t ml2 = SEARCH(ip, &found);
-            if (ml2 > ml) { ml = ml2; at = ip; ofb = found; }
+            if (ml2 > ml) { ml = ml2; at = ip; ofb = found; if (ml >= 4) ztr_arm(m, ORC_ZARM_L_SEARCH_WINS, ip, ml); }
         }
-        if (ml < 4) { ip += ((ip - anchor) >> 8) + 1; continue; }
+        if (ml < 4) { if ((ip - anchor) >> 8) ztr_arm(m, ORC_ZARM_L_STEP_GROWN, ip, ((ip - anchor) >> 8) + 1); ip += ((ip - anchor) >> 8) + 1; continue; }
         if (depth >= 1)
             while ((int64_t)ip < ilimit) {
                 ip++;
                 if ((rep1 > 0) & (rd32(s + ip) == rd32(s + ip - rep1))) {
                     const size_t mr = count_eq(s, ip + 4, ip + 4 - rep1, end) + 4;
                     const int g2 = (int)(mr * 3), g1 = (int)(ml * 3 - (size_t)hibit(ofb) + 1);
-                    if (mr >= 4 && g2 > g1) { ml = mr; ofb = 1; at = ip; }
+                    if (mr >= 4 && g2 > g1) { ml = mr; ofb = 1; at = ip; ztr_arm(m, ORC_ZARM_L_D1_REP, ip, ml); }
                 }
                 {
                     uint32_t cand = 999999999;
                     const size_t ml2 = SEARCH(ip, &cand);
                     const int g2 = (int)(ml2 * 4 - (size_t)hibit(cand)), g1 = (int)(ml * 4 - (size_t)hibit(ofb) + 4);
-                    if (ml2 >= 4 && g2 > g1) { ml = ml2; ofb = cand; at = ip; continue; }
+                    if (ml2 >= 4 && g2 > g1) { ml = ml2; ofb = cand; at = ip; ztr_arm(m, ORC_ZARM_L_D1_SEARCH, ip, ml); continue; }
                 }
                 if (depth == 2 && (int64_t)ip < ilimit) {
                     ip++;
                     if ((rep1 > 0) & (rd32(s + ip) == rd32(s + ip - rep1))) {
                         const size_t mr = count_eq(s, ip + 4, ip + 4 - rep1, end) + 4;
                         const int g2 = (int)(mr * 4), g1 = (int)(ml * 4 - (size_t)hibit(ofb) + 1);
-                        if (mr >= 4 && g2 > g1) { ml = mr; ofb = 1; at = ip; }
+                        if (mr >= 4 && g2 > g1) { ml = mr; ofb = 1; at = ip; ztr_arm(m, ORC_ZARM_L_D2_REP, ip, ml); }
                     }
                     {
                         uint32_t cand = 999999999;
                         const size_t ml2 = SEARCH(ip, &cand);
                         const int g2 = (int)(ml2 * 4 - (size_t)hibit(cand)), g1 = (int)(ml * 4 - (size_t)hibit(ofb) + 7);
-                        if (ml2 >= 4 && g2 > g1) { ml = ml2; ofb = cand; at = ip; continue; }
+                        if (ml2 >= 4 && g2 > g1) { ml = ml2; ofb = cand; at = ip; ztr_arm(m, ORC_ZARM_L_D2_SEARCH, ip, ml); continue; }
                     }
                 }
                 break;
             }
         if (ofb > 3) {
             const uint32_t off = ofb - 3;
+            const size_t at_found = at;
             while (at > anchor && at - off > prefix && s[at - 1] == s[at - off - 1]) { at--; ml++; }
+            ztr_arm(m, ORC_ZARM_L_CATCHUP, at, at_found - at);
             rep2 = rep1; rep1 = off;
         }
     store:
         store_seq(m, s, anchor, at - anchor, ofb, ml);
         anchor = ip = at + ml;
-        while (((int64_t)ip <= ilimit) & (rep2 > 0) && rd32(s + ip) == rd32(s + ip - rep2)) {
+        for (uint32_t turn = 1; ((int64_t)ip <= ilimit) & (rep2 > 0) && rd32(s + ip) == rd32(s + ip - rep2); turn++) {
             const uint32_t t = rep2;
+            ztr_arm(m, ORC_ZARM_L_REP_LOOP, ip, turn);
             ml = count_eq(s, ip + 4, ip + 4 - rep2, end) + 4;
             rep2 = rep1; rep1 = t;
             store_seq(m, s, anchor, 0, 1, ml);
@@ -1275,6 +1345,7 @@ static size_t lazy_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t st
     }
 #undef SEARCH
     saved2 = (saved1 != 0 && rep1 != 0) ? saved1 : saved2;
+    if ((saved1 && !rep1) || (saved2 && !rep2)) ztr_arm(m, ORC_ZARM_REP_RESTORED, end, (saved1 && !rep1) + 2 * (saved2 && !rep2));
     rep[0] = rep1 ? rep1 : saved1;
     rep[1] = rep2 ? rep2 : saved2;
     return end - anchor;
@@ -1411,6 +1482,7 @@ static uint32_t opt_matches(zmatch* m, optstate* o, const uint8_t* s, size_t ip,
     optmatch* const out = o->match;
     uint32_t n = 0;
     size_t best = to_beat - 1;
+    int from3 = 0;
     if (curr < m->next_to_update) return 0;                                      /* skipped area */
     for (uint32_t idx = m->next_to_update; idx < curr; ) idx += opt_tree_insert(m, s, idx, end, curr);
     m->next_to_update = curr;
@@ -1431,7 +1503,7 @@ static uint32_t opt_matches(zmatch* m, optstate* o, const uint8_t* s, size_t ip,
             if (len > best) {
                 best = len;
                 out[n].off = code - ll0 + 1; out[n].len = len; n++;
-                if (len > sufficient || ip + len == end) return n;
+                if (len > sufficient || ip + len == end) { ztr_search(m, ORC_ZSEARCH_OPT, ip, n, len > sufficient, 0, len); return n; }
             }
         }
         /* 3-byte matches through their own hash table (:385-404, :659-688) */
@@ -1444,8 +1516,8 @@ static uint32_t opt_matches(zmatch* m, optstate* o, const uint8_t* s, size_t ip,
                 const size_t len = count_eq(s, ip, i3 - 2, end);
                 if (len >= mls) {
                     best = len;
-                    out[0].off = curr - i3 + 3; out[0].len = (uint32_t)len; n = 1;
-                    if (len > sufficient || ip + len == end) { m->next_to_update = curr + 1; return 1; }
+                    out[0].off = curr - i3 + 3; out[0].len = (uint32_t)len; n = 1; from3 = 1;
+                    if (len > sufficient || ip + len == end) { m->next_to_update = curr + 1; ztr_search(m, ORC_ZSEARCH_OPT, ip, 1, len > sufficient, 1, len); return 1; }
                 }
             }
         }
@@ -1477,6 +1549,7 @@ static uint32_t opt_matches(zmatch* m, optstate* o, const uint8_t* s, size_t ip,
         if (larger != ~0u) bt[larger] = 0;
         m->next_to_update = end_idx - 8;                                         /* skip repetitive patterns */
     }
+    ztr_search(m, ORC_ZSEARCH_OPT, ip, n, n && out[n - 1].len > sufficient, from3, n ? out[n - 1].len : 0);
     return n;
 }
 
@@ -1490,9 +1563,10 @@ static size_t opt_block(zmatch* m, optstate* o, uint32_t rep[3], const uint8_t* 
     size_t ip = start, anchor = start;
     o->next3 = m->next_to_update;
     opt_first_block_stats(o, s + start, end - start);
+    ztr_arm(m, o->predef ? ORC_ZARM_O_PREDEF : ORC_ZARM_O_STATS, start, end - start);
     ip += (uint32_t)ip + 2 == m->dict_limit;
     while ((int64_t)ip < ilimit) {
-        uint32_t cur, last_pos = 0;
+        uint32_t cur, last_pos = 0, longest0 = 0;
         optnode last;
         {   /* the matches at ip open a series */
             const uint32_t litlen = (uint32_t)(ip - anchor), ll0 = !litlen;
@@ -1501,7 +1575,9 @@ static size_t opt_block(zmatch* m, optstate* o, uint32_t rep[3], const uint8_t* 
             if (!nb) { ip++; continue; }
             memcpy(node[0].rep, rep, sizeof node[0].rep);
             node[0].mlen = 0; node[0].litlen = litlen; node[0].price = (int)opt_ll_price(o, litlen);
+            longest0 = match[nb - 1].len;
             if (match[nb - 1].len > sufficient) {                                /* long match: taken at once */
+                ztr_arm(m, ORC_ZARM_O_IMMEDIATE, ip, match[nb - 1].len);
                 last.litlen = litlen; last.mlen = match[nb - 1].len; last.off = match[nb - 1].off; last.price = 0;
                 cur = 0;
                 goto shortest_path;
@@ -1522,6 +1598,7 @@ static size_t opt_block(zmatch* m, optstate* o, uint32_t rep[3], const uint8_t* 
                 const int price = node[cur - 1].price + (int)opt_literal_price(o, s[inr - 1]) + (int)opt_ll_price(o, litlen) - (int)opt_ll_price(o, litlen - 1);
                 if (price <= node[cur].price) { node[cur].mlen = 0; node[cur].off = 0; node[cur].litlen = litlen; node[cur].price = price; }
             }
+            if (node[cur].mlen != 0 && node[cur].off <= 3 && node[cur].litlen == 0) ztr_arm(m, ORC_ZARM_O_LL0_SHIFT, inr - node[cur].mlen, node[cur].off);
             if (node[cur].mlen != 0) opt_new_rep(node[cur].rep, node[cur - node[cur].mlen].rep, node[cur].off, node[cur].litlen == 0);
             else memcpy(node[cur].rep, node[cur - 1].rep, sizeof node[cur].rep);
             if ((int64_t)inr > ilimit) continue;                                 /* the last match starts at least 8 bytes before the end */
@@ -1533,6 +1610,8 @@ static size_t opt_block(zmatch* m, optstate* o, uint32_t rep[3], const uint8_t* 
                 const uint32_t nb = opt_matches(m, o, s, inr, end, node[cur].rep, ll0, minmatch);
                 if (!nb) continue;
                 if (match[nb - 1].len > sufficient || cur + match[nb - 1].len >= OPT_NUM) {
+                    if (match[nb - 1].len > sufficient) ztr_arm(m, ORC_ZARM_O_IMMEDIATE, inr, match[nb - 1].len);
+                    else ztr_arm(m, ORC_ZARM_O_ARRAY_FULL, inr, cur + match[nb - 1].len);
                     last.mlen = match[nb - 1].len; last.off = match[nb - 1].off; last.litlen = litlen; last.price = 0;
                     cur -= node[cur].mlen == 0 ? node[cur].litlen : 0;           /* may wrap: then it is the first sequence */
                     if (cur > OPT_NUM) cur = 0;
@@ -1568,6 +1647,7 @@ shortest_path:
             }
             for (uint32_t k = store_start; k <= store_end; k++) {
                 const uint32_t llen = node[k].litlen, mlen = node[k].mlen;
+                if (longest0) { if (mlen != longest0 || anchor + llen != ip) ztr_arm(m, ORC_ZARM_O_NOT_GREEDY, ip, longest0); longest0 = 0; }
                 if (mlen == 0) { ip = anchor + llen; continue; }                 /* trailing literals: the next series starts behind them */
                 opt_count_sequence(o, llen, s + anchor, node[k].off, mlen);
                 store_seq(m, s, anchor, llen, node[k].off, mlen);
@@ -1611,6 +1691,9 @@ static int is_rle(const uint8_t* s, size_t n)
 { for (size_t i = 1; i < n; i++) if (s[i] != s[0]) return 0; return 1; }
 
 int64_t orc_zstd_compress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, int level)
+{ return orc_zstd_compress_ex(src, n, dst, cap, level, NULL); }
+
+int64_t orc_zstd_compress_ex(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, int level, orc_trace* trace)
 {
     zparams p;
     zmatch m;
@@ -1653,6 +1736,7 @@ int64_t orc_zstd_compress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap
         opt.hlog3 = p.mml == 3 ? (p.wlog < 17 ? p.wlog : 17) : 1;       /* ZSTD_reset_matchState: hashLog3 = MIN(ZSTD_HASHLOG3_MAX, windowLog) */
         opt.hash3 = (uint32_t*)calloc((size_t)1 << opt.hlog3, 4);
     }
+    m.tr = trace; m.blk = 0;
     m.next_to_update = m.low_limit = m.dict_limit = 2;                /* ZSTD_WINDOW_START_INDEX */
     memset(m.hash_cache, 0, sizeof m.hash_cache);
     m.seq = (zseq*)malloc((BLOCK_MAX / 3 + 1) * sizeof(zseq));
@@ -1668,6 +1752,9 @@ int64_t orc_zstd_compress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap
         zentropy* next = &ent[cur ^ 1];
         size_t bcap;
         int64_t c = 0;
+        int32_t row[ORC_ZTR_BLOCK_WORDS] = {m.blk, (int32_t)pos, (int32_t)len, (int32_t)p.strat, 0, 0, -1, 0, 0, -1, 0, -1, 0, -1, 0, ORC_ZOUT_RAW_SHORT,
+                                            (int32_t)prev->rep[0], (int32_t)prev->rep[1], (int32_t)prev->rep[2], (int32_t)prev->rep[0], (int32_t)prev->rep[1], (int32_t)prev->rep[2],
+                                            (int32_t)p.wlog, (int32_t)p.clog, (int32_t)p.hlog, (int32_t)p.slog, (int32_t)p.mml, (int32_t)p.tlen};
         if (cap - o < 3 + 2 + 1) { result = ERR_TOOSMALL; break; }
         bcap = cap - o - 3;
         {   /* ZSTD_window_enforceMaxDist(window, block START, ...) and the nextToUpdate floor (zstd_compress.c:4017-4021) */
@@ -1686,24 +1773,33 @@ int64_t orc_zstd_compress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap
             memcpy(next->rep, prev->rep, sizeof next->rep);
             {   /* limited catch-up after a very long match (ZSTD_buildSeqStore, zstd_compress.c:2890-2896) */
                 const uint32_t curr = (uint32_t)pos + 2;
-                if (curr > m.next_to_update + 384) { const uint32_t gap = curr - m.next_to_update - 384; m.next_to_update = curr - (gap < 192 ? gap : 192); }
+                if (curr > m.next_to_update + 384) { const uint32_t gap = curr - m.next_to_update - 384; m.next_to_update = curr - (gap < 192 ? gap : 192); if (p.strat >= 3) ztr_arm(&m, ORC_ZARM_L_NTU_LIMIT, pos, gap < 192 ? gap : 192); }
             }
             if (p.strat == 7) tail = opt_block(&m, &opt, next->rep, src, pos, pos + len);
             else if (p.strat >= 3) tail = lazy_block(&m, next->rep, src, pos, pos + len, p.strat >= 5 ? 2 : p.strat == 3 ? 0 : 1, p.strat == 6 ? 2 : p.wlog > 14);
             else tail = p.strat == 2 ? dfast_block(&m, next->rep, src, pos, pos + len) : fast_block(&m, next->rep, src, pos, pos + len);
             memcpy(m.lit + m.nlit, src + pos + len - tail, tail); m.nlit += tail;
+            ztr_emit(&m, pos + len - tail, tail, 0, 0);
+            row[ORC_ZBLK_NSEQ] = (int32_t)m.nseq; row[ORC_ZBLK_NLIT] = (int32_t)m.nlit;
+            for (int k = 0; k < 3; k++) row[ORC_ZBLK_REP_OUT + k] = (int32_t)next->rep[k];
             lsz = compress_literals(prev, next, out, bcap, m.lit, m.nlit, m.nseq == 0 || m.nlit / m.nseq >= 20, p.strat);
             c = lsz;
             if (lsz >= 0) {
                 ssz = encode_sequences(out + lsz, bcap - (size_t)lsz, m.seq, m.nseq, llc, ofc, mlc, p.strat, prev, next);
                 c = ssz <= 0 ? ssz : lsz + ssz;
             }
-            if (c == ERR_TOOSMALL && len <= bcap) c = 0;
-            if (c < 0) { result = c; break; }
+            if (lsz >= 0) { row[ORC_ZBLK_LIT_TYPE] = next->note[0]; row[ORC_ZBLK_LIT_STREAMS] = next->note[1]; row[ORC_ZBLK_HUF_DROPPED] = next->note[2]; }
+            if (lsz >= 0) for (int k = 0; k < 6; k++) row[ORC_ZBLK_LL_TYPE + k] = next->note[3 + k];
+            row[ORC_ZBLK_OUTCOME] = ORC_ZOUT_COMPRESSED;
+            if (c == ERR_TOOSMALL && len <= bcap) { c = 0; row[ORC_ZBLK_OUTCOME] = ORC_ZOUT_RAW_TOO_SMALL; }
+            if (c < 0) { result = c; row[ORC_ZBLK_OUTCOME] = ORC_ZOUT_REFUSED; orc_tr_put(trace, ORC_TR_BLOCK, row, ORC_ZTR_BLOCK_WORDS); break; }
             if (c > 0 && (size_t)c >= len - ((len >> 6) + 2)) c = 0;
-            if (!first && c < 25 && is_rle(src + pos, len)) { c = 1; out[0] = src[pos]; }
+            if (c == 0 && row[ORC_ZBLK_OUTCOME] == ORC_ZOUT_COMPRESSED) row[ORC_ZBLK_OUTCOME] = ORC_ZOUT_RAW_NOT_SMALLER;
+            if (!first && c < 25 && is_rle(src + pos, len)) { c = 1; out[0] = src[pos]; row[ORC_ZBLK_OUTCOME] = ORC_ZOUT_RLE; }
             if (c > 1) cur ^= 1;
-        }
+        } else ztr_emit(&m, pos, len, 0, 0);
+        if (c == 0 && len + 3 > cap - o) row[ORC_ZBLK_OUTCOME] = ORC_ZOUT_REFUSED;
+        orc_tr_put(trace, ORC_TR_BLOCK, row, ORC_ZTR_BLOCK_WORDS);
         if (c == 0) {
             const uint32_t h = (uint32_t)last + ((uint32_t)len << 3);
             if (len + 3 > cap - o) { result = ERR_TOOSMALL; break; }
@@ -1715,7 +1811,7 @@ int64_t orc_zstd_compress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap
             dst[o] = (uint8_t)h; dst[o + 1] = (uint8_t)(h >> 8); dst[o + 2] = (uint8_t)(h >> 16);
             o += 3 + (size_t)c;
         }
-        pos += len; first = 0;
+        pos += len; first = 0; m.blk++;
     }
     free(m.table); free(m.small); free(m.tags); free(m.seq); free(m.lit); free(llc); free(opt.node); free(opt.match); free(opt.hash3);
     return result < 0 ? result : (int64_t)o;

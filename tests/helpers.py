@@ -252,6 +252,32 @@ def orc_zstd_compress(src, level=1, cap=None):
     return r, dst[:max(r, 0)].copy()
 
 
+class OrcTrace(C.Structure):              # orc_trace (oracle.h)
+    _fields_ = [("ev", C.POINTER(C.c_int32) * 4), ("cap", C.c_int * 4), ("n", C.c_int * 4)]
+
+
+ZSTD_TRACE_WORDS = (6, 28, 3, 5)          # oracle.h ORC_ZTR_*: SEARCH, BLOCK, ARM, EMIT
+
+
+def orc_zstd_compress_ex(src, level=1, cap=None):
+    """orc_zstd_compress_ex -> (result, frame bytes, [search, block, arm, emit] tables of int32 rows): two runs, the first
+    with no room to size the second."""
+    src = np.ascontiguousarray(src, dtype=np.uint8)
+    L = oracle()
+    L.orc_zstd_compress_ex.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]; L.orc_zstd_compress_ex.restype = C.c_int64
+    cap = zstd_bound(len(src)) if cap is None else cap
+    dst = np.empty(max(cap, 1) + 64, dtype=np.uint8)
+    t = OrcTrace()
+    L.orc_zstd_compress_ex(src.ctypes.data, len(src), dst.ctypes.data, cap, level, C.byref(t))
+    bufs = [np.zeros(max(t.n[k], 1), np.int32) for k in range(4)]
+    t2 = OrcTrace()
+    for k in range(4):
+        t2.ev[k] = bufs[k].ctypes.data_as(C.POINTER(C.c_int32)); t2.cap[k] = len(bufs[k])
+    r = L.orc_zstd_compress_ex(src.ctypes.data, len(src), dst.ctypes.data, cap, level, C.byref(t2))
+    assert [t2.n[k] for k in range(4)] == [t.n[k] for k in range(4)]
+    return r, dst[:max(r, 0)].copy(), [bufs[k][:t2.n[k]].reshape(-1, ZSTD_TRACE_WORDS[k]) for k in range(4)]
+
+
 def golden_zstd_inputs():
     """The inputs of tests/golden/zstd_frames.json (frames written by the reference's ZSTD_compress at levels 1..12);
     tests/golden/make_golden.py generates the fixture from exactly these."""
