@@ -34,8 +34,8 @@ int orc_lz4_compress_bound(int n);
  * Returns bytes written, or 0 when the output does not fit `cap` (limitedOutput). */
 int orc_lz4_compress_fast(const uint8_t* src, uint8_t* dst, int n, int cap);
 
-/* LZ4_compress_HC, hash-chain levels 1..8 (4mc uses 4 and 8) - native/lz4/lz4hc.c:958-973 -> :553-788.
- * Returns bytes written, 0 when it does not fit `cap`, -2 for levels this port does not cover. */
+/* LZ4_compress_HC at any level (4mc uses 4 and 8; levels below 1 run as 9, levels above 12 as 12, native/lz4/lz4hc.c:840-841) -
+ * :958-973 -> :553-788 (levels 1..9) / :1330-1626 (levels 10..12).  Returns bytes written, 0 when it does not fit `cap`. */
 int orc_lz4hc_compress(const uint8_t* src, uint8_t* dst, int n, int cap, int level);
 
 /* What a run of the HC or the Medium port did, as four tables of int32 rows.  A row is written whole or not at all; n[]
@@ -89,6 +89,45 @@ enum {  /* the statements of LZ4HC_compress_hashChain's arbitration (lz4hc.c:592
 enum { ORC_SHARE_NTU_PREV = 1, ORC_SHARE_NTU_IP = 2, ORC_SHARE_PREV_IP = 4,       /* two slots of one probe in one bucket ... */
        ORC_DIFF_NTU_PREV = 8, ORC_DIFF_NTU_IP = 16, ORC_DIFF_PREV_IP = 32 };      /* ... holding different words */
 int orc_lz4hc_compress_ex(const uint8_t* src, uint8_t* dst, int n, int cap, int level, orc_trace* trace);
+/* The trace of HC levels 9..12 (any level below 1 or above 8 after the mapping) has rows of its own; the rules above hold.
+ *   ORC_TR_SEARCH  one row per search, ORC_HX_SEARCH_WORDS: sequences emitted before it, ip, low, longest on entry, candidates
+ *                  walked, ORC_END_* (ORC_END_BREAK: the walk left through a `break`), the winner's number in the walk (-1: none),
+ *                  longest on return, the candidate the walk would have visited next (-1), nextToUpdate (a position) before the
+ *                  insert, 1 when pattern analysis set the final length, matchChainPos on return
+ *   ORC_TR_CAND    one row per candidate walked, ORC_HX_CAND_WORDS: position, the 2-byte probe at `longest` passed (0/1), four bytes
+ *                  equal (0/1), and for those the equal bytes after the four and before (within the lookback and the candidate's
+ *                  own position), what ended the forward count (ORC_HX_STOP_MISMATCH / _LIMIT = ihigh) and the backward count
+ *                  (_MISMATCH / _LIMIT = the lookback / _CAND = the candidate's position), how the walk left it (ORC_HX_LEFT_*)
+ *   ORC_TR_ARM     event rows of ORC_HX_EV_WORDS, unused words 0.  Word 0 below 40: ORC_ARM_* / ORC_REFUSE_*, ip, ORC_HX_SITE_*.
+ *       ORC_HX_EV_SWAP   a chain-swap decision: ip, candidate, end, positions visited, largest step, the resulting distance,
+ *                        matchChainPos after it, ORC_HX_SWAP_*, the last offset read (candidate + offset + 65536 is the ring index)
+ *       ORC_HX_EV_PA     a candidate whose chain delta is 1: ip, the position before it, repeat state (1 not a pattern, 2 confirmed),
+ *                        srcLen, forward run, backward run to position 0, backward run after the clamp at `lowest`, ORC_HX_PA_*,
+ *                        1 when this event set the repeat state (ORC_HX_PA_SWAPPED: matchChainPos), bit 0: clamped by `lowest`,
+ *                        bit 1: the run reached position 0
+ *       ORC_HX_EV_OPT_*  the optimal parser: ip, then
+ *           _NO_MATCH -;  _FIRST_NOW length, literals before;  _FIRST length, literals before, 1 when length == sufficient_len
+ *           _AT_MFLIMIT cur;  _SKIP cur, p1 <= pc, the second condition of level 12 (-1: levels 10, 11);  _SEARCH_ANYWAY cur
+ *           _NO_LONGER cur;  _INNER_NOW_ENOUGH / _INNER_NOW_FULL cur, length
+ *           _UPDATE cur, ORC_HX_BASE_*, match length, last_match_pos rose, records written through `pos > last + 3`, through
+ *                   `price <=`, refused, literal records improved
+ *           _SERIES (ip behind it) hops of the reverse traversal, literal records between matches, first record a literal,
+ *                   last_match_pos, matches, least and most literals priced
+ *   ORC_TR_EMIT    as for levels 1..8 */
+enum { ORC_HX_SEARCH_WORDS = 12, ORC_HX_CAND_WORDS = 8, ORC_HX_EV_WORDS = 12 };
+enum { ORC_END_BREAK = 5 };
+enum { ORC_HX_STOP_MISMATCH = 0, ORC_HX_STOP_LIMIT = 1, ORC_HX_STOP_CAND = 2 };
+enum { ORC_HX_LEFT_CHAIN = 0, ORC_HX_LEFT_SWAP, ORC_HX_LEFT_PATTERN, ORC_HX_LEFT_BREAK,
+       ORC_HX_LEFT_CHAIN_SWAPPED /* a chain step at a matchChainPos != 0 that an earlier candidate of this search set */ };
+enum { ORC_HX_SITE_CHAIN = 0 /* level 9's loop */, ORC_HX_SITE_FIRST /* a first match encoded at once */, ORC_HX_SITE_SERIES /* the optimal parser's encode loop, and the last literals */ };
+enum { ORC_HX_SWAP_OVERLAP = 0 /* candidate + longest > ip: no scan */, ORC_HX_SWAP_NONE /* distance <= 1 */, ORC_HX_SWAP_JUMP, ORC_HX_SWAP_BREAK /* distance > index */ };
+enum { ORC_HX_PA_NOT_PATTERN = 0, ORC_HX_PA_BELOW_LOWEST, ORC_HX_PA_DIFFER /* four bytes differ */, ORC_HX_PA_TO_END /* lz4hc.c:379 */,
+       ORC_HX_PA_TO_START_LOOKBACK /* :388, lookback != 0 */, ORC_HX_PA_TO_START_TAKEN, ORC_HX_PA_TO_START_NOT_LONGER,
+       ORC_HX_PA_BREAK_DISTANCE /* :398 */, ORC_HX_PA_BREAK_DELTA /* :405 */, ORC_HX_PA_SWAPPED /* matchChainPos != 0: no analysis */ };
+enum { ORC_HX_BASE_LIT_INSIDE = 0 /* cur > litlen */, ORC_HX_BASE_LIT_FROM_START /* cur <= litlen */, ORC_HX_BASE_MATCH };
+enum { ORC_HX_EV_SWAP = 40, ORC_HX_EV_PA, ORC_HX_EV_OPT_NO_MATCH = 50, ORC_HX_EV_OPT_FIRST_NOW, ORC_HX_EV_OPT_FIRST, ORC_HX_EV_OPT_AT_MFLIMIT,
+       ORC_HX_EV_OPT_SKIP, ORC_HX_EV_OPT_SEARCH_ANYWAY, ORC_HX_EV_OPT_NO_LONGER, ORC_HX_EV_OPT_INNER_NOW_ENOUGH, ORC_HX_EV_OPT_INNER_NOW_FULL,
+       ORC_HX_EV_OPT_UPDATE, ORC_HX_EV_OPT_SERIES };
 /* LZ4_compressMC (cap < 0) / LZ4_compressMC_limitedOutput — native/lz4/lz4mc.c:582-606. */
 int orc_lz4mc_compress(const uint8_t* src, uint8_t* dst, int n, int cap);
 int orc_lz4mc_compress_ex(const uint8_t* src, uint8_t* dst, int n, int cap, orc_trace* trace);

@@ -10,7 +10,16 @@
  * The byte counts and emission are plain loops.  The CPU test compares this with the reference's LZ4_compress_HC.
  * Test / design aid only; not product.
  *   gcc -O2 -shared -fPIC -I4mc_amd/csrc -o /tmp/liblz4hc_opt_model.so tools/model/lz4hc_opt_model.c
+ *
+ * Mutants (tests/test_hc_opt_shapes_cpu.py): -DHO_MUTANT=n makes one primitive subtly wrong, so that the test can show that
+ * the catalogue tests/hc_opt_shapes.py tells the difference.  1: the insert does not clamp a delta at 65535; 2: the first lane
+ * of a hash becomes the head, not the last; 3: the swap scan never reloads its 64 deltas; 4: the swap scan drops matchChainPos;
+ * 5: ho_opt_match returns the old last_match_pos when matchML > 64; 6: ho_count_back ignores maxn (it stops at the candidate's
+ * own position alone).  0 or undefined: the model.
  */
+#ifndef HO_MUTANT
+#define HO_MUTANT 0
+#endif
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -35,13 +44,14 @@ HO_FN void ho_insert(HO* c, uint32_t upto)
             h[lane] = ho_hash(ho_ld32(c, pos));
             for (l = lane - 1; l >= 0 && h[l] != h[lane]; l--) ;
             if (l >= 0) delta[lane] = (uint32_t)(lane - l);
-            else { delta[lane] = pos + HO_IDX0 - c->heads[h[lane]]; if (delta[lane] > HO_MAXD) delta[lane] = HO_MAXD; }
+            else { delta[lane] = pos + HO_IDX0 - c->heads[h[lane]]; if (delta[lane] > HO_MAXD && HO_MUTANT != 1) delta[lane] = HO_MAXD; }
         }
         for (lane = 0; lane < 64; lane++) {
             int later = 0;
             if (!on[lane]) continue;
             c->chain[(c->ntu + (uint32_t)lane) & 0xFFFFu] = (uint16_t)delta[lane];
-            for (l = lane + 1; l < 64 && !later; l++) later = on[l] && h[l] == h[lane];
+            if (HO_MUTANT == 2) { for (l = lane - 1; l >= 0 && !later; l--) later = h[l] == h[lane]; }
+            else for (l = lane + 1; l < 64 && !later; l++) later = on[l] && h[l] == h[lane];
             if (!later) c->heads[h[lane]] = c->ntu + (uint32_t)lane + HO_IDX0;
         }
         c->ntu = ho_min(upto, c->ntu + 64u);
@@ -51,7 +61,7 @@ HO_FN void ho_insert(HO* c, uint32_t upto)
 HO_FN uint32_t ho_count(const HO* c, uint32_t a, uint32_t b, uint32_t lim)
 { uint32_t n = 0; while (a + n < lim && c->src[a + n] == c->src[b + n]) n++; return n; }
 HO_FN uint32_t ho_count_back(const HO* c, uint32_t a, uint32_t b, uint32_t maxn)
-{ uint32_t n = 0; while (n < maxn && c->src[a - n - 1] == c->src[b - n - 1]) n++; return n; }
+{ uint32_t n = 0; if (HO_MUTANT == 6) maxn = b; while (n < maxn && c->src[a - n - 1] == c->src[b - n - 1]) n++; return n; }
 HO_FN uint32_t ho_run(const HO* c, uint32_t a, uint32_t byte, uint32_t lim)
 { uint32_t n = 0; while (a + n < lim && c->src[a + n] == byte) n++; return n; }
 HO_FN uint32_t ho_run_back(const HO* c, uint32_t a, uint32_t byte)
@@ -63,13 +73,13 @@ HO_FN uint32_t ho_swap_scan(const HO* c, uint32_t matchIndex, int end, uint32_t*
     int pos = 0, step = 1, accel = 1 << 4, base = -64, lane;
     for (; pos < end; pos += step) {
         uint32_t cd;
-        if (pos - base >= 64) {
+        if (HO_MUTANT == 3 ? base < 0 : pos - base >= 64) {
             base = pos;
             for (lane = 0; lane < 64; lane++) chunk[lane] = c->chain[(matchIndex + (uint32_t)base + (uint32_t)lane) & 0xFFFFu];
         }
-        cd = chunk[pos - base];
+        cd = chunk[(pos - base) & 63];
         step = accel++ >> 4;
-        if (cd > dist) { dist = cd; *mcp = (uint32_t)pos; accel = 1 << 4; }
+        if (cd > dist) { dist = cd; if (HO_MUTANT != 4) *mcp = (uint32_t)pos; accel = 1 << 4; }
     }
     return dist;
 }
@@ -112,7 +122,7 @@ HO_FN int ho_opt_match(HO* c, int cur, int matchML, int off, int last)
         }
     }
     for (k = 1; k <= matchML; k++) if (wr[k]) c->opt[cur + k] = out[k];     /* then every lane writes */
-    return newlast;
+    return (HO_MUTANT == 5 && matchML > 64) ? last : newlast;
 }
 
 HO_FN void put_len(HO* c, uint32_t rest) { while (rest >= 255) { c->dst[c->op++] = 255; rest -= 255; } c->dst[c->op++] = (uint8_t)rest; }
