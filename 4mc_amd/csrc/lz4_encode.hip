@@ -27,6 +27,10 @@
 //     earlier one - an LDS atomic-min scoreboard; the cut lane becomes lane 0 of the next batch;
 //   * whatever the registers do not hold (long matches, long catch-up, output nearly full) goes
 //     through one general sequence routine with wave-wide compares and copies.
+// Control: the dense windows are a loop of their own inside the block's main loop - its back edge is the commit, and a
+// window that ends the block, fills the output, cannot be followed by another or may have filled the record area leaves
+// through one exit; the main loop holds the sparse batch and calls the drain of a full record area, which is out of line
+// and, for a block that cannot fill its area (every block up to FOURMC_BLOCKSIZE), out of reach.
 // The parse never writes the payload: lz4_emit.hip turns the records into bytes after it, outside the chain.
 // Per block HBM traffic: n bytes read (+ candidate re-reads that hit L1/L2), 16 bytes per sequence of records written.
 #include <hip/hip_runtime.h>
@@ -95,10 +99,23 @@ __device__ __forceinline__ uint32_t scan_add(uint32_t v)
     return v;
 }
 
+// equal bytes from the low end of a difference of 8 bytes (8: all), from the high end of one of 4 (4: all), without a branch
+__device__ __forceinline__ uint32_t eq_lsb(uint64_t x) { return uint32_t(__builtin_ctzg(x, 64)) >> 3; }
+__device__ __forceinline__ uint32_t eq_msb(uint32_t x) { return uint32_t(__builtin_clzg(x, 32)) >> 3; }
+
 template <bool U32TAB> __device__ __forceinline__ uint32_t hash_of(uint64_t v)
 {
     if (U32TAB) return uint32_t(((v << 24) * 889523592379ULL) >> (64 - kHashLog));
     return (uint32_t(v) * 2654435761u) >> (32 - (kHashLog + 1));
+}
+
+// The record area is full (only a block above FOURMC_BLOCKSIZE gets here, or one with FOURMC_LZ4_RECORDS set): its bytes go out
+// now.  Out of line: the parse's loops do not carry the emitter's code or its registers.
+__device__ __noinline__ void drain_records(const uint4* rec, uint32_t rc, uint32_t anchor, const uint8_t* src, uint8_t* dst, int lane)
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    for (uint32_t i0 = 0; i0 < rc; i0 += 64) emit_records(rec, i0, rc, anchor, src, dst, lane);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 }
 
 template <bool U32TAB>
@@ -141,7 +158,7 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
     // between the two places), so the load has the walk, the records, the commit and the next table phase to arrive and is first
     // waited for a piece later, where it is stored.  The coordinate of position p is p + ralign, which makes every piece load
     // aligned in memory.
-    auto ralign_now = [&]() -> uint32_t {                               // (taken from src where it is used: not one more scalar kept across the walk)
+    auto ralign_now = [&]() -> uint32_t {                               // (taken from src once at the top of a window and kept up to the piece's load: not one more scalar across the walk)
         uint32_t a;
         asm volatile("s_and_b32 %0, %1, 15" : "=s"(a) : "s"(uint32_t(reinterpret_cast<uintptr_t>(src))) : "scc");
         return a;
@@ -151,12 +168,12 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
     Q16 rnext{0, 0, 0, 0};
     // One load, every lane, no wait where it is issued: only bytes of [src, src + n) are read - at the two ends of the block the
     // nearest 16 of them, which piece_store moves to their place (or drops) a piece later.
-    auto piece_load = [&](uint32_t k) -> Q16 {
-        const int p = int(k * kPiece + 16u * uint32_t(lane)) - int(ralign_now());
+    auto piece_load = [&](uint32_t k, uint32_t ralign) -> Q16 {
+        const int p = int(k * kPiece + 16u * uint32_t(lane)) - int(ralign);
         return ld16(src + min(max(p, 0), n - 16));
     };
-    auto piece_store = [&](uint32_t k, Q16 v) {
-        const int p = int(k * kPiece + 16u * uint32_t(lane)) - int(ralign_now());
+    auto piece_store = [&](uint32_t k, Q16 v, uint32_t ralign) {
+        const int p = int(k * kPiece + 16u * uint32_t(lane)) - int(ralign);
         const int sh = p - min(max(p, 0), n - 16);
         if (__ballot(sh != 0)) {                                        // an end of the block lies in this piece
             unsigned __int128 w = (static_cast<unsigned __int128>(u64(v.d2, v.d3)) << 64) | u64(v.d0, v.d1);
@@ -248,15 +265,17 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
         // whose ip-2 refill and immediate re-test (lz4.c:1207-1259) are still owed and whose search starts at sp+1;
         // otherwise it is probe number k0 of the running search.
         uint32_t sp = 1, k0 = 0; bool retest = false;
+        // Can the record area fill at all?  A block of n bytes has at most n/4 matches (each takes four bytes of input or more), so
+        // with the default area and n <= FOURMC_BLOCKSIZE it cannot.  That flag, worked out once, is kept as the limit itself - out
+        // of reach for such a block - so a window ends with one scalar compare and no second test of a flag.
+        const uint32_t rc_lim = un / 4 > reccap - kRecSlack ? reccap - kRecSlack : 0xFFFFFFFFu;
         for (;;) {
-            if (rc > reccap - kRecSlack) {
-                // the record area is full (only a block above FOURMC_BLOCKSIZE gets here): its bytes go out now
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                for (uint32_t i0 = 0; i0 < rc; i0 += 64) emit_records(rec, i0, rc, anchor, src, dst, lane);
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                rc = 0;
-            }
-            if (sp >= 4 && sp + 132 <= un && k0 <= 32) {
+            if (rc > rc_lim) { drain_records(rec, rc, anchor, src, dst, lane); rc = 0; }
+            // The dense windows are a loop of their own: its only back edge is the commit, and whatever else a window comes to leaves
+            // through the one exit below - `status` (1: last literals, 2: output full), a window that cannot follow (the sparse
+            // batch takes over), or a record area that may be full (back to the top).
+            int status = 0;
+            if (sp >= 4) while (sp + 132 <= un && k0 <= 32) {        // (sp only grows: tested once, not per window)
                 // ------------------------------------------------------------ dense window
                 // Probes 0..65 of a search are one byte apart, so around a fresh search the parse walks consecutive
                 // positions.  Lane l takes position sp+l, whatever role the parse will give it (probe, re-test,
@@ -271,19 +290,21 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 Q16 q0, q1;                                                              // [pos-4, pos+28)
                 uint32_t rpos = 0;                                                       // where they are in the ring
                 bool ask = false;                                                        // the ring moved: its next piece is owed
+                uint32_t ralign = 0;                                                     // src & 15, once per window
                 if (U32TAB) {
                     // The window reads [sp0-4, sp0+124): at most two pieces.  When it reaches piece `rend` the ring moves on by
                     // the piece in `rnext` (asked for a piece ago: no wait); after a jump past that, or after a sparse batch, it
                     // starts again at the window's two pieces (one trip to memory for both, as every window paid before).
                     // Either way the piece after them is asked for further down, once the candidates are in.
-                    const uint32_t a0 = sp0 + ralign_now() - 4;
+                    ralign = ralign_now();
+                    const uint32_t a0 = sp0 + ralign - 4;
                     const uint32_t c_lo = a0 >> kPieceLog, c_hi = (a0 + 127) >> kPieceLog;
                     if (c_hi >= rend) {
-                        if (rend != 0 && c_hi == rend) { K2CNT(pt_nrot); piece_store(rend, rnext); rend = VG(rend + 1); }
+                        if (rend != 0 && c_hi == rend) { K2CNT(pt_nrot); piece_store(rend, rnext, ralign); rend = VG(rend + 1); }
                         else {
                             K2CNT(pt_nrel);
-                            const Q16 a = piece_load(c_lo), b = piece_load(c_lo + 1);
-                            piece_store(c_lo, a); piece_store(c_lo + 1, b);
+                            const Q16 a = piece_load(c_lo, ralign), b = piece_load(c_lo + 1, ralign);
+                            piece_store(c_lo, a, ralign); piece_store(c_lo + 1, b, ralign);
                             rend = VG(c_lo + 2);
                         }
                         ask = true;
@@ -345,6 +366,16 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 uint32_t info;
                 bool hit = false, slow = false;
                 uint32_t fw = 0, bk = 0;
+                if (U32TAB) {
+                    // every lane holds 32 bytes of a candidate (of its own position where it has none): all of them compare, with
+                    // selects and without a branch, and only `hit` asks whether the candidate is one
+                    hit = near && c0.d1 == q0.d1;
+                    const uint32_t xb = q0.d0 ^ c0.d0;
+                    bk = eq_msb(xb);
+                    const uint32_t e0 = eq_lsb(u64(q0.d2, q0.d3) ^ u64(c0.d2, c0.d3)), e1 = eq_lsb(u64(q1.d0, q1.d1) ^ u64(c1.d0, c1.d1)),
+                                   e2 = eq_lsb(u64(q1.d2, q1.d3) ^ u64(c1.d2, c1.d3));
+                    fw = e0 < 8 ? e0 : (e1 < 8 ? 8u + e1 : 16u + e2);
+                } else
                 if (near) {
                     if (!U32TAB) { c0 = ld16(src + c - 4); c1 = ld16(src + c + 12); }
                     hit = c0.d1 == q0.d1;
@@ -390,7 +421,7 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                     // than the piece outstanding, so that no wait of the walk stands for it - the piece is first waited for where
                     // it is stored
                     __builtin_amdgcn_s_waitcnt(0x0F70);
-                    if (ask) rnext = piece_load(rend);
+                    if (ask) rnext = piece_load(rend, ralign);
                 }
                 // The first sequence may own literals from before the window, any number of them: its record needs only
                 // where they begin.  Near the end of the output buffer (what the window can write at most: those literals
@@ -404,10 +435,11 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 const unsigned long long hd2 = m_hit | stop2;
                 unsigned long long hd = m_hit | stop1, stp = stop1;
                 unsigned long long selw = 0, xint = 0;                  // chosen hit lanes; lanes inside directly emitted matches
+                unsigned long long in1 = 0; int rounds = 0;             // lanes inside the matches of the first record round; rounds
                 int cur = 0, anc = int(anchor - sp0);                   // lane of the next action; anchor as a lane number
                 bool any = retest, fresh = true;                        // a search has begun in this window; no sequence yet
                 bool gen = false;                                       // take one general step next (a resolved second lane)
-                int stoplane = 64, status = 0;
+                int stoplane = 64;
                 // Where the walk goes from lane l when a search starts there with nothing pending (anchor == l), for
                 // every l at once: the end of the first hit at or after l (| that hit lane << 8), or 0x8000 | the lane
                 // it has to stop at (64: none).  The scalar walk below is then one readlane per sequence.
@@ -492,6 +524,7 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                         op = U(op + rl(incl, 63));
                         anchor = sp0 + uint32_t(anc);
                         selw |= sel; any = true; fresh = false;
+                        if (rounds++ == 0) in1 = __ballot(below && lane < endP && lane != endP - 2);
                     }
                     K2PH(pt_emit);
                     if (reason == 0) {                                  // every remaining lane was a probe
@@ -568,15 +601,20 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                         hd = hd2; stp = stop2;
                     }
                 }
-                if (status == 2) return 0;
-                if (status == 1) goto last_literals;
+                if (status) break;
                 // commit: every lane the walk passed as a probe, re-test or refill enters the table; the latest
                 // position of a slot wins (a refill lane may share its slot with an earlier probe)
                 {
-                    const unsigned long long below = selw & ~(~0ull << lane);
-                    const int P = below ? 63 - __builtin_clzll(below) : 0;
-                    const int endP = int(__shfl(info, P) & 255);
-                    const bool inside = (below && lane < endP && lane != endP - 2) || ((xint >> lane) & 1);
+                    // (which lanes lie inside a chosen match is what the record round found for its own lanes: taken from there
+                    // when the window had one round or none, worked out from all chosen lanes otherwise)
+                    unsigned long long in = in1;
+                    if (rounds > 1) {
+                        const unsigned long long below = selw & ~(~0ull << lane);
+                        const int P = below ? 63 - __builtin_clzll(below) : 0;
+                        const int endP = int(__shfl(info, P) & 255);
+                        in = __ballot(below && lane < endP && lane != endP - 2);
+                    }
+                    const bool inside = ((in | xint) >> lane) & 1;
                     if (lane < stoplane && !inside) {
                         if (U32TAB) atomicMax(&tab32[h], enc(pos, ck));
                         else for (;;) { tab16[h] = uint16_t(pos); asm volatile("" ::: "memory"); if (uint32_t(tab16[h]) >= pos) break; }
@@ -584,8 +622,11 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 }
                 sp = U(sp); k0 = U(k0);
                 K2PH(pt_match);
-                continue;
+                if (rc > rc_lim) break;
             }
+            if (status == 2) return 0;
+            if (status == 1) goto last_literals;
+            if (rc > rc_lim) continue;
             // ---------------------------------------------------------------- sparse batch (lz4.c:1014-1076)
             // 64 probes of the running search at their strided positions: start and end of a block, and searches
             // that found nothing for a while.  The first lane (serial order) that hits or reaches the end limit ends
