@@ -65,6 +65,16 @@ class BstreamEncItem(C.Structure):
 
 
 assert C.sizeof(BstreamEncItem) == 72
+
+
+# struct fourmc_image_wr_item (include/fourmc_gpu.h: images from a job's write() calls); its reason is a FOURMC_BSW_* number
+class ImageWrItem(C.Structure):
+    _fields_ = [("src_off", C.c_uint64), ("src_bytes", C.c_uint64), ("image_off", C.c_uint64), ("image_cap", C.c_uint64),
+                ("writes_off", C.c_uint64), ("n_writes", C.c_uint64), ("write_bytes", C.c_uint32), ("reason", C.c_int32),
+                ("image_bytes", C.c_uint64), ("blocks", C.c_uint64), ("stored_blocks", C.c_uint64)]
+
+
+assert C.sizeof(ImageWrItem) == 80
 # FOURMC_BSW_*: the verdict of compress_bstreams on one stream, by number
 BSTREAM_WRITE_REASONS = ("OK", "SUM", "WRITE", "CAP")
 # FOURMC_BS_*: the verdict of a block-stream decode, by number
@@ -264,6 +274,8 @@ _GPU_API = {
     "fourmc_gpu_get_zst_round_blocks": (C.c_uint32, []),
     "fourmc_gpu_bstreams_compress": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_bstream_writes_bound": (C.c_uint64, [C.c_uint64, C.c_int]),
+    "fourmc_gpu_images_compress_writes": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "fourmc_gpu_image_writes_bound": (C.c_uint64, [C.c_uint64]),
     "fourmc_gpu_image_parse_stats": (None, [C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_decode_blocks": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),

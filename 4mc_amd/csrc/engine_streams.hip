@@ -327,6 +327,169 @@ int fourmc_gpu_bstreams_compress(const void* d_src, uint64_t src_total, const ui
     return FOURMC_OK;
 }
 
+// ---- .4mc / .4mz images from write() sizes --------------------------------------------------------------------------------------
+// FourMcOutputStream's blocks are the chunks of the plan above with M = 4 MiB (include/fourmc_gpu.h has the rule and its lines)
+uint64_t fourmc_gpu_image_writes_bound(uint64_t src_bytes)
+{
+    if (src_bytes > (~0ull >> 1)) return ~0ull;
+    return 12 + 16 * bsw_max_chunks(src_bytes, FOURMC_BLOCKSIZE) + src_bytes + 32;
+}
+
+// Workspaces as in bstreams_compress.  g_img_ws: the items (as the planner's own item type), the first tile of every stream, the plans
+// and the tile prefixes.  g_img_stage, sized after the plan's read-back: the slices, one running pair and one result per stream, the
+// bad count, the group table, the offset of every block of the call (the footers' index), and the descriptors, side entries, seal
+// descriptors and staging of one round.
+int fourmc_gpu_images_compress_writes(const void* d_src, uint64_t src_total, const uint32_t* d_writes, uint64_t writes_total,
+                                      void* d_images, uint64_t images_bytes, uint32_t magic, int level,
+                                      fourmc_image_wr_item* items, uint32_t n, void* stream)
+{
+    if (magic != FOURMC_MAGIC_4MC && magic != FOURMC_MAGIC_4MZ) { snprintf(g_err, sizeof g_err, "magic 0x%08x is neither 4mc nor 4mz", magic); return FOURMC_EINVAL; }
+    if (n == 0) return FOURMC_OK;
+    if (!items) { snprintf(g_err, sizeof g_err, "images_compress_writes: null items"); return FOURMC_EINVAL; }
+    std::vector<uint64_t> tile0(size_t(n) + 1);
+    std::vector<fourmc_bstream_enc_item> bi(n);
+    {
+        std::vector<std::pair<uint64_t, uint64_t>> d;
+        if (d_images) d.reserve(n);
+        uint64_t tiles = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            const fourmc_image_wr_item& it = items[i];
+            if (it.src_bytes && !d_src) { snprintf(g_err, sizeof g_err, "images_compress_writes: null source"); return FOURMC_EINVAL; }
+            if (it.n_writes && !d_writes) { snprintf(g_err, sizeof g_err, "images_compress_writes: null write table"); return FOURMC_EINVAL; }
+            if (span_outside(it.src_off, it.src_bytes, src_total)) {
+                snprintf(g_err, sizeof g_err, "images_compress_writes: the source of stream %u lies beyond the %llu bytes of sources", i, (unsigned long long)src_total);
+                return FOURMC_EINVAL;
+            }
+            if (span_outside(it.writes_off, it.n_writes, writes_total)) {
+                snprintf(g_err, sizeof g_err, "images_compress_writes: the write sizes of stream %u lie beyond the %llu entries of the table", i, (unsigned long long)writes_total);
+                return FOURMC_EINVAL;
+            }
+            fourmc_bstream_enc_item& b = bi[i];
+            b = {};
+            b.src_off = it.src_off; b.src_bytes = it.src_bytes; b.image_off = it.image_off; b.image_cap = it.image_cap;
+            b.writes_off = it.writes_off; b.n_writes = it.n_writes; b.write_bytes = it.write_bytes;
+            tile0[i] = tiles;
+            tiles += it.n_writes / 64 + (it.n_writes % 64 ? 1 : 0);
+            if (!d_images) continue;                          // the size query looks at no region
+            if (span_outside(it.image_off, it.image_cap, images_bytes)) {
+                snprintf(g_err, sizeof g_err, "images_compress_writes: the region of stream %u lies beyond the %llu bytes of images", i, (unsigned long long)images_bytes);
+                return FOURMC_EINVAL;
+            }
+            if (it.image_cap) d.emplace_back(it.image_off, it.image_off + it.image_cap);
+        }
+        tile0[n] = tiles;
+        if (int r = regions_overlap("images_compress_writes", "image regions", d)) return r;
+    }
+    int codec_level = 0;
+    const int codec = fourmc_level_codec(magic, level, &codec_level);
+    const int zstd = codec == FOURMC_CODEC_ZSTD;
+    if (int r = ensure_device()) return r;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t M = FOURMC_BLOCKSIZE;
+    const uint64_t ntiles = tile0[n];
+    const size_t o_tile0 = align256(size_t(n) * sizeof(fourmc_bstream_enc_item)), o_plans = o_tile0 + align256((size_t(n) + 1) * 8);
+    const size_t o_prefix = o_plans + align256(size_t(n) * sizeof(fourmc_bsw_plan));
+    WsLease ws(&g_img_ws); void* w = nullptr;
+    if (int r = ws.get(s, o_prefix + size_t(ntiles) * 8, &w)) return r;
+    char* base = static_cast<char*>(w);
+    auto* d_items = reinterpret_cast<fourmc_bstream_enc_item*>(base);
+    auto* d_tile0 = reinterpret_cast<uint64_t*>(base + o_tile0);
+    auto* d_plans = reinterpret_cast<fourmc_bsw_plan*>(base + o_plans);
+    auto* d_prefix = reinterpret_cast<uint64_t*>(base + o_prefix);
+    HIP_TRY(hipMemcpyAsync(d_items, bi.data(), size_t(n) * sizeof(fourmc_bstream_enc_item), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_tile0, tile0.data(), (size_t(n) + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(fourmc_launch_bsw_sums(d_writes, d_items, d_tile0, n, ntiles, d_prefix, d_plans, s));
+    HIP_TRY(fourmc_launch_bsw_chase(d_writes, d_items, d_tile0, d_prefix, n, M, zstd, d_plans, nullptr, nullptr, s));
+    std::vector<fourmc_bsw_plan> plans(n);
+    HIP_TRY(hipMemcpyAsync(plans.data(), d_plans, size_t(n) * sizeof(fourmc_bsw_plan), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<fourmc_bsw_slice> slices(size_t(n) + 1);
+    std::vector<uint64_t> worst(n);
+    fourmc_bsw_slice at = {};
+    for (uint32_t i = 0; i < n; i++) {                   // each written stream's share of the block numbers, the group table and the staging
+        fourmc_bsw_plan& pl = plans[i];
+        if (pl.reason == FOURMC_BSW_OK && (pl.groups > 0xFFFFFFFFull || pl.chunks > 0x7FFFFFFFull)) {
+            snprintf(g_err, sizeof g_err, "images_compress_writes: stream %u has %llu blocks", i, (unsigned long long)pl.chunks);
+            return FOURMC_EUNSUP;
+        }
+        worst[i] = 44 + 16 * pl.chunks + items[i].src_bytes;    // header, 12 + len per block, end mark, footer
+        if (d_images && pl.reason == FOURMC_BSW_OK && items[i].image_cap < worst[i]) pl.reason = FOURMC_BSW_CAP;
+        slices[i] = at;
+        if (pl.reason != FOURMC_BSW_OK) continue;
+        at.chunk0 += pl.chunks; at.stage0 += pl.stage;
+        if (items[i].n_writes) at.group0 += pl.groups;
+        if (at.chunk0 > 0x7FFFFFFFull) { snprintf(g_err, sizeof g_err, "images_compress_writes: more than 0x7FFFFFFF blocks"); return FOURMC_EUNSUP; }
+    }
+    slices[n] = at;
+    auto report = [&](const std::vector<fourmc_imgw_result>* res) {
+        for (uint32_t i = 0; i < n; i++) {
+            const fourmc_bsw_plan& pl = plans[i];
+            const bool planned = pl.reason == FOURMC_BSW_OK || pl.reason == FOURMC_BSW_CAP, written = res && pl.reason == FOURMC_BSW_OK;
+            items[i].reason = pl.reason;
+            items[i].blocks = planned ? pl.chunks : 0;
+            items[i].stored_blocks = written ? (*res)[i].stored : 0;
+            items[i].image_bytes = !planned ? 0 : written ? (*res)[i].image_bytes : worst[i];
+        }
+    };
+    if (!d_images) { report(nullptr); return FOURMC_OK; }
+    const uint32_t round = bsw_round();
+    const uint64_t nc = at.chunk0;
+    const uint32_t piece = uint32_t(nc < round ? nc : round);
+    const uint64_t slot_m = align256(bs_block_bound(zstd, M));
+    const uint64_t stage = at.stage0 < uint64_t(piece) * slot_m ? at.stage0 : uint64_t(piece) * slot_m;
+    const size_t o_run = align256((size_t(n) + 1) * sizeof(fourmc_bsw_slice)), o_res = o_run + align256(size_t(n) * sizeof(fourmc_imgw_run));
+    const size_t o_bad = o_res + align256(size_t(n) * sizeof(fourmc_imgw_result)), o_grp = o_bad + 256;
+    const size_t o_idx = o_grp + align256(size_t(at.group0) * sizeof(fourmc_bsw_group)), o_blk = o_idx + align256(size_t(nc) * 8);
+    const size_t o_side = o_blk + align256(size_t(piece) * sizeof(fourmc_block)), o_seal = o_side + align256(size_t(piece) * sizeof(fourmc_bsw_side));
+    const size_t o_stage = o_seal + align256(size_t(piece) * sizeof(fourmc_block));
+    WsLease ws2(&g_img_stage); void* w2 = nullptr;
+    if (int r = ws2.get(s, o_stage + size_t(stage) + kImagesStageSlack, &w2)) return r;
+    char* b2 = static_cast<char*>(w2);
+    auto* d_slices = reinterpret_cast<fourmc_bsw_slice*>(b2);
+    auto* d_run = reinterpret_cast<fourmc_imgw_run*>(b2 + o_run);
+    auto* d_res = reinterpret_cast<fourmc_imgw_result*>(b2 + o_res);
+    auto* d_bad = reinterpret_cast<uint64_t*>(b2 + o_bad);
+    auto* d_grp = reinterpret_cast<fourmc_bsw_group*>(b2 + o_grp);
+    auto* d_idx = reinterpret_cast<uint64_t*>(b2 + o_idx);
+    auto* d_blk = reinterpret_cast<fourmc_block*>(b2 + o_blk);
+    auto* d_side = reinterpret_cast<fourmc_bsw_side*>(b2 + o_side);
+    auto* d_seal = reinterpret_cast<fourmc_block*>(b2 + o_seal);
+    char* d_stage = b2 + o_stage;
+    HIP_TRY(hipMemcpyAsync(d_plans, plans.data(), size_t(n) * sizeof(fourmc_bsw_plan), hipMemcpyHostToDevice, s));      // with the _CAP verdicts
+    HIP_TRY(hipMemcpyAsync(d_slices, slices.data(), (size_t(n) + 1) * sizeof(fourmc_bsw_slice), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_run, 0, size_t(n) * sizeof(fourmc_imgw_run), s));
+    HIP_TRY(hipMemsetAsync(d_bad, 0, 8, s));
+    if (at.group0) HIP_TRY(fourmc_launch_bsw_chase(d_writes, d_items, d_tile0, d_prefix, n, M, zstd, d_plans, d_slices, d_grp, s));
+    // the XXH32 and the pack read a stored block's bytes from d_src and a compressed one's from the staging through one base address:
+    // the lower of the two, as the streaming writer's batches do
+    const uintptr_t p_src = reinterpret_cast<uintptr_t>(d_src), p_stage = reinterpret_cast<uintptr_t>(d_stage);
+    const uintptr_t lo = nc && p_src < p_stage ? p_src : p_stage;
+    for (uint64_t c0 = 0; c0 < nc; c0 += piece) {
+        const uint32_t m = uint32_t(nc - c0 < piece ? nc - c0 : piece);
+        HIP_TRY(fourmc_launch_bsw_desc(d_items, d_plans, d_slices, d_grp, n, M, zstd, codec == FOURMC_CODEC_LZ4_MC, c0, m, d_blk, d_side, s));
+        int r;
+        switch (codec) {
+            case FOURMC_CODEC_LZ4_FAST: r = fourmc_gpu_lz4_compress_fast(d_src, d_stage, d_blk, m, s); break;
+            case FOURMC_CODEC_LZ4_MC:   r = fourmc_gpu_lz4_compress_mc(d_src, d_stage, d_blk, m, s); break;
+            case FOURMC_CODEC_LZ4_HC:   r = fourmc_gpu_lz4_compress_hc(d_src, d_stage, d_blk, m, codec_level, s); break;
+            default:                    r = fourmc_gpu_zstd_compress(d_src, d_stage, d_blk, m, codec_level, s); break;
+        }
+        if (r) return r;
+        HIP_TRY(fourmc_launch_imgw_seal(d_blk, d_side, m, zstd, d_items, p_src - lo, p_stage - lo, d_seal, d_idx + c0, d_run, d_bad, s));
+        HIP_TRY(fourmc_launch_xxh32(reinterpret_cast<const void*>(lo), d_seal, m, 0, FOURMC_HASH_DST_RESULT, s));
+        HIP_TRY(fourmc_launch_pack_image(reinterpret_cast<const void*>(lo), d_images, d_seal, d_idx + c0, m, s));
+    }
+    HIP_TRY(fourmc_launch_imgw_tail(d_images, d_items, d_plans, d_slices, d_idx, d_run, n, magic, d_res, s));
+    std::vector<fourmc_imgw_result> res(n);
+    uint64_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(res.data(), d_res, size_t(n) * sizeof(fourmc_imgw_result), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bad) { snprintf(g_err, sizeof g_err, "images_compress_writes: %llu blocks with a codec result outside [1, bound]", (unsigned long long)bad); return FOURMC_EINVAL; }
+    report(&res);
+    return FOURMC_OK;
+}
+
 // The decode of n streams: the single call is its n = 1 case.  Workspace (g_img_ws): the items, one summary, one first-descriptor
 // number and one status per stream, then - sized after the first read-back - the descriptors and the side table of every stream.
 // When that grows the buffer its contents are gone: the items and the summaries (the host has both) go up again.

@@ -17,6 +17,9 @@
 // gives every image its slice of one descriptor table.
 // Many images, the encode (fourmc_gpu_images_compress): the same descriptors, scan and tail, one wave or workgroup per image, over
 // slices of one descriptor table and one dense offset table that the engine has laid out from the sizes.
+// Images from write() sizes (fourmc_gpu_images_compress_writes): blocks cut as Hadoop's FourMcOutputStream cuts them, planned and
+// described by the block streams' kernels (bstream.hip); here the seal (stored or compressed, by the stream's rule) with the
+// segmented scan across rounds, and the tail per image.
 // Random access (second half): the footer index of a single stream, block-range decodes and byte-range reads, each with the
 // verdict fourmc_file_decode_blocks (fourmc_file.c) reaches on the same bytes as a file.
 // Streaming reads (last part): the walk restated to stop at the end of each appended chunk and resume at the next, the gather of
@@ -191,6 +194,86 @@ void images_enc_tail_kernel(uint8_t* __restrict__ images, const fourmc_image_enc
     const uint32_t i = blockIdx.x;
     const fourmc_image_enc_plan pl = plans[i];
     enc_tail(images + pl.image_off, off + pl.first, pl.nblocks, end[i] - pl.image_off, pl.image_off, magic);
+}
+
+// ---- images from write() sizes (fourmc_gpu_images_compress_writes): the blocks are the chunks of the block streams' plan at
+// M = 4 MiB and come in rounds, with that plan's descriptors and side entries (bstream.hip: bsw_desc_kernel); the raw codec call has
+// run over them with the codec's bound as the capacity.
+// Seal and scan, one wave over the round's m blocks.  Seal (FourMcOutputStream.java:204): a block whose result c is not below its
+// length u is stored.  seal[b] names the bytes that go behind block b's header from ONE base address, so that one XXH32 launch and
+// one pack launch serve stored and compressed blocks alike: dst_off = the source bytes (src_delta + src_off) or the staging slot
+// (stage_delta + dst_off), result = their number (u or c), src_len = u.  Scan: idx[b] = the block header's absolute offset in
+// d_images = its stream's image_off + 12 + the bytes of the stream's blocks in front of it: those of earlier rounds in
+// run[stream].bytes, those of this round by the wave's prefix sum less its value at the segment's head (a stream's blocks are
+// consecutive).  A result outside [1, bound] is counted in *bad and the block stored, so nothing leaves the worst case the engine
+// checked the capacity against.
+__global__ __launch_bounds__(64)
+void imgw_seal_kernel(const fourmc_block* __restrict__ blocks, const fourmc_bsw_side* __restrict__ side, uint32_t m, int zstd,
+                      const fourmc_bstream_enc_item* __restrict__ items, uint64_t src_delta, uint64_t stage_delta,
+                      fourmc_block* __restrict__ seal, uint64_t* __restrict__ idx, fourmc_imgw_run* __restrict__ run,
+                      uint64_t* __restrict__ bad_out)
+{
+    const int lane = threadIdx.x;
+    uint32_t run_stream = 0xFFFFFFFFu, bad = 0;
+    uint64_t run_bytes = 0, run_stored = 0;
+    for (uint32_t b0 = 0; b0 < m; b0 += 64) {
+        const uint32_t b = b0 + uint32_t(lane);
+        const bool valid = b < m;
+        uint32_t step = 0, st = 0xFFFFFFFFu, stored = 0;
+        if (valid) {
+            const fourmc_block d = blocks[b];
+            st = side[b].stream;
+            const bool wrong = d.result <= 0 || uint32_t(d.result) > fourmc_bstream_block_bound(zstd, d.src_len);
+            bad += wrong;
+            stored = wrong || d.src_len <= uint32_t(d.result);
+            fourmc_block q;
+            q.src_off = d.src_off; q.src_len = d.src_len;
+            q.dst_off = stored ? src_delta + d.src_off : stage_delta + d.dst_off;
+            q.result = int32_t(stored ? d.src_len : uint32_t(d.result));
+            q.dst_cap = uint32_t(q.result); q.xxh32 = 0;
+            seal[b] = q;
+            step = 12u + uint32_t(q.result);
+        }
+        const uint32_t incl = scan_add(step), incl_s = scan_add(stored);
+        const uint32_t before = uint32_t(__shfl_up(int(st), 1)), after = uint32_t(__shfl_down(int(st), 1));
+        const unsigned long long heads = __ballot(valid && (lane == 0 || before != st));
+        const int h = 63 - __builtin_clzll((heads & (~0ull >> (63 - lane))) | 1ull);       // the head of this lane's segment
+        const uint32_t excl_h = uint32_t(__shfl(int(incl - step), h)), excl_sh = uint32_t(__shfl(int(incl_s - stored), h));
+        uint64_t end = 0, end_s = 0;
+        if (valid) {
+            const bool cont = h == 0 && st == run_stream;                                  // the segment began in an earlier step
+            const uint64_t pos = (cont ? run_bytes : run[st].bytes) + (incl - step - excl_h);
+            idx[b] = items[st].image_off + 12 + pos;
+            end = pos + step;
+            end_s = (cont ? run_stored : run[st].stored) + (incl_s - excl_sh);
+        }
+        const int last = 63 - __builtin_clzll(__ballot(valid));
+        if (valid && (lane == last || after != st)) { fourmc_imgw_run r; r.bytes = end; r.stored = end_s; run[st] = r; }
+        run_stream = uint32_t(__shfl(int(st), last));
+        run_bytes = uint64_t(__shfl((long long)end, last));
+        run_stored = uint64_t(__shfl((long long)end_s, last));
+    }
+    for (int o = 32; o; o >>= 1) bad += uint32_t(__shfl_xor(int(bad), o));
+    if (lane == 0) *bad_out += bad;
+}
+// Tail, one workgroup per stream that is written: its block offsets are its slice of idx (absolute, so the footer's first delta is
+// the in-image 12), its end mark lies behind its last block
+__global__ __launch_bounds__(256)
+void imgw_tail_kernel(uint8_t* __restrict__ images, const fourmc_bstream_enc_item* __restrict__ items,
+                      const fourmc_bsw_plan* __restrict__ plans, const fourmc_bsw_slice* __restrict__ slices,
+                      const uint64_t* __restrict__ idx, const fourmc_imgw_run* __restrict__ run, uint32_t magic,
+                      fourmc_imgw_result* __restrict__ res)
+{
+    const uint32_t i = blockIdx.x;
+    const fourmc_bsw_plan pl = plans[i];
+    if (pl.reason != FOURMC_BSW_OK) {
+        if (threadIdx.x == 0) { fourmc_imgw_result r; r.image_bytes = 0; r.stored = 0; res[i] = r; }
+        return;
+    }
+    const fourmc_imgw_run rn = run[i];
+    const uint64_t image_off = items[i].image_off, end = 12 + rn.bytes;
+    enc_tail(images + image_off, idx + slices[i].chunk0, uint32_t(pl.chunks), end, image_off, magic);
+    if (threadIdx.x == 0) { fourmc_imgw_result r; r.image_bytes = end + 12 + 20 + 4 * pl.chunks; r.stored = rn.stored; res[i] = r; }
 }
 
 // ------------------------------------------------------------------------------------------------------------- decode
@@ -1075,6 +1158,26 @@ hipError_t fourmc_launch_images_enc_frame(void* d_images, const fourmc_image_enc
     if (hipError_t e = hipGetLastError()) return e;
     if (hipError_t e = fourmc_launch_pack_image(d_staging, d_images, d_blocks, d_off, nblocks, s)) return e;
     hipLaunchKernelGGL(images_enc_tail_kernel, dim3(n), dim3(256), 0, s, static_cast<uint8_t*>(d_images), d_plans, d_off, d_end, magic);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_imgw_seal(const fourmc_block* d_blocks, const fourmc_bsw_side* d_side, uint32_t m, int zstd,
+                                   const fourmc_bstream_enc_item* d_items, uint64_t src_delta, uint64_t stage_delta,
+                                   fourmc_block* d_seal, uint64_t* d_idx, fourmc_imgw_run* d_run, uint64_t* d_bad, hipStream_t s)
+{
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(imgw_seal_kernel, dim3(1), dim3(64), 0, s, d_blocks, d_side, m, zstd, d_items, src_delta, stage_delta, d_seal,
+                       d_idx, d_run, d_bad);
+    return hipGetLastError();
+}
+
+hipError_t fourmc_launch_imgw_tail(void* d_images, const fourmc_bstream_enc_item* d_items, const fourmc_bsw_plan* d_plans,
+                                   const fourmc_bsw_slice* d_slices, const uint64_t* d_idx, const fourmc_imgw_run* d_run, uint32_t n,
+                                   uint32_t magic, fourmc_imgw_result* d_res, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(imgw_tail_kernel, dim3(n), dim3(256), 0, s, static_cast<uint8_t*>(d_images), d_items, d_plans, d_slices, d_idx,
+                       d_run, magic, d_res);
     return hipGetLastError();
 }
 

@@ -462,6 +462,23 @@ hipError_t fourmc_launch_bsw_pack(void* d_images, const fourmc_bstream_enc_item*
 /* d_bytes[i] = the length of stream i (0 for one with a verdict); writes the four bytes of a stream without a chunk */
 hipError_t fourmc_launch_bsw_result(const fourmc_bstream_enc_item* d_items, const fourmc_bsw_plan* d_plans, const uint64_t* d_carry,
                                     uint32_t n, void* d_images, uint64_t* d_bytes, hipStream_t s);
+/* fourmc_gpu_images_compress_writes (image.hip): .4mc / .4mz images whose blocks are the chunks of the plan above at M = 4 MiB.
+ * Per stream on the device: the bytes of its blocks placed so far (the 64-bit carry of the scan) and its stored blocks; what the
+ * tail leaves per stream for the read-back. */
+typedef struct fourmc_imgw_run { uint64_t bytes, stored; } fourmc_imgw_run;
+typedef struct fourmc_imgw_result { uint64_t image_bytes, stored; } fourmc_imgw_result;
+/* after the raw codec launch over the round's m blocks (d_blocks, d_side from fourmc_launch_bsw_desc): d_seal[b] describes the bytes
+ * block b writes behind its header, counted from one base address - src_delta + src_off for a stored block (src_len <= result),
+ * stage_delta + dst_off for a compressed one - in dst_off, their number in result and the block's length in src_len; d_idx[b] = the
+ * absolute offset of block b's header in d_images, by a segmented scan from and back into d_run[stream]; bad codec results (outside
+ * [1, bound]) are counted in *d_bad and stored */
+hipError_t fourmc_launch_imgw_seal(const fourmc_block* d_blocks, const fourmc_bsw_side* d_side, uint32_t m, int zstd,
+                                   const fourmc_bstream_enc_item* d_items, uint64_t src_delta, uint64_t stage_delta,
+                                   fourmc_block* d_seal, uint64_t* d_idx, fourmc_imgw_run* d_run, uint64_t* d_bad, hipStream_t s);
+/* one workgroup per stream that is FOURMC_BSW_OK: header, end mark and footer from its slice of d_idx; d_res[i] for every stream */
+hipError_t fourmc_launch_imgw_tail(void* d_images, const fourmc_bstream_enc_item* d_items, const fourmc_bsw_plan* d_plans,
+                                   const fourmc_bsw_slice* d_slices, const uint64_t* d_idx, const fourmc_imgw_run* d_run, uint32_t n,
+                                   uint32_t magic, fourmc_imgw_result* d_res, hipStream_t s);
 #ifdef FOURMC_RESEARCH      /* the research side build exports these two: tools/zstd_timing.py and tools/k7x_prof.py size their read-backs with them */
 #pragma GCC visibility push(default)
 #endif

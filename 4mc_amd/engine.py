@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .binding import (ZST_REASONS, ZSTW_REASONS, ZstItem, ZstStatus, ZstwItem, ZstwStatus, BLOCK_DTYPE, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, CODEC_LZ4_FAST, BstreamEncItem, BstreamItem, BstreamStatus, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageIndexInfo, ImageItem, ImageLines, ImageLineInfo, ImageLinesAt, ImageRef, ImageSplitItem,
+from .binding import (ZST_REASONS, ZSTW_REASONS, ZstItem, ZstStatus, ZstwItem, ZstwStatus, BLOCK_DTYPE, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, CODEC_LZ4_FAST, BstreamEncItem, BstreamItem, BstreamStatus, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageWrItem, ImageIndexInfo, ImageItem, ImageLines, ImageLineInfo, ImageLinesAt, ImageRef, ImageSplitItem,
                       ImagesSlice, ImagesSplitItem,
                       ImageRange, ImageRecords, ImageSlice, ImageStatus, check, lib)
 
@@ -253,6 +253,43 @@ def compress_bstreams(d_src, items, d_images, codec=CODEC_LZ4_FAST, level=0, d_w
     check(lib().fourmc_gpu_bstreams_compress(src, total, tab, ntab, img, cap, int(codec), int(level), C.cast(arr, C.c_void_p), len(q),
                                              _stream_ptr(stream)), "fourmc_gpu_bstreams_compress")
     return [{"image_bytes": int(arr[i].image_bytes), "groups": int(arr[i].groups), "chunks": int(arr[i].chunks), "reason": int(arr[i].reason),
+             "name": BSTREAM_WRITE_REASONS[arr[i].reason] if 0 <= arr[i].reason < len(BSTREAM_WRITE_REASONS) else "?"}
+            for i in range(len(q))]
+
+
+def image_writes_bound(src_bytes):
+    """A capacity that holds for the image of EVERY schedule of write() calls over src_bytes (fourmc_gpu_image_writes_bound)."""
+    return int(lib().fourmc_gpu_image_writes_bound(int(src_bytes)))
+
+
+def compress_images_writes(d_src, items, d_images, magic=MAGIC_4MC, level=1, d_writes=None, src_total=None, images_bytes=None, stream=None):
+    """Write many .4mc / .4mz images with one call, each cut into blocks as Hadoop's FourMcOutputStream cuts it for its job's write()
+    sizes (fourmc_gpu_images_compress_writes).  `items` is a sequence of (src_off, src_bytes, image_off, image_cap, writes_off,
+    n_writes, write_bytes), as compress_bstreams takes them; `level` is compress_images' level.  d_images None: the size query
+    (image_bytes = the exact worst case of each schedule).  Returns one dict per item: image_bytes, blocks, stored_blocks, reason (a
+    FOURMC_BSW_* number) and "name" (its entry of BSTREAM_WRITE_REASONS)."""
+    q = [tuple(int(v) for v in it) for it in items]
+    src = 0 if d_src is None or d_src.numel() == 0 else _dev_ptr(d_src, "compress_images_writes d_src")
+    total = (0 if d_src is None else d_src.numel()) if src_total is None else int(src_total)
+    if d_src is not None and total > d_src.numel():
+        raise EngineError(f"compress_images_writes: src_total {total} lies beyond the tensor's {d_src.numel()} bytes")
+    tab, ntab = 0, 0
+    if d_writes is not None and d_writes.numel():
+        tab, ntab = _writes_ptr(d_writes), d_writes.numel()
+    img, cap = 0, 0
+    if d_images is not None:
+        img = _dev_ptr(d_images, "compress_images_writes d_images")
+        cap = _image_len(d_images, images_bytes, "compress_images_writes")
+        if img == 0:
+            raise EngineError("compress_images_writes: d_images is empty (None asks for the sizes)")
+    arr = (ImageWrItem * max(len(q), 1))()
+    for i, (so, sb, io, ic, wo, nw, wb) in enumerate(q):
+        a = arr[i]
+        a.src_off, a.src_bytes, a.image_off, a.image_cap, a.writes_off, a.n_writes, a.write_bytes = so, sb, io, ic, wo, nw, wb
+    check(lib().fourmc_gpu_images_compress_writes(src, total, tab, ntab, img, cap, int(magic), int(level), C.cast(arr, C.c_void_p), len(q),
+                                                  _stream_ptr(stream)), "fourmc_gpu_images_compress_writes")
+    return [{"image_bytes": int(arr[i].image_bytes), "blocks": int(arr[i].blocks), "stored_blocks": int(arr[i].stored_blocks),
+             "reason": int(arr[i].reason),
              "name": BSTREAM_WRITE_REASONS[arr[i].reason] if 0 <= arr[i].reason < len(BSTREAM_WRITE_REASONS) else "?"}
             for i in range(len(q))]
 

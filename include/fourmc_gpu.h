@@ -952,6 +952,74 @@ int fourmc_gpu_bstreams_compress(const void* d_src, uint64_t src_total, const ui
                                  fourmc_bstream_enc_item* items /*host*/, uint32_t n, void* stream);
 uint64_t fourmc_gpu_bstream_writes_bound(uint64_t src_bytes, int codec);   /* host only, any schedule */
 
+/* ---- .4mc / .4mz images from a job's write() calls, many per call ---------------------------------------------------------------
+ * fourmc_gpu_images_compress cuts a block at every 4 MiB of input, as the `4mc` command line does.  A Hadoop job that names
+ * FourMcCodec, FourMzCodec or one of their six siblings as its output codec writes through FourMcOutputStream / FourMzOutputStream
+ * (FourMcOutputStream.java:69-223 over Lz4Compressor.java:147-298 / ZstdCompressor, with close()), whose blocks end at write()
+ * boundaries.  This call writes those files: for (data, write sizes, magic, level) the image is what that Java writes, byte for byte.
+ * tests/fourmc_stream_model.py restates the Java buffer by buffer; no JVM wrote a fixture for it.
+ * Block cuts, M = 4194304 (FourMcOutputStream.java:140-182).  Zero-length writes do nothing (:153).  At a write of w bytes with
+ *   acc > 0 bytes accumulated and acc + w > M the accumulated bytes become a block and acc = 0 (:157-161).  A write of w > M then
+ *   becomes ceil(w / M) blocks of its own, all of M bytes but the last, and the next write starts fresh (:163-173): the short rest is
+ *   not joined with what follows.  A write of w <= M accumulates (:176); when acc reaches M exactly the block is written at once
+ *   (:177-181).  close() writes what is accumulated (:105).  These are the chunks of the block streams above with M = 4 MiB in place
+ *   of the codec's max input, and the same device planner finds them.
+ * Block payload (FourMcOutputStream.java:195-223).  The compressor call is the JNI one with unlimited output: LZ4_compress,
+ *   LZ4_compressMC, LZ4_compressHC2(level) into a buffer of LZ4_compressBound (jniCompressor.c:91, :123, :156), ZSTD_compress with a
+ *   capacity of 1 GiB (jniZstdCompressor.c:93, :126, :160).  With u the block's length and c the call's result, the block is stored
+ *   when u <= c (:204): BE32(u) BE32(u) BE32(xxh32(raw)) and the raw bytes; otherwise BE32(u) BE32(c) BE32(xxh32(payload)) and the
+ *   payload.  The stream's 4 MiB byte buffer (compress(buffer, 0, buffer.length), :196) caps nothing that matters: bytesWritten is
+ *   min(c, 4 MiB) (Lz4Compressor.java:248-249), and a result above 4 MiB gives u <= 4 MiB <= bytesWritten, the stored case.
+ *   This is NOT the CLI's rule, which compresses into u - 1 bytes and stores when that fails.  For the LZ4 codecs the two give the
+ *   same bytes; for zstd a tight capacity can change the encoder's decisions near the end of an almost incompressible block, so the
+ *   device runs the raw codec call with capacity = the codec's bound, as fourmc_gpu_bstreams_compress does, and then applies u <= c.
+ * Framing.  magic, 1, xxh32 of those 8 bytes (:69-80); the blocks; twelve zero bytes (:108-110); the footer size, 1, deltas, size,
+ *   magic, xxh32 with size = 20 + 4 * blocks, deltas[0] = 12 and deltas[i] = offset of block i less offset of block i - 1
+ *   (:113-129): the layout fourmc_gpu_image_compress writes.  A stream without a non-empty write is the 44-byte image.
+ * Levels.  `level` is the CLI level of fourmc_gpu_images_compress; the eight codec classes map to it as
+ *   FourMcCodec 1 (LZ4_compress), FourMcMediumCodec 2 (LZ4_compressMC), FourMcHighCodec 3 (LZ4_compressHC2 4, Lz4HighCompressor.java:47),
+ *   FourMcUltraCodec 4 (LZ4_compressHC2 8, Lz4UltraCompressor.java:47), FourMzCodec 1 (ZSTD_compress 1, jniZstdCompressor.c:94),
+ *   FourMzMediumCodec 2 (ZSTD_compress 3, :127), FourMzHighCodec 3 (ZSTD_compress 6, ZstdHighCompressor.java:46),
+ *   FourMzUltraCodec 4 (ZSTD_compress 12, ZstdUltraCompressor.java:46).
+ * Schedules: as fourmc_bstream_enc_item has them (a table of uint32 sizes in device memory, or the uniform schedule).
+ * Verdicts, per item, FOURMC_BSW_*; an item that gets one writes nothing into its region and costs only itself: _SUM, _WRITE (it
+ *   wins over _SUM; image_bytes, blocks and stored_blocks are then 0) and _CAP: image_cap below the exact worst case of the schedule,
+ *   12 + sum over the blocks of (12 + len) + 12 + 20 + 4 * blocks = 44 + 16 * blocks + src_bytes (the stored fallback means no block
+ *   exceeds its input); image_bytes and blocks then hold that worst case and the plan's count.
+ * The size query.  d_images NULL plans only: blocks, and image_bytes = that worst case.  One synchronization.
+ * fourmc_gpu_image_writes_bound(S) = 12 + 16 * C(S) + S + 32 holds for every schedule over S bytes, with
+ *   C(S) = 3 * (S / (M + 2)) + min(S mod (M + 2), 2) the most blocks any schedule has (a 1-byte write in front of a write of M + 1:
+ *   the argument of fourmc_gpu_bstream_writes_bound).
+ * Arguments, checked on the host before a device is looked for, the magic first, `items` untouched: FOURMC_EINVAL for a magic that
+ *   is neither 4mc nor 4mz, items NULL with n > 0, d_src NULL with a nonzero src_bytes, d_writes NULL with a nonzero n_writes, a
+ *   source outside [0, src_total), a table range outside [0, writes_total), and - unless this is the query - a region outside
+ *   [0, images_bytes) or two regions of nonzero image_cap that overlap.  n == 0: FOURMC_OK.  More than 0x7FFFFFFF blocks in all (known
+ *   after the plan): FOURMC_EUNSUP.  No device: FOURMC_ENODEV.  A codec result outside [1, bound]: FOURMC_EINVAL after the call's work.
+ * Work.  The plan of fourmc_gpu_bstreams_compress with M = 4 MiB (its kernels, launched as they are), one read-back.  Then rounds of
+ *   at most FOURMC_BSW_ROUND blocks (default 512, read at every call) in file order over all streams: the block streams' descriptor
+ *   kernel (staging slot = the codec's bound rounded up to 256), the raw codec launch, a seal-and-scan kernel (stored or compressed
+ *   per block, a descriptor that points a stored block at its source bytes and a compressed one at its staging slot, and a segmented
+ *   scan with a 64-bit carry per stream that places every block and records its offset for the footer), the XXH32 launch over those
+ *   descriptors and the pack launch of the whole-image encode over them.  After the last round one workgroup per image writes the
+ *   header, the end mark and the footer.  A round may end inside a stream and inside a long write.
+ * Synchronizations of `stream`: two (the plan's read-back, the results); the query takes one.
+ * Writes.  Nothing outside [image_off, image_off + image_bytes) of the items that are FOURMC_BSW_OK.
+ * Not reproduced: a file written by a JVM as a fixture; .4mc and .4mz in one call; a streaming writer with Hadoop's cuts
+ *   (fourmc_gpu_image_writer_* cuts at every 4 MiB). */
+typedef struct fourmc_image_wr_item {   /* 80 bytes */
+    uint64_t src_off, src_bytes;      /* in : d_src[src_off, +src_bytes), the stream's data                          */
+    uint64_t image_off, image_cap;    /* in : the image goes to d_images[image_off, +image_cap)                      */
+    uint64_t writes_off, n_writes;    /* in : entries [writes_off, +n_writes) of d_writes; n_writes == 0: uniform    */
+    uint32_t write_bytes;             /* in : uniform schedule: every write() this long, the last short; 0 = one write() */
+    int32_t  reason;                  /* out: FOURMC_BSW_OK / _SUM / _WRITE / _CAP                                   */
+    uint64_t image_bytes;             /* out: the image's length (query, _CAP: the exact worst case)                 */
+    uint64_t blocks, stored_blocks;   /* out: its blocks, and those written raw                                      */
+} fourmc_image_wr_item;
+int fourmc_gpu_images_compress_writes(const void* d_src, uint64_t src_total, const uint32_t* d_writes, uint64_t writes_total,
+                                      void* d_images, uint64_t images_bytes, uint32_t magic, int level,
+                                      fourmc_image_wr_item* items /*host*/, uint32_t n, void* stream);
+uint64_t fourmc_gpu_image_writes_bound(uint64_t src_bytes);   /* host only, holds for every schedule */
+
 /* ---- host-buffer conveniences with the reference's per-block signatures ------------------- */
 /* These stage one block through HBM (H2D, one launch, D2H).  They exist so the JNI entry points
  * keep their exact one-call-one-block contract (SURVEY.md §8(b) "Batching constraint").        */
