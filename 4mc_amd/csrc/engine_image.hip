@@ -268,16 +268,10 @@ int fourmc_gpu_images_compress(const void* d_src, uint64_t src_total, void* d_im
         for (uint32_t i = 0; i < n; i++) {
             const fourmc_image_enc_item& it = items[i];
             if (it.src_bytes && !d_src) { snprintf(g_err, sizeof g_err, "images_compress: null source"); return FOURMC_EINVAL; }
-            if (span_outside(it.src_off, it.src_bytes, src_total)) {
-                snprintf(g_err, sizeof g_err, "images_compress: the source of image %u lies beyond the %llu bytes of sources", i, (unsigned long long)src_total);
-                return FOURMC_EINVAL;
-            }
+            if (span_outside(it.src_off, it.src_bytes, src_total)) return source_beyond("images_compress", "image", i, src_total);
             const uint64_t k = it.src_bytes / FOURMC_BLOCKSIZE + (it.src_bytes % FOURMC_BLOCKSIZE ? 1 : 0);
             if (k > 0x3FFFFFFFull) { snprintf(g_err, sizeof g_err, "images_compress: image %u has %llu blocks", i, (unsigned long long)k); return FOURMC_EINVAL; }
-            if (span_outside(it.image_off, it.image_cap, images_bytes)) {
-                snprintf(g_err, sizeof g_err, "images_compress: the region of image %u lies beyond the %llu bytes of images", i, (unsigned long long)images_bytes);
-                return FOURMC_EINVAL;
-            }
+            if (span_outside(it.image_off, it.image_cap, images_bytes)) return region_beyond("images_compress", "image", i, images_bytes);
             if (it.image_cap < fourmc_gpu_image_bound(it.src_bytes)) {
                 snprintf(g_err, sizeof g_err, "images_compress: image %u: capacity %llu below the bound %llu", i, (unsigned long long)it.image_cap,
                          (unsigned long long)fourmc_gpu_image_bound(it.src_bytes));

@@ -91,6 +91,29 @@ int decode_items_args(const char* who, const char* one, const char* many, const 
     return regions_overlap(who, "output regions", d);
 }
 
+// The encode side (images_compress, bstreams_compress, images_compress_writes, zsts_compress) keeps its loops - each checks other
+// things between these - and shares the words: FOURMC_EINVAL with the message of a source, a write table slice or an image region
+// that span_outside() found outside its buffer.  `one`: "image" / "stream".
+inline int source_beyond(const char* who, const char* one, uint32_t i, uint64_t src_total)
+{
+    snprintf(g_err, sizeof g_err, "%s: the source of %s %u lies beyond the %llu bytes of sources", who, one, i, (unsigned long long)src_total);
+    return FOURMC_EINVAL;
+}
+inline int writes_beyond(const char* who, uint32_t i, uint64_t writes_total)
+{
+    snprintf(g_err, sizeof g_err, "%s: the write sizes of stream %u lie beyond the %llu entries of the table", who, i, (unsigned long long)writes_total);
+    return FOURMC_EINVAL;
+}
+inline int region_beyond(const char* who, const char* one, uint32_t i, uint64_t images_bytes)
+{
+    snprintf(g_err, sizeof g_err, "%s: the region of %s %u lies beyond the %llu bytes of images", who, one, i, (unsigned long long)images_bytes);
+    return FOURMC_EINVAL;
+}
+
+// ---- engine_streams.hip
+// the raw codec launch of m described blocks, by FOURMC_CODEC_* selector (`level`: the codec's own; the two LZ4 codecs without one ignore it)
+int encode_raw_blocks(int codec, int level, const void* d_src, void* d_stage, fourmc_block* d_blk, uint32_t m, hipStream_t s);
+
 // ---- engine_image.hip, for engine_lines.hip and engine_streams.hip
 constexpr size_t kImagesStageSlack = 4096;  // bytes behind the staging of the many-image and block-stream encodes
 constexpr size_t kIdxBytes = 256;           // fourmc_image_index_dev

@@ -1,4 +1,4 @@
-// 4mc_amd/csrc/engine_streams.hip — Hadoop block streams (bstream.hip) and .zst streams read (zst.hip) and written (zstd_encode.hip).
+// 4mc_amd/csrc/engine_streams.hip — Hadoop block streams (bstream.hip), the .4mc / .4mz images that share their write plan, and .zst streams read (zst.hip) and written (zstd_encode.hip).
 #include "engine_int.h"
 
 namespace {
@@ -68,6 +68,16 @@ int zstw_run(const void* d_src, void* d_images, fourmc_zstw_item* items, uint32_
     return FOURMC_OK;
 }
 } // namespace
+
+int encode_raw_blocks(int codec, int level, const void* d_src, void* d_stage, fourmc_block* d_blk, uint32_t m, hipStream_t s)
+{
+    switch (codec) {
+        case FOURMC_CODEC_LZ4_FAST: return fourmc_gpu_lz4_compress_fast(d_src, d_stage, d_blk, m, s);
+        case FOURMC_CODEC_LZ4_MC:   return fourmc_gpu_lz4_compress_mc(d_src, d_stage, d_blk, m, s);
+        case FOURMC_CODEC_LZ4_HC:   return fourmc_gpu_lz4_compress_hc(d_src, d_stage, d_blk, m, level, s);
+        default:                    return fourmc_gpu_zstd_compress(d_src, d_stage, d_blk, m, level, s);
+    }
+}
 
 extern "C" {
 
@@ -147,14 +157,7 @@ int fourmc_gpu_bstream_compress(const void* d_src, uint64_t src_bytes, void* d_i
         const uint32_t m = uint32_t(ng - g0 < piece ? ng - g0 : piece);
         const uint64_t src0 = g0 * G, left = src_bytes - src0, span = uint64_t(m) * G;
         HIP_TRY(fourmc_launch_bstream_enc_desc(d_blk, src0, left < span ? left : span, G, stride, m, zstd, codec == FOURMC_CODEC_LZ4_MC, s));
-        int r;
-        switch (codec) {
-            case FOURMC_CODEC_LZ4_FAST: r = fourmc_gpu_lz4_compress_fast(d_src, d_stage, d_blk, m, s); break;
-            case FOURMC_CODEC_LZ4_MC:   r = fourmc_gpu_lz4_compress_mc(d_src, d_stage, d_blk, m, s); break;
-            case FOURMC_CODEC_LZ4_HC:   r = fourmc_gpu_lz4_compress_hc(d_src, d_stage, d_blk, m, level, s); break;
-            default:                    r = fourmc_gpu_zstd_compress(d_src, d_stage, d_blk, m, level, s); break;
-        }
-        if (r) return r;
+        if (int r = encode_raw_blocks(codec, level, d_src, d_stage, d_blk, m, s)) return r;
         HIP_TRY(fourmc_launch_bstream_enc_pack(d_image, d_blk, d_off, m, zstd, d_stage, d_sum, s));
     }
     fourmc_bstream_enc_summary h;
@@ -182,17 +185,153 @@ uint64_t fourmc_gpu_bstream_writes_bound(uint64_t src_bytes, int codec)
     return src_bytes + over + 4 * C + 4 * G + 4;
 }
 
+} // extern "C"
+
+// ---- what bstreams_compress and images_compress_writes share: the argument pass, the plan and the rounds' common part --------------
+namespace {
 // Chunks per round: FOURMC_BSW_ROUND, read at every call (a test sets it between two calls)
-static uint32_t bsw_round()
+uint32_t bsw_round()
 {
     const char* e = getenv("FOURMC_BSW_ROUND");
     const long v = e && *e ? atol(e) : long(kBsPiece);
     return uint32_t(v < 1 ? 1 : v > (1 << 20) ? (1 << 20) : v);
 }
 
-// Workspaces.  g_img_ws: the items, the first tile of every stream, the plans and the tile prefixes - what the plan computes and the
-// rounds read.  g_img_stage, sized after the plan's read-back (so that sizing it cannot move the prefixes): the slices, one carry and
-// one length per stream, the summary, the group table, and the descriptors, side entries, offsets and staging of one round.
+// The checks of n > 0 items, in this order per item: null source, null write table, source, write sizes, region (the size query,
+// d_images null, looks at no region); then the regions against each other.  Fills tile0[0 .. n]: the first 64-entry tile of every
+// stream's write sizes.  Item: fourmc_bstream_enc_item or fourmc_image_wr_item, whose first nine fields lie at the same offsets.
+template <class Item>
+int bsw_args(const char* who, const void* d_src, uint64_t src_total, const uint32_t* d_writes, uint64_t writes_total, const void* d_images,
+             uint64_t images_bytes, const Item* items, uint32_t n, std::vector<uint64_t>& tile0)
+{
+    std::vector<std::pair<uint64_t, uint64_t>> d;
+    if (d_images) d.reserve(n);
+    uint64_t tiles = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const Item& it = items[i];
+        if (it.src_bytes && !d_src) { snprintf(g_err, sizeof g_err, "%s: null source", who); return FOURMC_EINVAL; }
+        if (it.n_writes && !d_writes) { snprintf(g_err, sizeof g_err, "%s: null write table", who); return FOURMC_EINVAL; }
+        if (span_outside(it.src_off, it.src_bytes, src_total)) return source_beyond(who, "stream", i, src_total);
+        if (span_outside(it.writes_off, it.n_writes, writes_total)) return writes_beyond(who, i, writes_total);
+        tile0[i] = tiles;
+        tiles += it.n_writes / 64 + (it.n_writes % 64 ? 1 : 0);
+        if (!d_images) continue;                          // the size query looks at no region
+        if (span_outside(it.image_off, it.image_cap, images_bytes)) return region_beyond(who, "stream", i, images_bytes);
+        if (it.image_cap) d.emplace_back(it.image_off, it.image_off + it.image_cap);
+    }
+    tile0[n] = tiles;
+    return regions_overlap(who, "image regions", d);
+}
+
+// One call's state.  The caller sets the first line; bsw_plan() fills the second and third, bsw_round_open() the rest.
+// g_img_ws: the planner's items, the first tile of every stream, the plans and the tile prefixes - what the plan computes and the
+// rounds read.  g_img_stage, sized after the plan's read-back (so that sizing it cannot move the prefixes): the slices, the group
+// table, the descriptors and side entries of one round, the caller's own arrays (d_own) and one round's staging.
+struct BswCall {
+    const void* d_src; const uint32_t* d_writes; uint32_t n, M; int zstd, codec, level; hipStream_t s;
+    std::vector<fourmc_bsw_plan> plans; std::vector<fourmc_bsw_slice> slices; std::vector<uint64_t> worst; fourmc_bsw_slice at = {};
+    WsLease ws{&g_img_ws}; fourmc_bstream_enc_item* d_items; uint64_t* d_tile0; fourmc_bsw_plan* d_plans; uint64_t* d_prefix;
+    WsLease ws2{&g_img_stage}; uint64_t nc; uint32_t piece; fourmc_bsw_slice* d_slices; fourmc_bsw_group* d_grp; fourmc_block* d_blk;
+    fourmc_bsw_side* d_side; char* d_own; char* d_stage;
+};
+
+// The plan of every stream, read back (the call's first synchronization), and each planned stream's share of the chunk numbers, the
+// group table and the staging: c.slices, their totals in c.at.  `up`: the planner's items.  worst(plan, item): the stream's
+// worst-case length, kept in c.worst; when the call writes, a smaller image_cap is the verdict FOURMC_BSW_CAP.  `noun`: what the
+// family calls a chunk.
+template <class Worst>
+int bsw_plan(BswCall& c, const char* who, const char* noun, const fourmc_bstream_enc_item* up, const std::vector<uint64_t>& tile0, bool writes,
+             Worst worst)
+{
+    const uint32_t n = c.n;
+    hipStream_t s = c.s;
+    const uint64_t ntiles = tile0[n];
+    const size_t o_tile0 = align256(size_t(n) * sizeof(fourmc_bstream_enc_item)), o_plans = o_tile0 + align256((size_t(n) + 1) * 8);
+    const size_t o_prefix = o_plans + align256(size_t(n) * sizeof(fourmc_bsw_plan));
+    void* w = nullptr;
+    if (int r = c.ws.get(s, o_prefix + size_t(ntiles) * 8, &w)) return r;
+    char* base = static_cast<char*>(w);
+    c.d_items = reinterpret_cast<fourmc_bstream_enc_item*>(base);
+    c.d_tile0 = reinterpret_cast<uint64_t*>(base + o_tile0);
+    c.d_plans = reinterpret_cast<fourmc_bsw_plan*>(base + o_plans);
+    c.d_prefix = reinterpret_cast<uint64_t*>(base + o_prefix);
+    HIP_TRY(hipMemcpyAsync(c.d_items, up, size_t(n) * sizeof(fourmc_bstream_enc_item), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c.d_tile0, tile0.data(), (size_t(n) + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(fourmc_launch_bsw_sums(c.d_writes, c.d_items, c.d_tile0, n, ntiles, c.d_prefix, c.d_plans, s));
+    HIP_TRY(fourmc_launch_bsw_chase(c.d_writes, c.d_items, c.d_tile0, c.d_prefix, n, c.M, c.zstd, c.d_plans, nullptr, nullptr, s));
+    c.plans = std::vector<fourmc_bsw_plan>(n);
+    HIP_TRY(hipMemcpyAsync(c.plans.data(), c.d_plans, size_t(n) * sizeof(fourmc_bsw_plan), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    c.slices = std::vector<fourmc_bsw_slice>(size_t(n) + 1);
+    c.worst = std::vector<uint64_t>(n);
+    fourmc_bsw_slice& at = c.at;
+    for (uint32_t i = 0; i < n; i++) {
+        fourmc_bsw_plan& pl = c.plans[i];
+        if (pl.reason == FOURMC_BSW_OK && (pl.groups > 0xFFFFFFFFull || pl.chunks > 0x7FFFFFFFull)) {
+            snprintf(g_err, sizeof g_err, "%s: stream %u has %llu %s", who, i, (unsigned long long)pl.chunks, noun);
+            return FOURMC_EUNSUP;
+        }
+        c.worst[i] = worst(pl, up[i]);
+        if (writes && pl.reason == FOURMC_BSW_OK && up[i].image_cap < c.worst[i]) pl.reason = FOURMC_BSW_CAP;
+        c.slices[i] = at;
+        if (pl.reason != FOURMC_BSW_OK) continue;
+        at.chunk0 += pl.chunks; at.stage0 += pl.stage;
+        if (up[i].n_writes) at.group0 += pl.groups;
+        if (at.chunk0 > 0x7FFFFFFFull) { snprintf(g_err, sizeof g_err, "%s: more than 0x7FFFFFFF %s", who, noun); return FOURMC_EUNSUP; }
+    }
+    c.slices[n] = at;
+    return FOURMC_OK;
+}
+
+// The round size and the lease of g_img_stage; own(piece): the bytes of the caller's own arrays, which begin at c.d_own
+template <class Own>
+int bsw_round_open(BswCall& c, Own own)
+{
+    const uint32_t round = bsw_round();
+    c.nc = c.at.chunk0;
+    c.piece = uint32_t(c.nc < round ? c.nc : round);
+    const uint64_t slot_m = align256(bs_block_bound(c.zstd, c.M));
+    const uint64_t stage = c.at.stage0 < uint64_t(c.piece) * slot_m ? c.at.stage0 : uint64_t(c.piece) * slot_m;
+    const size_t o_grp = align256((size_t(c.n) + 1) * sizeof(fourmc_bsw_slice)), o_blk = o_grp + align256(size_t(c.at.group0) * sizeof(fourmc_bsw_group));
+    const size_t o_side = o_blk + align256(size_t(c.piece) * sizeof(fourmc_block)), o_own = o_side + align256(size_t(c.piece) * sizeof(fourmc_bsw_side));
+    const size_t o_stage = o_own + own(c.piece);
+    void* w = nullptr;
+    if (int r = c.ws2.get(c.s, o_stage + size_t(stage) + kImagesStageSlack, &w)) return r;
+    char* base = static_cast<char*>(w);
+    c.d_slices = reinterpret_cast<fourmc_bsw_slice*>(base);
+    c.d_grp = reinterpret_cast<fourmc_bsw_group*>(base + o_grp);
+    c.d_blk = reinterpret_cast<fourmc_block*>(base + o_blk);
+    c.d_side = reinterpret_cast<fourmc_bsw_side*>(base + o_side);
+    c.d_own = base + o_own;
+    c.d_stage = base + o_stage;
+    return FOURMC_OK;
+}
+
+// Before the first round: the plans (with the _CAP verdicts) and the slices go up, the caller's two running arrays are cleared, and
+// the group tables are written
+int bsw_round_start(BswCall& c, void* d_zero0, size_t bytes0, void* d_zero1, size_t bytes1)
+{
+    HIP_TRY(hipMemcpyAsync(c.d_plans, c.plans.data(), size_t(c.n) * sizeof(fourmc_bsw_plan), hipMemcpyHostToDevice, c.s));
+    HIP_TRY(hipMemcpyAsync(c.d_slices, c.slices.data(), (size_t(c.n) + 1) * sizeof(fourmc_bsw_slice), hipMemcpyHostToDevice, c.s));
+    HIP_TRY(hipMemsetAsync(d_zero0, 0, bytes0, c.s));
+    HIP_TRY(hipMemsetAsync(d_zero1, 0, bytes1, c.s));
+    if (c.at.group0) HIP_TRY(fourmc_launch_bsw_chase(c.d_writes, c.d_items, c.d_tile0, c.d_prefix, c.n, c.M, c.zstd, c.d_plans, c.d_slices, c.d_grp, c.s));
+    return FOURMC_OK;
+}
+
+// The round that begins at chunk c0: its *m descriptors and side entries, and the raw codec launch into the staging
+int bsw_round_encode(BswCall& c, uint64_t c0, uint32_t* m)
+{
+    *m = uint32_t(c.nc - c0 < c.piece ? c.nc - c0 : c.piece);
+    HIP_TRY(fourmc_launch_bsw_desc(c.d_items, c.d_plans, c.d_slices, c.d_grp, c.n, c.M, c.zstd, c.codec == FOURMC_CODEC_LZ4_MC, c0, *m, c.d_blk, c.d_side, c.s));
+    return encode_raw_blocks(c.codec, c.level, c.d_src, c.d_stage, c.d_blk, *m, c.s);
+}
+} // namespace
+
+extern "C" {
+
+// The host path above with M = the codec's chunk.  Its own arrays: one carry and one length per stream, the summary, and the
+// offsets of one round.  Worst case: the plan's own.
 int fourmc_gpu_bstreams_compress(const void* d_src, uint64_t src_total, const uint32_t* d_writes, uint64_t writes_total,
                                  void* d_images, uint64_t images_bytes, int codec, int level,
                                  fourmc_bstream_enc_item* items, uint32_t n, void* stream)
@@ -202,74 +341,16 @@ int fourmc_gpu_bstreams_compress(const void* d_src, uint64_t src_total, const ui
     if (n == 0) return FOURMC_OK;
     if (!items) { snprintf(g_err, sizeof g_err, "bstreams_compress: null items"); return FOURMC_EINVAL; }
     std::vector<uint64_t> tile0(size_t(n) + 1);
-    {
-        std::vector<std::pair<uint64_t, uint64_t>> d;
-        if (d_images) d.reserve(n);
-        uint64_t tiles = 0;
-        for (uint32_t i = 0; i < n; i++) {
-            const fourmc_bstream_enc_item& it = items[i];
-            if (it.src_bytes && !d_src) { snprintf(g_err, sizeof g_err, "bstreams_compress: null source"); return FOURMC_EINVAL; }
-            if (it.n_writes && !d_writes) { snprintf(g_err, sizeof g_err, "bstreams_compress: null write table"); return FOURMC_EINVAL; }
-            if (span_outside(it.src_off, it.src_bytes, src_total)) {
-                snprintf(g_err, sizeof g_err, "bstreams_compress: the source of stream %u lies beyond the %llu bytes of sources", i, (unsigned long long)src_total);
-                return FOURMC_EINVAL;
-            }
-            if (span_outside(it.writes_off, it.n_writes, writes_total)) {
-                snprintf(g_err, sizeof g_err, "bstreams_compress: the write sizes of stream %u lie beyond the %llu entries of the table", i, (unsigned long long)writes_total);
-                return FOURMC_EINVAL;
-            }
-            tile0[i] = tiles;
-            tiles += it.n_writes / 64 + (it.n_writes % 64 ? 1 : 0);
-            if (!d_images) continue;                          // the size query looks at no region
-            if (span_outside(it.image_off, it.image_cap, images_bytes)) {
-                snprintf(g_err, sizeof g_err, "bstreams_compress: the region of stream %u lies beyond the %llu bytes of images", i, (unsigned long long)images_bytes);
-                return FOURMC_EINVAL;
-            }
-            if (it.image_cap) d.emplace_back(it.image_off, it.image_off + it.image_cap);
-        }
-        tile0[n] = tiles;
-        if (int r = regions_overlap("bstreams_compress", "image regions", d)) return r;
-    }
+    if (int r = bsw_args("bstreams_compress", d_src, src_total, d_writes, writes_total, d_images, images_bytes, items, n, tile0)) return r;
     if (zstd && !fourmc_zstd_enc_level_ok(level)) { snprintf(g_err, sizeof g_err, "ZSTD level %d not on the device (levels 1..12 are)", level); return FOURMC_EUNSUP; }
     if (int r = ensure_device()) return r;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t M = fourmc_gpu_bstream_max_input(codec);
-    const uint64_t ntiles = tile0[n];
-    const size_t o_tile0 = align256(size_t(n) * sizeof(fourmc_bstream_enc_item)), o_plans = o_tile0 + align256((size_t(n) + 1) * 8);
-    const size_t o_prefix = o_plans + align256(size_t(n) * sizeof(fourmc_bsw_plan));
-    WsLease ws(&g_img_ws); void* w = nullptr;
-    if (int r = ws.get(s, o_prefix + size_t(ntiles) * 8, &w)) return r;
-    char* base = static_cast<char*>(w);
-    auto* d_items = reinterpret_cast<fourmc_bstream_enc_item*>(base);
-    auto* d_tile0 = reinterpret_cast<uint64_t*>(base + o_tile0);
-    auto* d_plans = reinterpret_cast<fourmc_bsw_plan*>(base + o_plans);
-    auto* d_prefix = reinterpret_cast<uint64_t*>(base + o_prefix);
-    HIP_TRY(hipMemcpyAsync(d_items, items, size_t(n) * sizeof(fourmc_bstream_enc_item), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_tile0, tile0.data(), (size_t(n) + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(fourmc_launch_bsw_sums(d_writes, d_items, d_tile0, n, ntiles, d_prefix, d_plans, s));
-    HIP_TRY(fourmc_launch_bsw_chase(d_writes, d_items, d_tile0, d_prefix, n, M, zstd, d_plans, nullptr, nullptr, s));
-    std::vector<fourmc_bsw_plan> plans(n);
-    HIP_TRY(hipMemcpyAsync(plans.data(), d_plans, size_t(n) * sizeof(fourmc_bsw_plan), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    std::vector<fourmc_bsw_slice> slices(size_t(n) + 1);
-    fourmc_bsw_slice at = {};
-    for (uint32_t i = 0; i < n; i++) {                   // each encoded stream's share of the chunk numbers, the group table and the staging
-        fourmc_bsw_plan& pl = plans[i];
-        if (pl.reason == FOURMC_BSW_OK && (pl.groups > 0xFFFFFFFFull || pl.chunks > 0x7FFFFFFFull)) {
-            snprintf(g_err, sizeof g_err, "bstreams_compress: stream %u has %llu chunks", i, (unsigned long long)pl.chunks);
-            return FOURMC_EUNSUP;
-        }
-        if (d_images && pl.reason == FOURMC_BSW_OK && items[i].image_cap < pl.worst) pl.reason = FOURMC_BSW_CAP;
-        slices[i] = at;
-        if (pl.reason != FOURMC_BSW_OK) continue;
-        at.chunk0 += pl.chunks; at.stage0 += pl.stage;
-        if (items[i].n_writes) at.group0 += pl.groups;
-        if (at.chunk0 > 0x7FFFFFFFull) { snprintf(g_err, sizeof g_err, "bstreams_compress: more than 0x7FFFFFFF chunks"); return FOURMC_EUNSUP; }
-    }
-    slices[n] = at;
+    BswCall c{d_src, d_writes, n, fourmc_gpu_bstream_max_input(codec), zstd, codec, level, s};
+    if (int r = bsw_plan(c, "bstreams_compress", "chunks", items, tile0, d_images != nullptr,
+                         [](const fourmc_bsw_plan& pl, const fourmc_bstream_enc_item&) { return pl.worst; })) return r;
     auto report = [&](const std::vector<uint64_t>* bytes) {
         for (uint32_t i = 0; i < n; i++) {
-            const fourmc_bsw_plan& pl = plans[i];
+            const fourmc_bsw_plan& pl = c.plans[i];
             const bool planned = pl.reason == FOURMC_BSW_OK || pl.reason == FOURMC_BSW_CAP;
             items[i].reason = pl.reason;
             items[i].groups = planned ? uint32_t(pl.groups) : 0; items[i].chunks = planned ? uint32_t(pl.chunks) : 0;
@@ -277,46 +358,19 @@ int fourmc_gpu_bstreams_compress(const void* d_src, uint64_t src_total, const ui
         }
     };
     if (!d_images) { report(nullptr); return FOURMC_OK; }
-    const uint32_t round = bsw_round();
-    const uint64_t nc = at.chunk0;
-    const uint32_t piece = uint32_t(nc < round ? nc : round);
-    const uint64_t slot_m = align256(bs_block_bound(zstd, M));
-    const uint64_t stage = at.stage0 < uint64_t(piece) * slot_m ? at.stage0 : uint64_t(piece) * slot_m;
-    const size_t o_carry = align256((size_t(n) + 1) * sizeof(fourmc_bsw_slice)), o_bytes = o_carry + align256(size_t(n) * 8);
-    const size_t o_sum = o_bytes + align256(size_t(n) * 8), o_grp = o_sum + align256(sizeof(fourmc_bstream_enc_summary));
-    const size_t o_blk = o_grp + align256(size_t(at.group0) * sizeof(fourmc_bsw_group)), o_side = o_blk + align256(size_t(piece) * sizeof(fourmc_block));
-    const size_t o_off = o_side + align256(size_t(piece) * sizeof(fourmc_bsw_side)), o_stage = o_off + align256(size_t(piece) * 8);
-    WsLease ws2(&g_img_stage); void* w2 = nullptr;
-    if (int r = ws2.get(s, o_stage + size_t(stage) + kImagesStageSlack, &w2)) return r;
-    char* b2 = static_cast<char*>(w2);
-    auto* d_slices = reinterpret_cast<fourmc_bsw_slice*>(b2);
-    auto* d_carry = reinterpret_cast<uint64_t*>(b2 + o_carry);
-    auto* d_bytes = reinterpret_cast<uint64_t*>(b2 + o_bytes);
-    auto* d_sum = reinterpret_cast<fourmc_bstream_enc_summary*>(b2 + o_sum);
-    auto* d_grp = reinterpret_cast<fourmc_bsw_group*>(b2 + o_grp);
-    auto* d_blk = reinterpret_cast<fourmc_block*>(b2 + o_blk);
-    auto* d_side = reinterpret_cast<fourmc_bsw_side*>(b2 + o_side);
-    auto* d_off = reinterpret_cast<uint64_t*>(b2 + o_off);
-    void* d_stage = b2 + o_stage;
-    HIP_TRY(hipMemcpyAsync(d_plans, plans.data(), size_t(n) * sizeof(fourmc_bsw_plan), hipMemcpyHostToDevice, s));      // with the _CAP verdicts
-    HIP_TRY(hipMemcpyAsync(d_slices, slices.data(), (size_t(n) + 1) * sizeof(fourmc_bsw_slice), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_carry, 0, size_t(n) * 8, s));
-    HIP_TRY(hipMemsetAsync(d_sum, 0, sizeof(fourmc_bstream_enc_summary), s));
-    if (at.group0) HIP_TRY(fourmc_launch_bsw_chase(d_writes, d_items, d_tile0, d_prefix, n, M, zstd, d_plans, d_slices, d_grp, s));
-    for (uint64_t c0 = 0; c0 < nc; c0 += piece) {
-        const uint32_t m = uint32_t(nc - c0 < piece ? nc - c0 : piece);
-        HIP_TRY(fourmc_launch_bsw_desc(d_items, d_plans, d_slices, d_grp, n, M, zstd, codec == FOURMC_CODEC_LZ4_MC, c0, m, d_blk, d_side, s));
-        int r;
-        switch (codec) {
-            case FOURMC_CODEC_LZ4_FAST: r = fourmc_gpu_lz4_compress_fast(d_src, d_stage, d_blk, m, s); break;
-            case FOURMC_CODEC_LZ4_MC:   r = fourmc_gpu_lz4_compress_mc(d_src, d_stage, d_blk, m, s); break;
-            case FOURMC_CODEC_LZ4_HC:   r = fourmc_gpu_lz4_compress_hc(d_src, d_stage, d_blk, m, level, s); break;
-            default:                    r = fourmc_gpu_zstd_compress(d_src, d_stage, d_blk, m, level, s); break;
-        }
-        if (r) return r;
-        HIP_TRY(fourmc_launch_bsw_pack(d_images, d_items, d_blk, d_side, d_off, m, zstd, d_stage, d_carry, d_sum, s));
+    const size_t o_bytes = align256(size_t(n) * 8), o_sum = o_bytes + align256(size_t(n) * 8), o_off = o_sum + align256(sizeof(fourmc_bstream_enc_summary));
+    if (int r = bsw_round_open(c, [&](uint32_t piece) { return o_off + align256(size_t(piece) * 8); })) return r;
+    auto* d_carry = reinterpret_cast<uint64_t*>(c.d_own);
+    auto* d_bytes = reinterpret_cast<uint64_t*>(c.d_own + o_bytes);
+    auto* d_sum = reinterpret_cast<fourmc_bstream_enc_summary*>(c.d_own + o_sum);
+    auto* d_off = reinterpret_cast<uint64_t*>(c.d_own + o_off);
+    if (int r = bsw_round_start(c, d_carry, size_t(n) * 8, d_sum, sizeof(fourmc_bstream_enc_summary))) return r;
+    for (uint64_t c0 = 0; c0 < c.nc; c0 += c.piece) {
+        uint32_t m;
+        if (int r = bsw_round_encode(c, c0, &m)) return r;
+        HIP_TRY(fourmc_launch_bsw_pack(d_images, c.d_items, c.d_blk, c.d_side, d_off, m, zstd, c.d_stage, d_carry, d_sum, s));
     }
-    HIP_TRY(fourmc_launch_bsw_result(d_items, d_plans, d_carry, n, d_images, d_bytes, s));
+    HIP_TRY(fourmc_launch_bsw_result(c.d_items, c.d_plans, d_carry, n, d_images, d_bytes, s));
     std::vector<uint64_t> bytes(n);
     fourmc_bstream_enc_summary h;
     HIP_TRY(hipMemcpyAsync(bytes.data(), d_bytes, size_t(n) * 8, hipMemcpyDeviceToHost, s));
@@ -335,10 +389,9 @@ uint64_t fourmc_gpu_image_writes_bound(uint64_t src_bytes)
     return 12 + 16 * bsw_max_chunks(src_bytes, FOURMC_BLOCKSIZE) + src_bytes + 32;
 }
 
-// Workspaces as in bstreams_compress.  g_img_ws: the items (as the planner's own item type), the first tile of every stream, the plans
-// and the tile prefixes.  g_img_stage, sized after the plan's read-back: the slices, one running pair and one result per stream, the
-// bad count, the group table, the offset of every block of the call (the footers' index), and the descriptors, side entries, seal
-// descriptors and staging of one round.
+// The same host path with M = 4 MiB; the planner's items are the caller's in the planner's own item type.  Its own arrays: one
+// running pair and one result per stream, the bad count, the offset of every block of the call (the footers' index) and the seal
+// descriptors of one round.  Worst case: header, 12 + len per block, end mark, footer.
 int fourmc_gpu_images_compress_writes(const void* d_src, uint64_t src_total, const uint32_t* d_writes, uint64_t writes_total,
                                       void* d_images, uint64_t images_bytes, uint32_t magic, int level,
                                       fourmc_image_wr_item* items, uint32_t n, void* stream)
@@ -347,139 +400,55 @@ int fourmc_gpu_images_compress_writes(const void* d_src, uint64_t src_total, con
     if (n == 0) return FOURMC_OK;
     if (!items) { snprintf(g_err, sizeof g_err, "images_compress_writes: null items"); return FOURMC_EINVAL; }
     std::vector<uint64_t> tile0(size_t(n) + 1);
+    if (int r = bsw_args("images_compress_writes", d_src, src_total, d_writes, writes_total, d_images, images_bytes, items, n, tile0)) return r;
     std::vector<fourmc_bstream_enc_item> bi(n);
-    {
-        std::vector<std::pair<uint64_t, uint64_t>> d;
-        if (d_images) d.reserve(n);
-        uint64_t tiles = 0;
-        for (uint32_t i = 0; i < n; i++) {
-            const fourmc_image_wr_item& it = items[i];
-            if (it.src_bytes && !d_src) { snprintf(g_err, sizeof g_err, "images_compress_writes: null source"); return FOURMC_EINVAL; }
-            if (it.n_writes && !d_writes) { snprintf(g_err, sizeof g_err, "images_compress_writes: null write table"); return FOURMC_EINVAL; }
-            if (span_outside(it.src_off, it.src_bytes, src_total)) {
-                snprintf(g_err, sizeof g_err, "images_compress_writes: the source of stream %u lies beyond the %llu bytes of sources", i, (unsigned long long)src_total);
-                return FOURMC_EINVAL;
-            }
-            if (span_outside(it.writes_off, it.n_writes, writes_total)) {
-                snprintf(g_err, sizeof g_err, "images_compress_writes: the write sizes of stream %u lie beyond the %llu entries of the table", i, (unsigned long long)writes_total);
-                return FOURMC_EINVAL;
-            }
-            fourmc_bstream_enc_item& b = bi[i];
-            b = {};
-            b.src_off = it.src_off; b.src_bytes = it.src_bytes; b.image_off = it.image_off; b.image_cap = it.image_cap;
-            b.writes_off = it.writes_off; b.n_writes = it.n_writes; b.write_bytes = it.write_bytes;
-            tile0[i] = tiles;
-            tiles += it.n_writes / 64 + (it.n_writes % 64 ? 1 : 0);
-            if (!d_images) continue;                          // the size query looks at no region
-            if (span_outside(it.image_off, it.image_cap, images_bytes)) {
-                snprintf(g_err, sizeof g_err, "images_compress_writes: the region of stream %u lies beyond the %llu bytes of images", i, (unsigned long long)images_bytes);
-                return FOURMC_EINVAL;
-            }
-            if (it.image_cap) d.emplace_back(it.image_off, it.image_off + it.image_cap);
-        }
-        tile0[n] = tiles;
-        if (int r = regions_overlap("images_compress_writes", "image regions", d)) return r;
+    for (uint32_t i = 0; i < n; i++) {
+        const fourmc_image_wr_item& it = items[i];
+        fourmc_bstream_enc_item& b = bi[i];
+        b = {};
+        b.src_off = it.src_off; b.src_bytes = it.src_bytes; b.image_off = it.image_off; b.image_cap = it.image_cap;
+        b.writes_off = it.writes_off; b.n_writes = it.n_writes; b.write_bytes = it.write_bytes;
     }
     int codec_level = 0;
     const int codec = fourmc_level_codec(magic, level, &codec_level);
     const int zstd = codec == FOURMC_CODEC_ZSTD;
     if (int r = ensure_device()) return r;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t M = FOURMC_BLOCKSIZE;
-    const uint64_t ntiles = tile0[n];
-    const size_t o_tile0 = align256(size_t(n) * sizeof(fourmc_bstream_enc_item)), o_plans = o_tile0 + align256((size_t(n) + 1) * 8);
-    const size_t o_prefix = o_plans + align256(size_t(n) * sizeof(fourmc_bsw_plan));
-    WsLease ws(&g_img_ws); void* w = nullptr;
-    if (int r = ws.get(s, o_prefix + size_t(ntiles) * 8, &w)) return r;
-    char* base = static_cast<char*>(w);
-    auto* d_items = reinterpret_cast<fourmc_bstream_enc_item*>(base);
-    auto* d_tile0 = reinterpret_cast<uint64_t*>(base + o_tile0);
-    auto* d_plans = reinterpret_cast<fourmc_bsw_plan*>(base + o_plans);
-    auto* d_prefix = reinterpret_cast<uint64_t*>(base + o_prefix);
-    HIP_TRY(hipMemcpyAsync(d_items, bi.data(), size_t(n) * sizeof(fourmc_bstream_enc_item), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_tile0, tile0.data(), (size_t(n) + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(fourmc_launch_bsw_sums(d_writes, d_items, d_tile0, n, ntiles, d_prefix, d_plans, s));
-    HIP_TRY(fourmc_launch_bsw_chase(d_writes, d_items, d_tile0, d_prefix, n, M, zstd, d_plans, nullptr, nullptr, s));
-    std::vector<fourmc_bsw_plan> plans(n);
-    HIP_TRY(hipMemcpyAsync(plans.data(), d_plans, size_t(n) * sizeof(fourmc_bsw_plan), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    std::vector<fourmc_bsw_slice> slices(size_t(n) + 1);
-    std::vector<uint64_t> worst(n);
-    fourmc_bsw_slice at = {};
-    for (uint32_t i = 0; i < n; i++) {                   // each written stream's share of the block numbers, the group table and the staging
-        fourmc_bsw_plan& pl = plans[i];
-        if (pl.reason == FOURMC_BSW_OK && (pl.groups > 0xFFFFFFFFull || pl.chunks > 0x7FFFFFFFull)) {
-            snprintf(g_err, sizeof g_err, "images_compress_writes: stream %u has %llu blocks", i, (unsigned long long)pl.chunks);
-            return FOURMC_EUNSUP;
-        }
-        worst[i] = 44 + 16 * pl.chunks + items[i].src_bytes;    // header, 12 + len per block, end mark, footer
-        if (d_images && pl.reason == FOURMC_BSW_OK && items[i].image_cap < worst[i]) pl.reason = FOURMC_BSW_CAP;
-        slices[i] = at;
-        if (pl.reason != FOURMC_BSW_OK) continue;
-        at.chunk0 += pl.chunks; at.stage0 += pl.stage;
-        if (items[i].n_writes) at.group0 += pl.groups;
-        if (at.chunk0 > 0x7FFFFFFFull) { snprintf(g_err, sizeof g_err, "images_compress_writes: more than 0x7FFFFFFF blocks"); return FOURMC_EUNSUP; }
-    }
-    slices[n] = at;
+    BswCall c{d_src, d_writes, n, FOURMC_BLOCKSIZE, zstd, codec, codec_level, s};
+    if (int r = bsw_plan(c, "images_compress_writes", "blocks", bi.data(), tile0, d_images != nullptr,
+                         [](const fourmc_bsw_plan& pl, const fourmc_bstream_enc_item& it) { return 44 + 16 * pl.chunks + it.src_bytes; })) return r;
     auto report = [&](const std::vector<fourmc_imgw_result>* res) {
         for (uint32_t i = 0; i < n; i++) {
-            const fourmc_bsw_plan& pl = plans[i];
+            const fourmc_bsw_plan& pl = c.plans[i];
             const bool planned = pl.reason == FOURMC_BSW_OK || pl.reason == FOURMC_BSW_CAP, written = res && pl.reason == FOURMC_BSW_OK;
             items[i].reason = pl.reason;
             items[i].blocks = planned ? pl.chunks : 0;
             items[i].stored_blocks = written ? (*res)[i].stored : 0;
-            items[i].image_bytes = !planned ? 0 : written ? (*res)[i].image_bytes : worst[i];
+            items[i].image_bytes = !planned ? 0 : written ? (*res)[i].image_bytes : c.worst[i];
         }
     };
     if (!d_images) { report(nullptr); return FOURMC_OK; }
-    const uint32_t round = bsw_round();
-    const uint64_t nc = at.chunk0;
-    const uint32_t piece = uint32_t(nc < round ? nc : round);
-    const uint64_t slot_m = align256(bs_block_bound(zstd, M));
-    const uint64_t stage = at.stage0 < uint64_t(piece) * slot_m ? at.stage0 : uint64_t(piece) * slot_m;
-    const size_t o_run = align256((size_t(n) + 1) * sizeof(fourmc_bsw_slice)), o_res = o_run + align256(size_t(n) * sizeof(fourmc_imgw_run));
-    const size_t o_bad = o_res + align256(size_t(n) * sizeof(fourmc_imgw_result)), o_grp = o_bad + 256;
-    const size_t o_idx = o_grp + align256(size_t(at.group0) * sizeof(fourmc_bsw_group)), o_blk = o_idx + align256(size_t(nc) * 8);
-    const size_t o_side = o_blk + align256(size_t(piece) * sizeof(fourmc_block)), o_seal = o_side + align256(size_t(piece) * sizeof(fourmc_bsw_side));
-    const size_t o_stage = o_seal + align256(size_t(piece) * sizeof(fourmc_block));
-    WsLease ws2(&g_img_stage); void* w2 = nullptr;
-    if (int r = ws2.get(s, o_stage + size_t(stage) + kImagesStageSlack, &w2)) return r;
-    char* b2 = static_cast<char*>(w2);
-    auto* d_slices = reinterpret_cast<fourmc_bsw_slice*>(b2);
-    auto* d_run = reinterpret_cast<fourmc_imgw_run*>(b2 + o_run);
-    auto* d_res = reinterpret_cast<fourmc_imgw_result*>(b2 + o_res);
-    auto* d_bad = reinterpret_cast<uint64_t*>(b2 + o_bad);
-    auto* d_grp = reinterpret_cast<fourmc_bsw_group*>(b2 + o_grp);
-    auto* d_idx = reinterpret_cast<uint64_t*>(b2 + o_idx);
-    auto* d_blk = reinterpret_cast<fourmc_block*>(b2 + o_blk);
-    auto* d_side = reinterpret_cast<fourmc_bsw_side*>(b2 + o_side);
-    auto* d_seal = reinterpret_cast<fourmc_block*>(b2 + o_seal);
-    char* d_stage = b2 + o_stage;
-    HIP_TRY(hipMemcpyAsync(d_plans, plans.data(), size_t(n) * sizeof(fourmc_bsw_plan), hipMemcpyHostToDevice, s));      // with the _CAP verdicts
-    HIP_TRY(hipMemcpyAsync(d_slices, slices.data(), (size_t(n) + 1) * sizeof(fourmc_bsw_slice), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_run, 0, size_t(n) * sizeof(fourmc_imgw_run), s));
-    HIP_TRY(hipMemsetAsync(d_bad, 0, 8, s));
-    if (at.group0) HIP_TRY(fourmc_launch_bsw_chase(d_writes, d_items, d_tile0, d_prefix, n, M, zstd, d_plans, d_slices, d_grp, s));
+    const size_t o_res = align256(size_t(n) * sizeof(fourmc_imgw_run)), o_bad = o_res + align256(size_t(n) * sizeof(fourmc_imgw_result));
+    const size_t o_idx = o_bad + 256, o_seal = o_idx + align256(size_t(c.at.chunk0) * 8);
+    if (int r = bsw_round_open(c, [&](uint32_t piece) { return o_seal + align256(size_t(piece) * sizeof(fourmc_block)); })) return r;
+    auto* d_run = reinterpret_cast<fourmc_imgw_run*>(c.d_own);
+    auto* d_res = reinterpret_cast<fourmc_imgw_result*>(c.d_own + o_res);
+    auto* d_bad = reinterpret_cast<uint64_t*>(c.d_own + o_bad);
+    auto* d_idx = reinterpret_cast<uint64_t*>(c.d_own + o_idx);
+    auto* d_seal = reinterpret_cast<fourmc_block*>(c.d_own + o_seal);
+    if (int r = bsw_round_start(c, d_run, size_t(n) * sizeof(fourmc_imgw_run), d_bad, 8)) return r;
     // the XXH32 and the pack read a stored block's bytes from d_src and a compressed one's from the staging through one base address:
     // the lower of the two, as the streaming writer's batches do
-    const uintptr_t p_src = reinterpret_cast<uintptr_t>(d_src), p_stage = reinterpret_cast<uintptr_t>(d_stage);
-    const uintptr_t lo = nc && p_src < p_stage ? p_src : p_stage;
-    for (uint64_t c0 = 0; c0 < nc; c0 += piece) {
-        const uint32_t m = uint32_t(nc - c0 < piece ? nc - c0 : piece);
-        HIP_TRY(fourmc_launch_bsw_desc(d_items, d_plans, d_slices, d_grp, n, M, zstd, codec == FOURMC_CODEC_LZ4_MC, c0, m, d_blk, d_side, s));
-        int r;
-        switch (codec) {
-            case FOURMC_CODEC_LZ4_FAST: r = fourmc_gpu_lz4_compress_fast(d_src, d_stage, d_blk, m, s); break;
-            case FOURMC_CODEC_LZ4_MC:   r = fourmc_gpu_lz4_compress_mc(d_src, d_stage, d_blk, m, s); break;
-            case FOURMC_CODEC_LZ4_HC:   r = fourmc_gpu_lz4_compress_hc(d_src, d_stage, d_blk, m, codec_level, s); break;
-            default:                    r = fourmc_gpu_zstd_compress(d_src, d_stage, d_blk, m, codec_level, s); break;
-        }
-        if (r) return r;
-        HIP_TRY(fourmc_launch_imgw_seal(d_blk, d_side, m, zstd, d_items, p_src - lo, p_stage - lo, d_seal, d_idx + c0, d_run, d_bad, s));
+    const uintptr_t p_src = reinterpret_cast<uintptr_t>(d_src), p_stage = reinterpret_cast<uintptr_t>(c.d_stage);
+    const uintptr_t lo = c.nc && p_src < p_stage ? p_src : p_stage;
+    for (uint64_t c0 = 0; c0 < c.nc; c0 += c.piece) {
+        uint32_t m;
+        if (int r = bsw_round_encode(c, c0, &m)) return r;
+        HIP_TRY(fourmc_launch_imgw_seal(c.d_blk, c.d_side, m, zstd, c.d_items, p_src - lo, p_stage - lo, d_seal, d_idx + c0, d_run, d_bad, s));
         HIP_TRY(fourmc_launch_xxh32(reinterpret_cast<const void*>(lo), d_seal, m, 0, FOURMC_HASH_DST_RESULT, s));
         HIP_TRY(fourmc_launch_pack_image(reinterpret_cast<const void*>(lo), d_images, d_seal, d_idx + c0, m, s));
     }
-    HIP_TRY(fourmc_launch_imgw_tail(d_images, d_items, d_plans, d_slices, d_idx, d_run, n, magic, d_res, s));
+    HIP_TRY(fourmc_launch_imgw_tail(d_images, c.d_items, c.d_plans, c.d_slices, d_idx, d_run, n, magic, d_res, s));
     std::vector<fourmc_imgw_result> res(n);
     uint64_t bad = 0;
     HIP_TRY(hipMemcpyAsync(res.data(), d_res, size_t(n) * sizeof(fourmc_imgw_result), hipMemcpyDeviceToHost, s));
@@ -648,14 +617,8 @@ int fourmc_gpu_zsts_compress(const void* d_src, uint64_t src_total, void* d_imag
             const bool read = it.src_bytes <= kZstwMaxSource;            // (a source beyond the limit is refused unread: only its descriptor exists)
             if (read && it.src_bytes && !d_src) { snprintf(g_err, sizeof g_err, "zsts_compress: null source"); return FOURMC_EINVAL; }
             if (it.image_cap && !d_images) { snprintf(g_err, sizeof g_err, "zsts_compress: null images"); return FOURMC_EINVAL; }
-            if (read && span_outside(it.src_off, it.src_bytes, src_total)) {
-                snprintf(g_err, sizeof g_err, "zsts_compress: the source of stream %u lies beyond the %llu bytes of sources", i, (unsigned long long)src_total);
-                return FOURMC_EINVAL;
-            }
-            if (span_outside(it.image_off, it.image_cap, images_bytes)) {
-                snprintf(g_err, sizeof g_err, "zsts_compress: the region of stream %u lies beyond the %llu bytes of images", i, (unsigned long long)images_bytes);
-                return FOURMC_EINVAL;
-            }
+            if (read && span_outside(it.src_off, it.src_bytes, src_total)) return source_beyond("zsts_compress", "stream", i, src_total);
+            if (span_outside(it.image_off, it.image_cap, images_bytes)) return region_beyond("zsts_compress", "stream", i, images_bytes);
             if (it.image_cap) d.emplace_back(it.image_off, it.image_off + it.image_cap);
         }
         if (int r = regions_overlap("zsts_compress", "image regions", d)) return r;

@@ -225,6 +225,33 @@ def bstream_writes_bound(src_bytes, codec=CODEC_LZ4_FAST):
     return int(lib().fourmc_gpu_bstream_writes_bound(int(src_bytes), int(codec)))
 
 
+def _compress_writes(who, item_cls, fn, mid, row, d_src, items, d_images, d_writes, src_total, images_bytes, stream):
+    """What compress_bstreams and compress_images_writes share: the pointer and total checks, the write table, the images pointer,
+    the item fill and the call of lib().<fn> with `mid` between the images and the items; row(item) is one entry of the result."""
+    q = [tuple(int(v) for v in it) for it in items]
+    src = 0 if d_src is None or d_src.numel() == 0 else _dev_ptr(d_src, f"{who} d_src")
+    total = (0 if d_src is None else d_src.numel()) if src_total is None else int(src_total)
+    if d_src is not None and total > d_src.numel():
+        raise EngineError(f"{who}: src_total {total} lies beyond the tensor's {d_src.numel()} bytes")
+    tab, ntab = 0, 0
+    if d_writes is not None and d_writes.numel():
+        tab, ntab = _writes_ptr(d_writes), d_writes.numel()
+    img, cap = 0, 0
+    if d_images is not None:
+        img = _dev_ptr(d_images, f"{who} d_images")
+        cap = _image_len(d_images, images_bytes, who)
+        if img == 0:
+            raise EngineError(f"{who}: d_images is empty (None asks for the sizes)")
+    arr = (item_cls * max(len(q), 1))()
+    for i, (so, sb, io, ic, wo, nw, wb) in enumerate(q):
+        a = arr[i]
+        a.src_off, a.src_bytes, a.image_off, a.image_cap, a.writes_off, a.n_writes, a.write_bytes = so, sb, io, ic, wo, nw, wb
+    check(getattr(lib(), fn)(src, total, tab, ntab, img, cap, *mid, C.cast(arr, C.c_void_p), len(q), _stream_ptr(stream)), fn)
+    return [dict(row(arr[i]), reason=int(arr[i].reason),
+                 name=BSTREAM_WRITE_REASONS[arr[i].reason] if 0 <= arr[i].reason < len(BSTREAM_WRITE_REASONS) else "?")
+            for i in range(len(q))]
+
+
 def compress_bstreams(d_src, items, d_images, codec=CODEC_LZ4_FAST, level=0, d_writes=None, src_total=None, images_bytes=None, stream=None):
     """Write many block streams with one call, each shaped by its job's write() sizes (fourmc_gpu_bstreams_compress).  `items` is a
     sequence of (src_off, src_bytes, image_off, image_cap, writes_off, n_writes, write_bytes): n_writes entries of d_writes (a uint32
@@ -232,29 +259,9 @@ def compress_bstreams(d_src, items, d_images, codec=CODEC_LZ4_FAST, level=0, d_w
     write (0: one write of the whole source).  d_images None: the size query (image_bytes = the exact worst case of each schedule).
     Returns one dict per item: image_bytes, groups, chunks, reason (a FOURMC_BSW_* number) and "name" (its entry of
     BSTREAM_WRITE_REASONS)."""
-    q = [tuple(int(v) for v in it) for it in items]
-    src = 0 if d_src is None or d_src.numel() == 0 else _dev_ptr(d_src, "compress_bstreams d_src")
-    total = (0 if d_src is None else d_src.numel()) if src_total is None else int(src_total)
-    if d_src is not None and total > d_src.numel():
-        raise EngineError(f"compress_bstreams: src_total {total} lies beyond the tensor's {d_src.numel()} bytes")
-    tab, ntab = 0, 0
-    if d_writes is not None and d_writes.numel():
-        tab, ntab = _writes_ptr(d_writes), d_writes.numel()
-    img, cap = 0, 0
-    if d_images is not None:
-        img = _dev_ptr(d_images, "compress_bstreams d_images")
-        cap = _image_len(d_images, images_bytes, "compress_bstreams")
-        if img == 0:
-            raise EngineError("compress_bstreams: d_images is empty (None asks for the sizes)")
-    arr = (BstreamEncItem * max(len(q), 1))()
-    for i, (so, sb, io, ic, wo, nw, wb) in enumerate(q):
-        a = arr[i]
-        a.src_off, a.src_bytes, a.image_off, a.image_cap, a.writes_off, a.n_writes, a.write_bytes = so, sb, io, ic, wo, nw, wb
-    check(lib().fourmc_gpu_bstreams_compress(src, total, tab, ntab, img, cap, int(codec), int(level), C.cast(arr, C.c_void_p), len(q),
-                                             _stream_ptr(stream)), "fourmc_gpu_bstreams_compress")
-    return [{"image_bytes": int(arr[i].image_bytes), "groups": int(arr[i].groups), "chunks": int(arr[i].chunks), "reason": int(arr[i].reason),
-             "name": BSTREAM_WRITE_REASONS[arr[i].reason] if 0 <= arr[i].reason < len(BSTREAM_WRITE_REASONS) else "?"}
-            for i in range(len(q))]
+    return _compress_writes("compress_bstreams", BstreamEncItem, "fourmc_gpu_bstreams_compress", (int(codec), int(level)),
+                            lambda a: {"image_bytes": int(a.image_bytes), "groups": int(a.groups), "chunks": int(a.chunks)},
+                            d_src, items, d_images, d_writes, src_total, images_bytes, stream)
 
 
 def image_writes_bound(src_bytes):
@@ -268,30 +275,9 @@ def compress_images_writes(d_src, items, d_images, magic=MAGIC_4MC, level=1, d_w
     n_writes, write_bytes), as compress_bstreams takes them; `level` is compress_images' level.  d_images None: the size query
     (image_bytes = the exact worst case of each schedule).  Returns one dict per item: image_bytes, blocks, stored_blocks, reason (a
     FOURMC_BSW_* number) and "name" (its entry of BSTREAM_WRITE_REASONS)."""
-    q = [tuple(int(v) for v in it) for it in items]
-    src = 0 if d_src is None or d_src.numel() == 0 else _dev_ptr(d_src, "compress_images_writes d_src")
-    total = (0 if d_src is None else d_src.numel()) if src_total is None else int(src_total)
-    if d_src is not None and total > d_src.numel():
-        raise EngineError(f"compress_images_writes: src_total {total} lies beyond the tensor's {d_src.numel()} bytes")
-    tab, ntab = 0, 0
-    if d_writes is not None and d_writes.numel():
-        tab, ntab = _writes_ptr(d_writes), d_writes.numel()
-    img, cap = 0, 0
-    if d_images is not None:
-        img = _dev_ptr(d_images, "compress_images_writes d_images")
-        cap = _image_len(d_images, images_bytes, "compress_images_writes")
-        if img == 0:
-            raise EngineError("compress_images_writes: d_images is empty (None asks for the sizes)")
-    arr = (ImageWrItem * max(len(q), 1))()
-    for i, (so, sb, io, ic, wo, nw, wb) in enumerate(q):
-        a = arr[i]
-        a.src_off, a.src_bytes, a.image_off, a.image_cap, a.writes_off, a.n_writes, a.write_bytes = so, sb, io, ic, wo, nw, wb
-    check(lib().fourmc_gpu_images_compress_writes(src, total, tab, ntab, img, cap, int(magic), int(level), C.cast(arr, C.c_void_p), len(q),
-                                                  _stream_ptr(stream)), "fourmc_gpu_images_compress_writes")
-    return [{"image_bytes": int(arr[i].image_bytes), "blocks": int(arr[i].blocks), "stored_blocks": int(arr[i].stored_blocks),
-             "reason": int(arr[i].reason),
-             "name": BSTREAM_WRITE_REASONS[arr[i].reason] if 0 <= arr[i].reason < len(BSTREAM_WRITE_REASONS) else "?"}
-            for i in range(len(q))]
+    return _compress_writes("compress_images_writes", ImageWrItem, "fourmc_gpu_images_compress_writes", (int(magic), int(level)),
+                            lambda a: {"image_bytes": int(a.image_bytes), "blocks": int(a.blocks), "stored_blocks": int(a.stored_blocks)},
+                            d_src, items, d_images, d_writes, src_total, images_bytes, stream)
 
 
 def _bstream_dict(st):

@@ -1,8 +1,9 @@
 """What the many-item entry points of the engine refuse, and in which words: every argument check of fourmc_gpu_images_compress,
-_images_decompress, _bstreams_compress, _bstreams_decompress, _zsts_compress, _zsts_decompress, _image_read, _image_read_lines_batch and
-_images_read_lines, as (return code, fourmc_gpu_last_error()) against tests/golden/engine_arg_messages.json.
+_images_decompress, _bstreams_compress, _images_compress_writes, _bstreams_decompress, _zsts_compress, _zsts_decompress, _image_read,
+_image_read_lines_batch and _images_read_lines, as (return code, fourmc_gpu_last_error()) against
+tests/golden/engine_arg_messages.json.
 
-The golden was recorded from the build in which every entry point still carried its own copy of the span and overlap checks (run
+The golden was recorded from the builds in which every entry point still carried its own copy of the span and overlap checks (run
 this module as a script to write it); it is not written again from code that shares them.  Every refused call returns before a
 device is looked for, so these cases need none and behave the same with one."""
 import ctypes as C
@@ -87,6 +88,13 @@ def bstreams_compress(p, rows, items=True, src=True, writes=True, images=True, c
     arr = _fill(p.BstreamEncItem, ("src_off", "src_bytes", "image_off", "image_cap", "writes_off", "n_writes"), rows)
     return p.lib().fourmc_gpu_bstreams_compress(_ptr(BUF.src, src), SRC, _ptr(BUF.writes, writes), WRITES, _ptr(BUF.img, images), IMG, codec, level,
                                                 _items(arr, items), _n(rows, n), None)
+
+
+# rows: (src_off, src_bytes, image_off, image_cap, writes_off, n_writes)
+def images_compress_writes(p, rows, items=True, src=True, writes=True, images=True, magic=MAGIC, level=1, n=None):
+    arr = _fill(p.ImageWrItem, ("src_off", "src_bytes", "image_off", "image_cap", "writes_off", "n_writes"), rows)
+    return p.lib().fourmc_gpu_images_compress_writes(_ptr(BUF.src, src), SRC, _ptr(BUF.writes, writes), WRITES, _ptr(BUF.img, images), IMG, magic, level,
+                                                     _items(arr, items), _n(rows, n), None)
 
 
 # rows: (src_off, src_bytes, image_off, image_cap, level)
@@ -222,6 +230,28 @@ REFUSED = (
         ("bstreams_compress: two faults, an overlap and the level", bstreams_compress, [BSW, (0, 100, 100, 200, 0, 2)], dict(codec=ZSTD, level=13)),
         ("bstreams_compress: two faults, codec and null items", bstreams_compress, [BSW], dict(items=False, codec=9)),
 
+        # bstreams_compress's rows, one for one, but for the level: this call refuses none
+        ("images_compress_writes: null items", images_compress_writes, [BSW], dict(items=False)),
+        ("images_compress_writes: null source with a non-empty stream", images_compress_writes, [(0, 0, 0, 200, 0, 0), (0, 100, 200, 200, 0, 2)], dict(src=False)),
+        ("images_compress_writes: null write table with writes", images_compress_writes, [(0, 100, 0, 200, 0, 0), (0, 100, 200, 200, 0, 2)], dict(writes=False)),
+        ("images_compress_writes: source starts beyond the buffer", images_compress_writes, [BSW, (SRC + 1, 0, 200, 200, 0, 0)], {}),
+        ("images_compress_writes: source ends beyond the buffer", images_compress_writes, [(SRC - 4, 8, 0, 200, 0, 2)], {}),
+        ("images_compress_writes: src_off + src_bytes wraps", images_compress_writes, [(8, W - 4, 0, 200, 0, 2)], {}),
+        ("images_compress_writes: write sizes start beyond the table", images_compress_writes, [(0, 100, 0, 200, WRITES + 1, 0)], {}),
+        ("images_compress_writes: write sizes end beyond the table", images_compress_writes, [BSW, (0, 100, 200, 200, WRITES - 3, 4)], {}),
+        ("images_compress_writes: writes_off + n_writes wraps", images_compress_writes, [(0, 100, 0, 200, 8, W - 4)], {}),
+        ("images_compress_writes: region starts beyond the images", images_compress_writes, [(0, 100, IMG + 1, 0, 0, 2)], {}),
+        ("images_compress_writes: region ends beyond the images", images_compress_writes, [BSW, (0, 100, IMG - 199, 200, 2, 2)], {}),
+        ("images_compress_writes: image_off + image_cap wraps", images_compress_writes, [(0, 100, 8, W - 4, 0, 2)], {}),
+        ("images_compress_writes: regions overlap by one byte", images_compress_writes, [(0, 100, 200, 200, 0, 2), (0, 100, 1, 200, 2, 2)], {}),
+        ("images_compress_writes: the same region twice", images_compress_writes, [BSW, BSW], {}),
+        ("images_compress_writes: one region inside another", images_compress_writes,
+         [(0, 100, 0, 1000, 0, 2), (0, 100, 2000, 200, 0, 2), (0, 100, 300, 200, 0, 2)], {}),
+        ("images_compress_writes: two faults, a source and its write sizes", images_compress_writes, [(SRC + 1, 0, 0, 200, WRITES + 1, 0)], {}),
+        ("images_compress_writes: two faults, write sizes and the region", images_compress_writes, [(0, 100, IMG + 1, 0, WRITES + 1, 0)], {}),
+        ("images_compress_writes: two faults, an overlap and a later region", images_compress_writes, [BSW, (0, 100, 100, 200, 0, 2), (0, 100, IMG, 1, 0, 2)], {}),
+        ("images_compress_writes: two faults, magic and null items", images_compress_writes, [BSW], dict(items=False, magic=0x12345678)),
+
         ("zsts_compress: null items", zsts_compress, [ZSW], dict(items=False)),
         ("zsts_compress: null source with a non-empty stream", zsts_compress, [(0, 0, 0, 200, 1), (0, 100, 200, 200, 1)], dict(src=False)),
         ("zsts_compress: null images with a non-empty region", zsts_compress, [(0, 100, 0, 0, 1), (0, 100, 200, 200, 1)], dict(images=False)),
@@ -269,7 +299,12 @@ ACCEPTED = [
     ("zsts_decompress: the size query looks at no destination", zsts_decompress, [(0, 100, 0, 200), (100, 100, 100, 200), (0, 100, DST + 1, W - 1)], dict(dst=False)),
     ("bstreams_compress: regions that touch, empty regions", bstreams_compress, [BSW, (0, 100, 200, 200, 2, 2), (0, 100, 100, 0, 0, 0), (SRC, 0, IMG, 0, WRITES, 0)], {}),
     ("bstreams_compress: the size query looks at no region", bstreams_compress, [BSW, (0, 100, 100, 200, 0, 2), (0, 100, IMG + 1, W - 1, 0, 2)], dict(images=False)),
-    ("zsts_compress: regions that touch, empty regions", zsts_compress, [ZSW, (0, 100, 200, 200, 3), (50, 0, 100, 0, 2), (SRC, 0, IMG, 0, 4)], {}),
+    ("images_compress_writes: regions that touch, empty regions", images_compress_writes,
+     [BSW, (0, 100, 200, 200, 2, 2), (0, 100, 100, 0, 0, 0), (SRC, 0, IMG, 0, WRITES, 0)], {}),
+    ("images_compress_writes: the size query looks at no region", images_compress_writes,
+     [BSW, (0, 100, 100, 200, 0, 2), (0, 100, IMG + 1, W - 1, 0, 2)], dict(images=False)),
+    ("images_compress_writes: every level is taken", images_compress_writes, [BSW], dict(level=99)),
+    ("zsts_compress: regions that touch, empty regions", zsts_compress,[ZSW, (0, 100, 200, 200, 3), (50, 0, 100, 0, 2), (SRC, 0, IMG, 0, 4)], {}),
     ("image_read: destinations that touch, empty ranges", image_read, [(0, 100, 0), (0, 100, 100), (0, 0, 50), (0, 0, W - 1)], {}),
     ("image_read: a null destination of empty ranges", image_read, [(0, 0, 0), (0, 0, 0)], dict(dst=False)),
     ("image_read_lines_batch: regions that touch, empty regions", lines_batch,

@@ -13,8 +13,11 @@ import numpy as np
 import pytest
 import torch
 
+import bstream_model as bm
+import bstream_writes_model as wm
 import fourmc_stream_cases as cases
 import fourmc_stream_model as fm
+import helpers
 import line_index_model as lim
 import lines_model as lm
 
@@ -186,6 +189,54 @@ def test_rounds_of_three_blocks_end_inside_streams_and_inside_a_long_write(p, ma
     for c, st, g in zip(cs, res, got):
         img, _, lens, stored = want(magic, 1, c)
         assert g == img and st["stored_blocks"] == sum(stored), c.name
+
+
+# ---- next to the block streams --------------------------------------------------------------------------------------------------
+def test_streams_and_images_take_turns_on_one_stream_and_keep_their_bytes(p):
+    """compress_bstreams and compress_images_writes run through one host path and lease the same two workspace registries.  On one
+    stream, with rounds of three chunks: block streams (LZ4 fast), .4mc images (level 1), block streams again, each over a source of
+    0 bytes, one of 5 000 bytes written 7 at a time from the table and one of 12 000 bytes as uniform writes of 4 096; then the same
+    with twice the items, so that both leases grow between the calls.  Every byte is the model's, and the streams come out the same
+    before and after the images."""
+    text = helpers.corpus(40000).tobytes()
+    lz4, blk = bm.oracle_compressor(0, 0), fm.compressor(MC, 1)
+    sevens = [7] * (5000 // 7) + [5000 % 7]
+    d_src = torch.from_numpy(np.frombuffer(text + b"\0" * 64, np.uint8).copy()).cuda()
+    d_writes = torch.from_numpy(np.array([9] * 3 + sevens, np.int32)).cuda()
+    assert "FOURMC_BSW_ROUND" not in os.environ
+    os.environ["FOURMC_BSW_ROUND"] = "3"
+    try:
+        for copies in (1, 2):
+            srcs = [(off, k, sizes, tab) for c in range(copies)
+                    for off, k, sizes, tab in ((11 + 17001 * c, 0, [], False), (11 + 17001 * c, 5000, sevens, True),
+                                               (5011 + 17001 * c, 12000, wm.uniform(12000, 4096), False))]
+            rows = [[off, k, 0, 0, 3 if tab else 0, len(sizes) if tab else 0, 0 if tab else 4096] for off, k, sizes, tab in srcs]
+            want_s = [bm.write_stream(text[off:off + k], sizes, lz4, False) for off, k, sizes, _ in srcs]
+            want_i = [fm.image(text[off:off + k], sizes, blk, MC)[0] for off, k, sizes, _ in srcs]
+
+            def call(fn, caps, *args):
+                at = GUARD
+                for r, cap in zip(rows, caps):
+                    r[2], r[3] = at, cap
+                    at += cap + GUARD
+                d_images = torch.full((at + SLACK,), CANARY, dtype=torch.uint8, device="cuda")
+                res = fn(d_src, [tuple(r) for r in rows], d_images, *args, d_writes=d_writes, images_bytes=at)
+                out = d_images.cpu().numpy()
+                got = [out[r[2]:r[2] + st["image_bytes"]].tobytes() for r, st in zip(rows, res)]
+                for r, st in zip(rows, res):
+                    assert st["reason"] == 0 and st["image_bytes"] <= r[3], st
+                    out[r[2]:r[2] + st["image_bytes"]] = CANARY
+                assert (out == CANARY).all(), "bytes written outside the regions"
+                return res, got
+            s_caps = [p.bstream_writes_bound(k, 0) for _, k, _, _ in srcs]
+            i_caps = [fm.worst_case(sizes) for _, _, sizes, _ in srcs]
+            first = call(p.compress_bstreams, s_caps, 0, 0)
+            images = call(p.compress_images_writes, i_caps, MC, 1)
+            again = call(p.compress_bstreams, s_caps, 0, 0)
+            assert first[1] == want_s and images[1] == want_i
+            assert again == first
+    finally:
+        del os.environ["FOURMC_BSW_ROUND"]
 
 
 # ---- the readers on uneven blocks -----------------------------------------------------------------------------------------------
