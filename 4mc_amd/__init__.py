@@ -16,7 +16,7 @@ from .binding import (  # noqa: F401
     BLOCK_DTYPE, BLOCKSIZE, MAGIC_4MC, MAGIC_4MZ, CODEC_LZ4_FAST, CODEC_LZ4_MC, CODEC_LZ4_HC,
     CODEC_ZSTD, BLK_BADSUM, BLK_CORRUPT, EngineError, lib, lib_path, research_lib_path, use_research, cli_path, exported_symbols,
     make_blocks, gpu_init, ImageStatus, ImageItem, ImageEncItem, ImageEntry, ImageIndexInfo, ImageRange, IMAGE_ENTRY_DTYPE, ImageSlice, ImageRecords, ImageLines, ImageSplitItem,
-    ImageRef, ImagesSplitItem, ImagesSlice, ImageLineEntry, ImageLineInfo, ImageLinesAt, IMAGE_LINE_ENTRY_DTYPE, BstreamStatus, BstreamItem, BstreamEncItem, ImageWrItem, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, bstream_codec,
+    ImageRef, ImagesSplitItem, ImagesSlice, ImageLineEntry, ImageLineInfo, ImageLinesAt, IMAGE_LINE_ENTRY_DTYPE, BstreamStatus, BstreamItem, BstreamEncItem, ImageWrItem, LinesSrc, LinesPackItem, LinesWrItem, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, bstream_codec,
     ZstStatus, ZstItem, ZST_REASONS, ZstwStatus, ZstwItem, ZSTW_REASONS,
 )
 from .engine import (  # noqa: F401
@@ -27,6 +27,7 @@ from .engine import (  # noqa: F401
     ImageReader,
     bstream_max_input, bstream_bound, compress_bstream, decompress_bstream, decompress_bstreams, compress_bstreams, bstream_writes_bound,
     compress_images_writes, image_writes_bound,
+    LinesSource, pack_lines, write_lines_images, write_lines_bstreams,
     decompress_zst, decompress_zsts, zst_stats,
     compress_zst, compress_zsts, zst_bound, zst_codec_level,
 )

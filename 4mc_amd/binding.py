@@ -76,7 +76,27 @@ class ImageWrItem(C.Structure):
 
 assert C.sizeof(ImageWrItem) == 80
 # FOURMC_BSW_*: the verdict of compress_bstreams on one stream, by number
-BSTREAM_WRITE_REASONS = ("OK", "SUM", "WRITE", "CAP")
+BSTREAM_WRITE_REASONS = ("OK", "SUM", "WRITE", "CAP", "LINE")
+
+
+# struct fourmc_lines_src / fourmc_lines_pack_item / fourmc_lines_wr_item (include/fourmc_gpu.h: text lines written as part files)
+class LinesSrc(C.Structure):
+    _fields_ = [("d_text", C.c_void_p), ("text_bytes", C.c_uint64), ("d_starts", C.c_void_p), ("row_bytes", C.c_uint32),
+                ("d_text_len", C.c_void_p), ("table_lines", C.c_uint64), ("d_pick", C.c_void_p), ("pick_total", C.c_uint64)]
+
+
+class LinesPackItem(C.Structure):
+    _fields_ = [("line_off", C.c_uint64), ("n_lines", C.c_uint64), ("packed_off", C.c_uint64), ("packed_cap", C.c_uint64),
+                ("writes_off", C.c_uint64), ("reason", C.c_int32), ("pad", C.c_int32), ("packed_bytes", C.c_uint64)]
+
+
+class LinesWrItem(C.Structure):
+    _fields_ = [("line_off", C.c_uint64), ("n_lines", C.c_uint64), ("image_off", C.c_uint64), ("image_cap", C.c_uint64),
+                ("reason", C.c_int32), ("pad", C.c_int32), ("text_bytes", C.c_uint64), ("image_bytes", C.c_uint64),
+                ("blocks", C.c_uint64), ("stored_blocks", C.c_uint64)]
+
+
+assert C.sizeof(LinesSrc) == 64 and C.sizeof(LinesPackItem) == 56 and C.sizeof(LinesWrItem) == 72
 # FOURMC_BS_*: the verdict of a block-stream decode, by number
 BSTREAM_REASONS = ("OK", "BAD_RAWLEN", "CLEN_UNREADABLE", "BAD_CLEN", "DATA_UNREADABLE", "CORRUPT", "SHAPE", "DST_SMALL")
 # struct fourmc_zst_status / fourmc_zst_item (include/fourmc_gpu.h: .zst streams)
@@ -276,6 +296,9 @@ _GPU_API = {
     "fourmc_gpu_bstream_writes_bound": (C.c_uint64, [C.c_uint64, C.c_int]),
     "fourmc_gpu_images_compress_writes": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_image_writes_bound": (C.c_uint64, [C.c_uint64]),
+    "fourmc_gpu_lines_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "fourmc_gpu_images_write_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "fourmc_gpu_bstreams_write_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
     "fourmc_gpu_image_parse_stats": (None, [C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "fourmc_gpu_image_decode_blocks": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -27,6 +27,7 @@
 #include "kernels.h"
 #include "devcopy.h"
 #include "devframe.h"
+#include "bswscan.h"
 
 namespace {
 
@@ -220,32 +221,10 @@ void bstream_pack_kernel(const uint8_t* __restrict__ staging, uint8_t* __restric
 // BlockCompressorStream's rule over a stream's write() sizes w_0 .. w_{k-1} (include/fourmc_gpu.h): at write i with nothing
 // accumulated, w_i > M is a long group of ceil(w_i / M) chunks; otherwise the group takes writes i .. j for the largest j whose sum
 // stays <= M and is one chunk; a group of sum 0 is not written.  A group is long exactly when its rawlen is above M.
-constexpr uint32_t kBswTile = 64;                        // table entries per tile: one wave reads a tile in one step
+// (kBswTile, scan_add64 and bsw_owner: bswscan.h, shared with lines_pack.hip)
 constexpr uint64_t kBswBadBit = 1ull << 63;              // in a tile's sum, before the finish: an entry above 0x7FFFFFFF
 
 __device__ __forceinline__ uint32_t bsw_slot(int zstd, uint32_t len) { return (fourmc_bstream_block_bound(zstd, len) + 255u) & ~255u; }
-
-// wave64 inclusive prefix sum of 64-bit values
-__device__ __forceinline__ uint64_t scan_add64(uint64_t v, int lane)
-{
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t up = uint64_t(__shfl_up((long long)v, o));
-        if (lane >= o) v += up;
-    }
-    return v;
-}
-
-// the largest i in [0, n) with first[i * stride8] <= x, for a table of n + 1 ascending 64-bit values whose first is 0 and whose last
-// is above x (entries of equal value are items that own nothing: the last of them owns x)
-__device__ __forceinline__ uint32_t bsw_owner(const uint64_t* __restrict__ first, uint32_t stride8, uint32_t n, uint64_t x)
-{
-    uint32_t lo = 0, hi = n;                             // first[lo] <= x < first[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (first[size_t(mid) * stride8] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // one wave per tile of 64 entries, over the tiles of all streams: sums[tile] = the sum of its entries, kBswBadBit set when one of
 // them is above 0x7FFFFFFF

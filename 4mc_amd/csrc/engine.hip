@@ -85,6 +85,8 @@ int ensure_device()
 std::map<hipStream_t, StreamWs*> g_ws;
 std::map<hipStream_t, StreamWs*> g_img_ws;
 std::map<hipStream_t, StreamWs*> g_img_stage;
+std::map<hipStream_t, StreamWs*> g_txt_ws;
+std::map<hipStream_t, StreamWs*> g_txt_stage;
 
 int WsLease::get(hipStream_t s, size_t need, void** out)
 {
@@ -148,7 +150,7 @@ int fourmc_gpu_release_workspaces(void)
 {
     std::vector<std::pair<hipStream_t, StreamWs*>> all;
     { std::lock_guard<std::mutex> lk(g_wsmu); for (auto& kv : g_ws) all.push_back(kv); for (auto& kv : g_img_ws) all.push_back(kv);
-      for (auto& kv : g_img_stage) all.push_back(kv); }
+      for (auto& kv : g_img_stage) all.push_back(kv); for (auto& kv : g_txt_ws) all.push_back(kv); for (auto& kv : g_txt_stage) all.push_back(kv); }
     for (auto& kv : all) {
         std::lock_guard<std::mutex> lk(kv.second->mu);
         if (kv.second->p) {

@@ -43,6 +43,10 @@ extern std::map<hipStream_t, StreamWs*> g_img_ws;
 // image_read's descriptors and staging slots: a third registry, so that sizing them after the plan's read-back cannot move the
 // index and the plan that the second one holds
 extern std::map<hipStream_t, StreamWs*> g_img_stage;
+// The line writers (engine_text.hip) call the write planner's host path, which leases and may grow both of those: their own tables
+// (items, tile prefixes, per-line offsets) and their staging (the packed text and its write table) live in two registries of their own
+extern std::map<hipStream_t, StreamWs*> g_txt_ws;
+extern std::map<hipStream_t, StreamWs*> g_txt_stage;
 
 class WsLease {
     StreamWs* w_ = nullptr;

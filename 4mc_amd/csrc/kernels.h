@@ -479,6 +479,31 @@ hipError_t fourmc_launch_imgw_seal(const fourmc_block* d_blocks, const fourmc_bs
 hipError_t fourmc_launch_imgw_tail(void* d_images, const fourmc_bstream_enc_item* d_items, const fourmc_bsw_plan* d_plans,
                                    const fourmc_bsw_slice* d_slices, const uint64_t* d_idx, const fourmc_imgw_run* d_run, uint32_t n,
                                    uint32_t magic, fourmc_imgw_result* d_res, hipStream_t s);
+/* fourmc_gpu_lines_pack and the two line writers (lines_pack.hip).  An item on the device (the engine uploads n + 1 of them, the last
+ * one with the totals in tile0 and off0): its lines, its place, its first tile of 64 lines counted over all items and the first of
+ * its n_lines + 1 per-line offsets.  Its tile prefixes are the tiles + 1 entries of d_prefix from tile0 + (the item's number) on. */
+typedef struct fourmc_lp_item {         /* 64 bytes */
+    uint64_t line_off, n_lines, packed_off, packed_cap, writes_off;
+    uint64_t tile0, off0, pad;
+} fourmc_lp_item;
+/* what the measure leaves per item for the read-back (n + 1 entries; entry n: bytes = packed_off = the bytes of all items that are
+ * OK, chunk0 = the chunks of the gather) */
+typedef struct fourmc_lp_sum {          /* 32 bytes */
+    uint64_t bytes;            /* T: the packed text's length (0 for _WRITE and _LINE)                      */
+    uint64_t packed_off;       /* where it goes: the item's own packed_off, or (mode 2) behind the items before it */
+    uint64_t chunk0;           /* its first chunk of the gather, counted over all items                     */
+    int32_t  reason;           /* FOURMC_BSW_OK / _WRITE / _LINE / _CAP                                     */
+    uint32_t pad;
+} fourmc_lp_sum;
+/* the lengths, offsets in the tile (d_off), tile prefixes (d_prefix: ntiles + n entries), T and verdicts; mode 0: the query, 1: the
+ * items' own places with _CAP, 2: the items placed one behind the other from byte 0; base16: the packed buffer's address mod 16 */
+hipError_t fourmc_launch_lp_measure(const fourmc_lines_src* src, const fourmc_lp_item* d_items, uint32_t n, uint64_t ntiles, int mode,
+                                    uint32_t base16, uint64_t* d_prefix, uint64_t* d_off, fourmc_lp_sum* d_sums, hipStream_t s);
+/* for the items that are OK: the 64-bit offset of every line, the write table (d_writes NULL: none) and the gather into d_packed
+ * (NULL: none), nchunks workgroups */
+hipError_t fourmc_launch_lp_copy(const fourmc_lines_src* src, const fourmc_lp_item* d_items, const fourmc_lp_sum* d_sums, uint32_t n,
+                                 uint64_t ntiles, uint64_t nchunks, const uint64_t* d_prefix, uint64_t* d_off, void* d_packed,
+                                 uint32_t* d_writes, hipStream_t s);
 #ifdef FOURMC_RESEARCH      /* the research side build exports these two: tools/zstd_timing.py and tools/k7x_prof.py size their read-backs with them */
 #pragma GCC visibility push(default)
 #endif

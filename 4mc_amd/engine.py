@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .binding import (ZST_REASONS, ZSTW_REASONS, ZstItem, ZstStatus, ZstwItem, ZstwStatus, BLOCK_DTYPE, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, CODEC_LZ4_FAST, BstreamEncItem, BstreamItem, BstreamStatus, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageWrItem, ImageIndexInfo, ImageItem, ImageLines, ImageLineInfo, ImageLinesAt, ImageRef, ImageSplitItem,
+from .binding import (ZST_REASONS, ZSTW_REASONS, ZstItem, ZstStatus, ZstwItem, ZstwStatus, BLOCK_DTYPE, BSTREAM_REASONS, BSTREAM_WRITE_REASONS, CODEC_LZ4_FAST, BstreamEncItem, BstreamItem, BstreamStatus, IMAGE_ENTRY_DTYPE, MAGIC_4MC, EngineError, ImageEncItem, ImageWrItem, LinesSrc, LinesPackItem, LinesWrItem, ImageIndexInfo, ImageItem, ImageLines, ImageLineInfo, ImageLinesAt, ImageRef, ImageSplitItem,
                       ImagesSlice, ImagesSplitItem,
                       ImageRange, ImageRecords, ImageSlice, ImageStatus, check, lib)
 
@@ -278,6 +278,105 @@ def compress_images_writes(d_src, items, d_images, magic=MAGIC_4MC, level=1, d_w
     return _compress_writes("compress_images_writes", ImageWrItem, "fourmc_gpu_images_compress_writes", (int(magic), int(level)),
                             lambda a: {"image_bytes": int(a.image_bytes), "blocks": int(a.blocks), "stored_blocks": int(a.stored_blocks)},
                             d_src, items, d_images, d_writes, src_total, images_bytes, stream)
+
+
+class LinesSource:
+    """Lines in device memory, as the line readers hand them out (struct fourmc_lines_src).  `text`: a uint8 CUDA tensor of any
+    shape; `text_len`: int32 / uint32, one entry per table line; `starts`: int64 offsets into text (image_read_lines' table), or
+    None for rows of `row_bytes` (image_read_lines_at's; default: the row length of a two-dimensional text); `pick`: int64 table
+    line numbers, or None for the table's own order.  table_lines defaults to text_len.numel(), text_bytes to text.numel()."""
+
+    def __init__(self, text, text_len, starts=None, row_bytes=0, pick=None, text_bytes=None, table_lines=None):
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+
+        def table(t, kinds, what):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype in kinds):
+                raise EngineError(f"LinesSource {what}: a contiguous CUDA tensor of {' / '.join(str(k) for k in kinds)} is required")
+            return t
+        self.text = None if text is None else table(text, (torch.uint8,), "text")
+        self.text_len = None if text_len is None else table(text_len, words, "text_len")
+        self.starts = None if starts is None else table(starts, (torch.int64,), "starts")
+        self.pick = None if pick is None else table(pick, (torch.int64,), "pick")
+        if starts is None and not row_bytes and self.text is not None and self.text.dim() == 2:
+            row_bytes = self.text.shape[1]
+        self.row_bytes = int(row_bytes)
+        self.text_bytes = (0 if self.text is None else self.text.numel()) if text_bytes is None else int(text_bytes)
+        self.table_lines = (0 if self.text_len is None else self.text_len.numel()) if table_lines is None else int(table_lines)
+        if self.text is not None and self.text_bytes > self.text.numel():
+            raise EngineError("LinesSource: text_bytes lies beyond the text tensor")
+        if any(t is not None and self.table_lines > t.numel() for t in (self.text_len, self.starts)):
+            raise EngineError("LinesSource: table_lines lies beyond the tables")
+
+    def struct(self):
+        def at(t):
+            return int(t.data_ptr()) if t is not None and t.numel() else None
+        return LinesSrc(at(self.text), self.text_bytes, at(self.starts), self.row_bytes, at(self.text_len), self.table_lines,
+                        at(self.pick), 0 if self.pick is None else self.pick.numel())
+
+
+def _lines_src(src):
+    return src if isinstance(src, LinesSource) else LinesSource(**src)
+
+
+def _bsw_name(reason):
+    return BSTREAM_WRITE_REASONS[reason] if 0 <= reason < len(BSTREAM_WRITE_REASONS) else "?"
+
+
+def pack_lines(src, items, d_packed, d_writes=None, packed_total=None, stream=None):
+    """Lines into the data and the write() sizes of a TextOutputFormat job (fourmc_gpu_lines_pack): for every item text_0 LF text_1
+    LF ... at d_packed[packed_off:] and the sizes len_0, 1, len_1, 1, ... at d_writes[writes_off:], ready for compress_images_writes,
+    compress_bstreams or compress_zsts.  `src`: a LinesSource, or a dict of its arguments; `items`: a sequence of (line_off, n_lines,
+    packed_off, packed_cap, writes_off); d_writes: an int32 / uint32 CUDA tensor.  d_packed None: the size query.  Returns one dict
+    per item: packed_bytes, reason (a FOURMC_BSW_* number) and "name" (its entry of BSTREAM_WRITE_REASONS)."""
+    s = _lines_src(src).struct()
+    q = [tuple(int(v) for v in it) for it in items]
+    dst, cap, tab, ntab = 0, 0, 0, 0
+    if d_packed is not None:
+        dst = _dev_ptr(d_packed, "pack_lines d_packed")
+        cap = _image_len(d_packed, packed_total, "pack_lines")
+        if dst == 0:
+            raise EngineError("pack_lines: d_packed is empty (None asks for the sizes)")
+    if d_writes is not None and d_writes.numel():
+        tab, ntab = _writes_ptr(d_writes), d_writes.numel()
+    arr = (LinesPackItem * max(len(q), 1))()
+    for i, (lo, nl, po, pc, wo) in enumerate(q):
+        a = arr[i]
+        a.line_off, a.n_lines, a.packed_off, a.packed_cap, a.writes_off = lo, nl, po, pc, wo
+    check(lib().fourmc_gpu_lines_pack(C.byref(s), dst, cap, tab, ntab, C.cast(arr, C.c_void_p), len(q), _stream_ptr(stream)), "fourmc_gpu_lines_pack")
+    return [{"packed_bytes": int(arr[i].packed_bytes), "reason": int(arr[i].reason), "name": _bsw_name(arr[i].reason)} for i in range(len(q))]
+
+
+def _write_lines(who, fn, mid, src, items, d_images, images_bytes, stream):
+    s = _lines_src(src).struct()
+    q = [tuple(int(v) for v in it) for it in items]
+    img, cap = 0, 0
+    if d_images is not None:
+        img = _dev_ptr(d_images, f"{who} d_images")
+        cap = _image_len(d_images, images_bytes, who)
+        if img == 0:
+            raise EngineError(f"{who}: d_images is empty (None asks for the sizes)")
+    arr = (LinesWrItem * max(len(q), 1))()
+    for i, (lo, nl, io, ic) in enumerate(q):
+        a = arr[i]
+        a.line_off, a.n_lines, a.image_off, a.image_cap = lo, nl, io, ic
+    check(getattr(lib(), fn)(C.byref(s), img, cap, *mid, C.cast(arr, C.c_void_p), len(q), _stream_ptr(stream)), fn)
+    return [{"text_bytes": int(arr[i].text_bytes), "image_bytes": int(arr[i].image_bytes), "blocks": int(arr[i].blocks),
+             "stored_blocks": int(arr[i].stored_blocks), "reason": int(arr[i].reason), "name": _bsw_name(arr[i].reason)} for i in range(len(q))]
+
+
+def write_lines_images(src, items, d_images, magic=MAGIC_4MC, level=1, images_bytes=None, stream=None):
+    """Lines as the .4mc / .4mz part files of a TextOutputFormat job, many per call (fourmc_gpu_images_write_lines): each item's image
+    is what compress_images_writes writes for the lines' text with a newline behind each and two write() calls per line.  `src`: a
+    LinesSource or a dict of its arguments; `items`: a sequence of (line_off, n_lines, image_off, image_cap); `level`:
+    compress_images' level.  d_images None: the size query.  Returns one dict per item: text_bytes, image_bytes, blocks,
+    stored_blocks, reason (a FOURMC_BSW_* number) and "name" (its entry of BSTREAM_WRITE_REASONS)."""
+    return _write_lines("write_lines_images", "fourmc_gpu_images_write_lines", (int(magic), int(level)), src, items, d_images, images_bytes, stream)
+
+
+def write_lines_bstreams(src, items, d_images, codec=CODEC_LZ4_FAST, level=0, images_bytes=None, stream=None):
+    """Lines as the Lz4Codec / ZstdCodec part files of a TextOutputFormat job, many per call (fourmc_gpu_bstreams_write_lines): as
+    write_lines_images, over compress_bstreams; (codec, level) as bstream_codec(ext) gives them.  `blocks` counts the chunks."""
+    return _write_lines("write_lines_bstreams", "fourmc_gpu_bstreams_write_lines", (int(codec), int(level)), src, items, d_images, images_bytes, stream)
 
 
 def _bstream_dict(st):

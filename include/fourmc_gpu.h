@@ -935,7 +935,8 @@ enum {
     FOURMC_BSW_OK    = 0,
     FOURMC_BSW_SUM   = 1,   /* the write sizes do not sum to src_bytes                    */
     FOURMC_BSW_WRITE = 2,   /* a write size above 0x7FFFFFFF                              */
-    FOURMC_BSW_CAP   = 3    /* image_cap below the exact worst case of the schedule       */
+    FOURMC_BSW_CAP   = 3,   /* image_cap below the exact worst case of the schedule       */
+    FOURMC_BSW_LINE  = 4    /* the line writers below: a line that cannot be read         */
 };
 typedef struct fourmc_bstream_enc_item {   /* 72 bytes */
     uint64_t src_off, src_bytes;      /* in : d_src[src_off, +src_bytes)                                             */
@@ -1019,6 +1020,102 @@ int fourmc_gpu_images_compress_writes(const void* d_src, uint64_t src_total, con
                                       void* d_images, uint64_t images_bytes, uint32_t magic, int level,
                                       fourmc_image_wr_item* items /*host*/, uint32_t n, void* stream);
 uint64_t fourmc_gpu_image_writes_bound(uint64_t src_bytes);   /* host only, holds for every schedule */
+
+/* ---- text lines written as the part files of a TextOutputFormat job, many per call -------------------------------------------------
+ * The line readers above hand out lines in two layouts: a packed buffer with a table of starts and a table of text lengths
+ * (image_read_lines, _batch, images_read_lines), or rows of a fixed stride with a table of text lengths (image_read_lines_at).  These
+ * calls take lines in either layout - all of them, or the ones a table of picks names, in its order - and write them as the files a
+ * job with TextOutputFormat and one of the sixteen codecs writes.
+ * The writer rule.  Hadoop's TextOutputFormat.LineRecordWriter with a NullWritable / null key, over new DataOutputStream(
+ *   codec.createOutputStream(fileOut)), issues for every record out.write(text, 0, len) and then out.write(NEWLINE), NEWLINE the one
+ *   byte 0x0A; DataOutputStream passes both straight to the codec stream's write(b, off, len).  This is written from knowledge of
+ *   Hadoop's classes: the Hadoop source is not part of this tree and no JVM wrote a fixture.  For lines of text lengths
+ *   l_0 .. l_{k-1} the data is text_0 '\n' text_1 '\n' .. text_{k-1} '\n', T = sum(l_j) + k bytes, and the write schedule is
+ *   [l_0, 1, l_1, 1, .., l_{k-1}, 1], 2 k entries - not one write per line: FourMcOutputStream ends blocks at write boundaries
+ *   (FourMcOutputStream.java:153-181), so a block can end between a text and its LF, and a line of 4 MiB is followed by a block that
+ *   holds only the LF.  An empty line is a zero-length write, which both streams ignore, and a one-byte write.  Every record gets its
+ *   newline: the data always ends with LF, and an image whose last line was unterminated comes back one byte longer.  Text is copied
+ *   as it is: a CR or LF inside a text is written and reads back as more lines, as with the Java writer.  No line at all is the stream
+ *   with no write: the 44-byte image, or the block stream 00 00 00 00.  tests/text_output_model.py restates the rule.
+ * The lines (fourmc_lines_src, in device memory, one description per call).  Table line k is d_text_len[k] bytes at
+ *   d_text[d_starts[k]] - or, with d_starts NULL, at d_text[k * row_bytes], the rows of image_read_lines_at.  Output line j of an item
+ *   is table line d_pick[line_off + j], or line_off + j without d_pick.  A pick may name a line more than once and in any order, two
+ *   items may share picks and lines, and lines may overlap in d_text: a compaction of matching line numbers, a slice of a random
+ *   permutation or the d_lines of image_read_lines_at can be passed as they are.
+ * Verdicts, per item, FOURMC_BSW_*, the first that applies; an item that gets one copies nothing and costs only itself:
+ *   FOURMC_BSW_WRITE  a text length above 0x7FFFFFFF (the write planner would refuse that write; it is decided before any copy);
+ *   FOURMC_BSW_LINE   a line that cannot be read: a pick >= table_lines, d_starts[k] + d_text_len[k] > text_bytes, or in the row
+ *                     layout d_text_len[k] > row_bytes (the reader cut that row short; writing it would silently lose text);
+ *   FOURMC_BSW_CAP    lines_pack: packed_cap < T.  The writers: image_cap below the exact worst case, as the call below them says;
+ *   FOURMC_BSW_SUM    is never given (the write table is made from the same lengths as the text).
+ * fourmc_gpu_lines_pack writes, for every item that is OK, the data to d_packed[packed_off, +T) and the schedule to
+ *   d_writes[writes_off, +2 n_lines): what fourmc_gpu_images_compress_writes, fourmc_gpu_bstreams_compress and - for .zst targets,
+ *   whose files do not depend on write sizes - fourmc_gpu_zsts_compress take.  packed_bytes = T, also for _CAP; 0 for _WRITE and
+ *   _LINE.  d_packed NULL is the size query: nothing is copied, no table is written, regions are not looked at.  The call returns
+ *   after its one synchronization; the copy is queued on `stream` behind it.
+ * The two writers are the pack into staging the call owns followed by fourmc_gpu_images_compress_writes / fourmc_gpu_bstreams_compress
+ *   themselves, with d_src = the staging and d_writes = the packed table.  THE ONE RULE: for every item that is OK the image is, byte
+ *   for byte, what that call writes for the data and the schedule of the writer rule, and image_bytes, blocks, stored_blocks and the
+ *   size query are that call's (block streams: blocks = its chunks, stored_blocks = 0).  An item the pack refused goes below as an
+ *   item that owns nothing, so its neighbours' bytes and verdicts are those of a call without it; its image_bytes, blocks and
+ *   stored_blocks are 0.  text_bytes = T.  d_images NULL is the size query: nothing is copied (only the write table is made, which the
+ *   planner reads) and image_bytes is the exact worst case of the schedule.  `magic`, `level`, `codec`: as those calls take them.
+ * Staging, leased per stream from two registries of the line writers' own (the calls below lease theirs and may grow them) and given
+ *   back by fourmc_gpu_release_workspaces: 64 bytes per item, 8 bytes per line and per 64 lines for the offsets and tile prefixes;
+ *   for the writers also sum(T) bytes of text and 8 bytes per line of write sizes.
+ * Arguments, checked on the host before a device is looked for, each FOURMC_EINVAL with `items` untouched and a message that names the
+ *   call and the item: the magic / codec checks of the calls below, first; then src or items NULL with n > 0; d_text NULL with
+ *   text_bytes > 0; d_text_len NULL with table_lines > 0; d_starts NULL and row_bytes 0 with table_lines > 0; in the row layout
+ *   table_lines * row_bytes overflowing or above text_bytes; per item [line_off, +n_lines) outside pick_total (outside table_lines
+ *   without a pick); and - unless this is the query - d_writes NULL (lines_pack), a region outside its buffer, a write slice
+ *   [writes_off, +2 n_lines) outside writes_total, two regions of nonzero capacity or two non-empty write slices that overlap.  A zstd
+ *   level outside the device's 1 .. 12 (bstreams_write_lines): FOURMC_EUNSUP.  n == 0: FOURMC_OK.  No device: FOURMC_ENODEV.  More
+ *   than 2^31 - 1 chunks of 16 KiB in one call, or an item of 2^38 lines or more: FOURMC_EUNSUP.
+ * Work.  Measure: one lane per output line, one wave per tile of 64 lines, resolves the pick, reads the length, checks it and scans
+ *   the piece sizes l + 1; one workgroup per item turns the tile sums into 64-bit prefixes, T and the verdict; one wave places the
+ *   items.  After the read-back: the same tiles give every line its 64-bit offset in its item's text and the write table.  Gather:
+ *   the packed text is cut into chunks of 16 KiB, one workgroup of 256 each, whatever the lines are; a workgroup finds its chunk's
+ *   first and last line by searching the tile prefixes and one tile, and every lane owns aligned 16-byte pieces of the output, which
+ *   it fills from one unaligned 16-byte load when they lie inside one text and byte by byte, terminators included, where lines meet.
+ *   The kernels clamp what they read from the tables a second time: tables that change during the call may give wrong text, never an
+ *   access outside d_text[0, text_bytes), the item's region or its write slice.
+ * Synchronizations of `stream`: lines_pack one (the items' sums and verdicts), also as the query; each writer three (that one and
+ *   the two of the call below), its query two.  A lease that has to grow synchronizes once more.
+ * Writes.  Nothing outside d_packed[packed_off, +T) and d_writes[writes_off, +2 n_lines) / [image_off, +image_bytes) of the items
+ *   that are OK.  d_text, the tables and the outputs must not overlap each other (not checked).
+ * Not reproduced: the key form of the record writer (key, separator, value, newline: four writes per record); a separator or
+ *   terminator other than LF; .zst targets through a call of their own (lines_pack plus fourmc_gpu_zsts_compress gives them); .4mc
+ *   and .4mz in one call; a streaming form. */
+typedef struct fourmc_lines_src {
+    const void*     d_text;      uint64_t text_bytes;   /* the bytes the lines point into                                      */
+    const uint64_t* d_starts;                           /* line k's text starts at d_text[d_starts[k]]; NULL: at k * row_bytes  */
+    uint32_t        row_bytes;                          /* the stride when d_starts is NULL (image_read_lines_at's rows)        */
+    const uint32_t* d_text_len;                         /* text length without terminator, as the readers write it             */
+    uint64_t        table_lines;                        /* entries of d_starts / d_text_len (rows of d_text)                    */
+    const uint64_t* d_pick;      uint64_t pick_total;   /* optional: output line j of an item is table line d_pick[line_off + j];
+                                                           NULL: table line line_off + j.  Duplicates and any order allowed      */
+} fourmc_lines_src;
+typedef struct fourmc_lines_pack_item {   /* host, 56 bytes */
+    uint64_t line_off, n_lines;           /* in : entries of d_pick if given, else of the tables                         */
+    uint64_t packed_off, packed_cap;      /* in : the text goes to d_packed[packed_off, +packed_cap)                     */
+    uint64_t writes_off;                  /* in : its 2 * n_lines sizes go to d_writes[writes_off, ...)                   */
+    int32_t  reason, pad;                 /* out: FOURMC_BSW_OK / _WRITE / _LINE / _CAP                                  */
+    uint64_t packed_bytes;                /* out: T (also for the query and for _CAP)                                    */
+} fourmc_lines_pack_item;
+int fourmc_gpu_lines_pack(const fourmc_lines_src* src, void* d_packed, uint64_t packed_total,
+                          uint32_t* d_writes, uint64_t writes_total,
+                          fourmc_lines_pack_item* items /*host*/, uint32_t n, void* stream);
+typedef struct fourmc_lines_wr_item {     /* host, 72 bytes */
+    uint64_t line_off, n_lines;           /* in : entries of d_pick if given, else of the tables                         */
+    uint64_t image_off, image_cap;        /* in : the file goes to d_images[image_off, +image_cap)                       */
+    int32_t  reason, pad;                 /* out: FOURMC_BSW_* of the pack or of the writer below it                     */
+    uint64_t text_bytes;                  /* out: T                                                                      */
+    uint64_t image_bytes, blocks, stored_blocks;   /* out: as fourmc_image_wr_item has them; block streams: chunks, 0    */
+} fourmc_lines_wr_item;
+int fourmc_gpu_images_write_lines  (const fourmc_lines_src* src, void* d_images, uint64_t images_bytes, uint32_t magic, int level,
+                                    fourmc_lines_wr_item* items /*host*/, uint32_t n, void* stream);
+int fourmc_gpu_bstreams_write_lines(const fourmc_lines_src* src, void* d_images, uint64_t images_bytes, int codec, int level,
+                                    fourmc_lines_wr_item* items /*host*/, uint32_t n, void* stream);
 
 /* ---- host-buffer conveniences with the reference's per-block signatures ------------------- */
 /* These stage one block through HBM (H2D, one launch, D2H).  They exist so the JNI entry points
