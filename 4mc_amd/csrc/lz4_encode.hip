@@ -16,7 +16,10 @@
 //   * "dense window": lane l takes position sp+l whatever role the walk will give it, prepares
 //     candidate / 4-byte test / match extents against the table as it stands (its own bytes come from an LDS ring
 //     that runs a KiB ahead of the cursor - 32-bit table only, in the scoreboard's memory); lanes sharing a
-//     slot are found on the table itself (lane tags, atomic max); a scalar walk of one readlane
+//     slot are found on the table itself (lane tags, atomic max; a second lane's look at its predecessor's bytes is a
+//     permute asked for between the tag rounds, so it returns under a wait the table phase pays anyway); where the walk
+//     goes from a lane, as a probe and as a chosen hit, is worked out for all lanes with two independent permutes of
+//     one register under one wait; a scalar walk of one readlane
 //     per sequence chooses the hit lanes; sizes and output positions of the chosen sequences are
 //     then computed by all lanes at once and their records (lz4emit.h) written in one store, and the
 //     visited lanes enter the table (latest position of a slot wins);
@@ -344,8 +347,15 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 // in front of one the walk reaches as a probe).  16-bit table: a folded min-scoreboard, first lane
                 // clean, all others dirty.
                 bool dirty, second = false; int pred = 0;
+                uint32_t wpred = 0;                                     // the four bytes at the predecessor's position
                 if (U32TAB) {
                     pred = 63 - int(tag & 63);
+                    // A second lane of a slot compares its bytes with its predecessor's further down.  They are the window's own
+                    // and `pred` is known here, so the permute is asked for now: it comes back under the second tag round's wait
+                    // (or, in a window without one, while the candidates' bytes are still on their way) instead of behind the
+                    // compares.  Every lane takes part: the source lane must be active.  The barrier keeps it here.
+                    wpred = __shfl(q0.d1, pred);
+                    __builtin_amdgcn_sched_barrier(0);
                     const bool first = pred == lane;
                     dirty = false;
                     if (__ballot(!first)) {
@@ -410,7 +420,6 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 }
                 // A second lane of a slot sees its predecessor's position instead of the table entry if the walk made the
                 // predecessor a probe.  Hit on neither: an ordinary probe.  Otherwise it is decided when the walk gets there.
-                const uint32_t wpred = __shfl(q0.d1, pred);              // (every lane takes part: the source lane must be active)
                 const bool hitA = second && wpred == q0.d1;
                 const unsigned long long m_cond = __ballot(second && (hitA || hit));
                 const unsigned long long m_hit = __ballot(hit) & ~m_cond, m_dirty = __ballot(dirty), m_slow = __ballot(hit && slow);
@@ -443,22 +452,32 @@ __device__ int lz4_encode_block(const uint8_t* src, uint8_t* dst, const int n, c
                 // Where the walk goes from lane l when a search starts there with nothing pending (anchor == l), for
                 // every l at once: the end of the first hit at or after l (| that hit lane << 8), or 0x8000 | the lane
                 // it has to stop at (64: none).  The scalar walk below is then one readlane per sequence.
-                uint32_t nxt;
+                // The same for a lane as a chosen HIT (nextE, fin): where the walk lands behind its match (`land`), and what it
+                // does there - which is nxt[land].  Every lane holds the event masks, so it finds the first event at or after
+                // `land` by itself and reads that lane's `info` directly: two permutes of one register, asked for back to back
+                // and waited for once (a permute of `nxt` would wait for the first one's answer).  Whether the event lane is a
+                // stop lane is read from `stop2` here and does not travel.
+                uint32_t nxt, nextE, fin;
                 {
-                    const unsigned long long shm = (m_hit | stop2) >> lane;
-                    const int E = lane + (shm ? __builtin_ctzll(shm) : 0);
-                    const uint32_t infE = __shfl(info | (uint32_t((stop2 >> lane) & 1) << 17), E);
-                    const bool term = !shm || ((infE >> 17) & 1) || (((infE >> 8) & 7) == 5 && E - lane >= 5);
-                    nxt = term ? (0x8000u | (shm ? uint32_t(E) : 64u)) : ((infE & 255) | (uint32_t(E) << 8));
-                }
-                // the same for a lane as a chosen HIT: where the walk lands behind its match, and what it does there
-                uint32_t nextE, fin;
-                {
-                    const uint32_t land = info & 255;
-                    const uint32_t nl = __shfl(nxt, int(land & 63));
-                    const bool endn = land >= 64 || (nl & 0x8000u);
-                    nextE = endn ? uint32_t(lane) : (nl >> 8) & 63;
-                    fin = land >= 64 ? 0x4000u : nl;
+                    // d: distance to the first event at or after a lane (64: none), ds: to the first stop lane.  The stop lanes
+                    // are events, so ds == d says "a stop lane, or nothing" - without a branch.
+                    const unsigned long long evs = m_hit | stop2;
+                    const uint32_t land = info & 255, la = land & 63;
+                    const uint32_t d = uint32_t(__builtin_ctzg(evs >> lane, 64)), d2 = uint32_t(__builtin_ctzg(evs >> la, 64));
+                    const uint32_t E = uint32_t(lane) + d, E2 = la + d2;                      // the event's lane (64 and up: none)
+                    uint32_t infE = __shfl(info, int(E & 63)), infE2 = __shfl(info, int(E2 & 63));
+                    __builtin_amdgcn_sched_barrier(0);                  // both asked for; what needs neither answer follows
+                    const uint32_t ds = uint32_t(__builtin_ctzg(stop2 >> lane, 64)), ds2 = uint32_t(__builtin_ctzg(stop2 >> la, 64));
+                    const uint32_t endE = 0x8000u | min(E, 64u), endE2 = 0x8000u | min(E2, 64u);
+                    const bool far = d >= 5, far2 = d2 >= 5, nothing = ds == d, nothing2 = ds2 == d2, out = land >= 64;
+                    __builtin_amdgcn_sched_barrier(0);
+                    asm volatile("" : "+v"(infE), "+v"(infE2));         // both answers are used here: the one wait for the two
+                    const uint32_t goE = (infE & 255) | (E << 8), goE2 = (infE2 & 255) | (E2 << 8);
+                    const bool term = nothing | ((((infE >> 8) & 7) == 5) & far), term2 = nothing2 | ((((infE2 >> 8) & 7) == 5) & far2);
+                    nxt = term ? endE : goE;
+                    const uint32_t nl = term2 ? endE2 : goE2;           // nxt[land]
+                    nextE = (out | term2) ? uint32_t(lane) : E2;
+                    fin = out ? 0x4000u : nl;                           // (a match that leaves the window: nothing behind it is read)
                 }
                 K2PH(pt_prep);
                 for (;;) {

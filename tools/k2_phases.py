@@ -2,7 +2,10 @@
 """Per-phase cycle split of the LZ4 fast encoder (K2) per S-mix block class.  Uses a side build of the library
 compiled with -DK2_PROF (cycle counters written behind the compressed payload):
     make -C 4mc_amd/csrc prof      # -> 4mc_amd/lib/libhadoop-4mc-prof.so
-    FOURMC_LIB=4mc_amd/lib/libhadoop-4mc-prof.so python tools/k2_phases.py"""
+    FOURMC_LIB=4mc_amd/lib/libhadoop-4mc-prof.so python tools/k2_phases.py
+Every marker waits for everything outstanding, so a phase holds the round trips asked for in it: `table` the tag rounds and the
+permute of the predecessor's bytes (asked for behind the first tag; before r14 it was asked for, and counted, in `gather`), `gather`
+the rest of the candidates' trip and the compares, `prep` the two permutes of `info` under one wait (before r14: two dependent ones)."""
 import importlib, sys, os
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
