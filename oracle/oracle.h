@@ -238,6 +238,59 @@ int64_t orc_zstd_compress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap
 int64_t orc_zstd_compress_ex(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, int level, orc_trace* trace);
 int     orc_codec_zstd1(void* ctx, const uint8_t* src, int n, uint8_t* dst, int cap);
 
+/* ZSTD_initCStream(level) + ZSTD_compressStream + ZSTD_endStream for levels 1..4 (what ZstCodec writes, jniZStreamCompressor.c:86-137):
+ * the frame without a content size, blocks of 128 KiB out of an input ring of window + 128 KiB bytes (zstd_compress.c:1591-1594,
+ * :5517-5519), the window bookkeeping of ZSTD_window_update / ZSTD_window_enforceMaxDist (zstd_compress_internal.h:1177-1212,
+ * :1086-1122), the ext-dict parsers (zstd_fast.c:684-935, zstd_double_fast.c:592-734) and the prefix-only parsers with
+ * ZSTD_getLowestPrefixIndex's repeat-offset limit, and the block entropy stage of orc_zstd_compress.  The source is read at its
+ * stream positions (both ring segments are contiguous there); every decision is taken on the reference's indices.
+ * Returns the frame size, -70 when `cap` is too small (the reference never fails on output: give 2 n + 4096), ORC_ZSTD_UNSUPPORTED
+ * for another level.  `trace` (NULL: none) never changes a byte; `mutate` (ORC_ZMUT_*, 0: none) takes ONE decision wrongly, for
+ * the test that shows the catalogue of tests/zst_write_shapes.py tells each apart.
+ * Tables (int32 rows, positions are stream offsets, indices are positions + 2):
+ *   ORC_TR_BLOCK   ORC_ZSTR_BLOCK_WORDS, ORC_ZSB_* names the words
+ *   ORC_TR_SEARCH  ORC_ZSTR_SEARCH_WORDS, one row per search of an ext-dict parser: block, first position, pairs (fast) or positions
+ *                  (dfast) probed before the event, the step at the event, ORC_ZSARM_* of the event (0: the block ended), bytes from the
+ *                  anchor to the event, the least number of probes between two probes of this search that fell into one table slot
+ *                  (0: none within 63 probes), 1 when such a pair at most 15 probes apart also holds equal words, 1 when the two
+ *                  positions of one pair fell into one slot (fast), the number of probes made when the step first grew inside the search (0: it did not)
+ *   ORC_TR_ARM     ORC_ZSTR_SEQ_WORDS, one row per sequence: block, ORC_ZSARM_*, the match's start in the input (after the catch-up),
+ *                  the candidate's index (a repeat-offset arm: the repeat index), segment the match starts in (0 ext, 1 prefix), 1 when
+ *                  its forward count crosses the wrap point, catch-up length, ORC_ZSTOP_*, match length, bytes from the match's end to the
+ *                  block's end, 1 when the candidate was entered by this same search, the turn of the behind-match loop (from 1).
+ *                  A prefix-only block gives block, ORC_ZSARM_PFX_*, start, off_base, 1, 0, 0, 0, match length, 0, 0, 0.
+ *   ORC_TR_EMIT    ORC_ZSTR_REP_WORDS, one row per repeat-offset test of an ext-dict parser that found equal bytes: block, site (0 the
+ *                  search, 1 behind a match), the tested position, repeat index - prefixStartIndex, 1 accepted / 0 refused by the rule;
+ *                  and one row per table entry at or up to 7 below the candidate bound that holds the probe's four bytes and is refused for
+ *                  its index: block, site 2, the probing position, entry - dictStartIndex (0: dfast alone), 0 */
+enum { ORC_ZSTR_SEARCH_WORDS = 10, ORC_ZSTR_BLOCK_WORDS = 20, ORC_ZSTR_SEQ_WORDS = 12, ORC_ZSTR_REP_WORDS = 5 };
+enum { ORC_ZSB_NUMBER = 0, ORC_ZSB_START, ORC_ZSB_LEN, ORC_ZSB_MODE /* ORC_ZSMODE_* */, ORC_ZSB_DICT_IDX, ORC_ZSB_PFX_IDX,
+       ORC_ZSB_REP_IN /* 2 words */, ORC_ZSB_REP_OUT = ORC_ZSB_REP_IN + 2 /* 2 words */, ORC_ZSB_ZEROED = ORC_ZSB_REP_OUT + 2 /* bit 0 rep1, bit 1 rep2 */,
+       ORC_ZSB_RESTORED /* bit 0: rep1 <- saved1, bit 1: rep2 <- saved2, bit 2: rep2 <- saved1 */, ORC_ZSB_TYPE /* 0 raw, 1 rle, 2 compressed */,
+       ORC_ZSB_NSEQ, ORC_ZSB_IN_CYCLE /* k mod m */, ORC_ZSB_CYCLE /* k / m */, ORC_ZSB_DEV_MAX, ORC_ZSB_REF_MAX /* prefix-only blocks */,
+       ORC_ZSB_MAX_REP /* ext blocks of fast */, ORC_ZSB_LAST };
+enum { ORC_ZSMODE_SHORT = 0 /* fewer than 7 bytes: not parsed */, ORC_ZSMODE_PREFIX, ORC_ZSMODE_PREFIX_CARRY /* an offset in (dev_max, ref_max] came in */,
+       ORC_ZSMODE_EXT, ORC_ZSMODE_HANDOVER /* ext-dict mode, dictStartIndex == prefixStartIndex: the prefix-only parser's */, ORC_ZSMODE_HANDOVER_CARRY };
+enum { ORC_ZSARM_REP = 1 /* fast: at ip2; dfast: at ip + 1 */, ORC_ZSARM_HIT_IP0, ORC_ZSARM_HIT_IP1, ORC_ZSARM_LONG, ORC_ZSARM_SHORT, ORC_ZSARM_SHORT_THEN_LONG,
+       ORC_ZSARM_REP_LOOP /* behind a match */, ORC_ZSARM_PFX_REP, ORC_ZSARM_PFX_HIT };
+enum { ORC_ZSTOP_NONE = 0 /* no catch-up is made (repeat-offset arms) */, ORC_ZSTOP_ANCHOR, ORC_ZSTOP_LOW_EQUAL /* the segment's low end, equal bytes in front */,
+       ORC_ZSTOP_LOW, ORC_ZSTOP_MISMATCH };
+enum { ORC_ZMUT_NONE = 0,
+       ORC_ZMUT_CATCHUP_PFX,      /* the catch-up ignores the segment's low end, prefix source */
+       ORC_ZMUT_CATCHUP_EXT,      /* ... ext source */
+       ORC_ZMUT_FAST_REP_3,       /* fast search: (u32)(pfx - rep_idx) >= 3 */
+       ORC_ZMUT_AFTER_REP_4,      /* behind a match: (u32)(pfx - 1 - rep_idx2) >= 4 */
+       ORC_ZMUT_FAST_STRICT,      /* fast: candidate > dictStartIndex */
+       ORC_ZMUT_DFAST_LOOSE,      /* dfast: candidate >= dictStartIndex */
+       ORC_ZMUT_MAXREP_GT,        /* ext block start: offset > max_rep is dropped (not >=) */
+       ORC_ZMUT_NO_RESTORE,       /* the saved repeat offsets are not put back */
+       ORC_ZMUT_HANDOVER_EXT,     /* the hand-over block goes to the ext parser */
+       ORC_ZMUT_DICT_FROM_START,  /* dictStartIndex from the block's start */
+       ORC_ZMUT_CARRY_DROPPED,    /* a carried offset above dev_max is dropped */
+       ORC_ZMUT_NO_UPGRADE,       /* dfast: no long match at ip + 1 */
+       ORC_ZMUT_COUNT };
+int64_t orc_zstd_stream_compress_ex(const uint8_t* src, size_t n, int level, uint8_t* dst, size_t cap, orc_trace* trace, int mutate);
+
 /* codec adaptors with the orc_block_codec_fn shape (ctx unused) */
 int orc_codec_lz4_fast(void* ctx, const uint8_t* src, int n, uint8_t* dst, int cap);
 int orc_codec_lz4_decode(void* ctx, const uint8_t* src, int n, uint8_t* dst, int cap);

@@ -801,6 +801,11 @@ typedef struct {
     zseq*     seq;  size_t nseq;
     uint8_t*  lit;  size_t nlit;
     orc_trace* tr;  int32_t blk;  /* the trace (NULL: none) and the inner block's number */
+    /* the streaming compressor alone (orc_zstd_stream_compress_ex); all 0 in a one-shot frame */
+    uint32_t   stream_dl;         /* window.dictLimit while a prefix-only parser runs on a streamed block: the repeat-offset limit and the
+                                     prefix start are ZSTD_getLowestPrefixIndex's, measured from it (0: the one-shot frame's, from the block's end) */
+    int        mutate;            /* ORC_ZMUT_* */
+    orc_trace* str;               /* the stream's trace: a prefix-only block gives one SEQ row per sequence through store_seq */
 } zmatch;
 
 /* trace rows (oracle.h: ORC_ZTR_*): nothing but these three helpers writes one, and none of them touches the encoder's state */
@@ -837,6 +842,10 @@ static void store_seq(zmatch* m, const uint8_t* s, size_t anchor, size_t ll, uin
     m->seq[m->nseq].ll = (uint32_t)ll; m->seq[m->nseq].ml = (uint32_t)(ml - 3); m->seq[m->nseq].off = off_base;
     m->nseq++;
     ztr_emit(m, anchor, ll, off_base, ml);
+    if (m->str && m->stream_dl) {
+        const int32_t row[ORC_ZSTR_SEQ_WORDS] = {m->blk, off_base <= 3 ? ORC_ZSARM_PFX_REP : ORC_ZSARM_PFX_HIT, (int32_t)(anchor + ll), (int32_t)off_base, 1, 0, 0, 0, (int32_t)ml, 0, 0, 0};
+        orc_tr_put(m->str, ORC_TR_ARM, row, ORC_ZSTR_SEQ_WORDS);
+    }
 }
 
 /* ZSTD_compressBlock_fast_noDict_generic over s[start, end); returns the last-literals length */
@@ -847,7 +856,13 @@ static size_t fast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t st
     const uint32_t mls = (m->p.mml >= 5 && m->p.mml <= 7) ? m->p.mml : 4;
     const size_t step0 = m->p.tlen > 1 ? (size_t)m->p.tlen + 1 : 2;
     const uint32_t end_idx = (uint32_t)end + 2;
-    const uint32_t prefix_idx = end_idx - 2 > wsize ? end_idx - wsize : 2;     /* dictLimit after enforceMaxDist */
+    /* A streamed block (stream_dl != 0) measures both the prefix start and the repeat-offset limit from window.dictLimit, as
+     * ZSTD_getLowestPrefixIndex does; a one-shot frame (stream_dl == 0) keeps its rule: both from the block's end.  The mutant
+     * ORC_ZMUT_CARRY_DROPPED takes the repeat-offset limit alone (dl, used for `low` below) by the one-shot rule. */
+    const uint32_t dl = m->mutate == ORC_ZMUT_CARRY_DROPPED ? 0 : m->stream_dl;
+    const uint32_t from_end = end_idx - 2 > wsize ? end_idx - wsize : 2;
+    const uint32_t from_dict_limit = end_idx - m->stream_dl > wsize ? end_idx - wsize : m->stream_dl;
+    const uint32_t prefix_idx = m->stream_dl ? from_dict_limit : from_end;     /* dictLimit after enforceMaxDist */
     const size_t prefix = prefix_idx - 2;
     const int64_t ilimit = (int64_t)end - 8;       /* may be negative for a 7-byte input: compared as signed */
     size_t anchor = start, ip0 = start, ip1, ip2, ip3, step, next_step, match0, mlen;
@@ -857,7 +872,8 @@ static size_t fast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t st
     ip0 += (ip0 == prefix);
     {
         const uint32_t cur = (uint32_t)ip0 + 2;
-        const uint32_t low = cur - prefix_idx > wsize ? cur - wsize : prefix_idx;
+        const uint32_t floor_idx = dl ? dl : prefix_idx;                 /* streamed: window.dictLimit; one-shot (and the mutant): the prefix start */
+        const uint32_t low = cur - floor_idx > wsize ? cur - wsize : floor_idx;
         const uint32_t max_rep = cur - low;
         if (rep2 > max_rep) { saved2 = rep2; rep2 = 0; }
         if (rep1 > max_rep) { saved1 = rep1; rep1 = 0; }
@@ -928,6 +944,7 @@ static size_t fast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t st
 cleanup:
     saved2 = (saved1 != 0 && rep1 != 0) ? saved1 : saved2;
     if ((saved1 && !rep1) || (saved2 && !rep2)) ztr_arm(m, ORC_ZARM_REP_RESTORED, end, (saved1 && !rep1) + 2 * (saved2 && !rep2));
+    if (m->mutate == ORC_ZMUT_NO_RESTORE) saved1 = saved2 = 0;
     rep[0] = rep1 ? rep1 : saved1;
     rep[1] = rep2 ? rep2 : saved2;
     return end - anchor;
@@ -941,7 +958,13 @@ static size_t dfast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t s
     const uint32_t hl_log = m->p.hlog, hs_log = m->p.clog, wsize = 1u << m->p.wlog;
     const uint32_t mls = (m->p.mml >= 5 && m->p.mml <= 7) ? m->p.mml : 4;
     const uint32_t end_idx = (uint32_t)end + 2;
-    const uint32_t prefix_idx = end_idx - 2 > wsize ? end_idx - wsize : 2;
+    /* A streamed block (stream_dl != 0) measures both the prefix start and the repeat-offset limit from window.dictLimit, as
+     * ZSTD_getLowestPrefixIndex does; a one-shot frame (stream_dl == 0) keeps its rule: both from the block's end.  The mutant
+     * ORC_ZMUT_CARRY_DROPPED takes the repeat-offset limit alone (dl, used for `low` below) by the one-shot rule. */
+    const uint32_t dl = m->mutate == ORC_ZMUT_CARRY_DROPPED ? 0 : m->stream_dl;
+    const uint32_t from_end = end_idx - 2 > wsize ? end_idx - wsize : 2;
+    const uint32_t from_dict_limit = end_idx - m->stream_dl > wsize ? end_idx - wsize : m->stream_dl;
+    const uint32_t prefix_idx = m->stream_dl ? from_dict_limit : from_end;
     const size_t prefix = prefix_idx - 2;
     const int64_t ilimit = (int64_t)end - 8;
     size_t anchor = start, ip = start, ip1, step, next_step, mlen, match;
@@ -950,7 +973,8 @@ static size_t dfast_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t s
     ip += (ip == prefix);
     {
         const uint32_t c = (uint32_t)ip + 2;
-        const uint32_t low = c - prefix_idx > wsize ? c - wsize : prefix_idx;
+        const uint32_t floor_idx = dl ? dl : prefix_idx;                 /* streamed: window.dictLimit; one-shot (and the mutant): the prefix start */
+        const uint32_t low = c - floor_idx > wsize ? c - wsize : floor_idx;
         const uint32_t max_rep = c - low;
         if (rep2 > max_rep) { saved2 = rep2; rep2 = 0; }
         if (rep1 > max_rep) { saved1 = rep1; rep1 = 0; }
@@ -1034,6 +1058,7 @@ cleanup:
 #undef HL
     saved2 = (saved1 != 0 && rep1 != 0) ? saved1 : saved2;
     if ((saved1 && !rep1) || (saved2 && !rep2)) ztr_arm(m, ORC_ZARM_REP_RESTORED, end, (saved1 && !rep1) + 2 * (saved2 && !rep2));
+    if (m->mutate == ORC_ZMUT_NO_RESTORE) saved1 = saved2 = 0;
     rep[0] = rep1 ? rep1 : saved1;
     rep[1] = rep2 ? rep2 : saved2;
     return end - anchor;
@@ -1346,6 +1371,7 @@ static size_t lazy_block(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t st
 #undef SEARCH
     saved2 = (saved1 != 0 && rep1 != 0) ? saved1 : saved2;
     if ((saved1 && !rep1) || (saved2 && !rep2)) ztr_arm(m, ORC_ZARM_REP_RESTORED, end, (saved1 && !rep1) + 2 * (saved2 && !rep2));
+    if (m->mutate == ORC_ZMUT_NO_RESTORE) saved1 = saved2 = 0;
     rep[0] = rep1 ? rep1 : saved1;
     rep[1] = rep2 ? rep2 : saved2;
     return end - anchor;
@@ -1736,7 +1762,7 @@ int64_t orc_zstd_compress_ex(const uint8_t* src, size_t n, uint8_t* dst, size_t 
         opt.hlog3 = p.mml == 3 ? (p.wlog < 17 ? p.wlog : 17) : 1;       /* ZSTD_reset_matchState: hashLog3 = MIN(ZSTD_HASHLOG3_MAX, windowLog) */
         opt.hash3 = (uint32_t*)calloc((size_t)1 << opt.hlog3, 4);
     }
-    m.tr = trace; m.blk = 0;
+    m.tr = trace; m.blk = 0; m.stream_dl = 0; m.mutate = 0; m.str = NULL;
     m.next_to_update = m.low_limit = m.dict_limit = 2;                /* ZSTD_WINDOW_START_INDEX */
     memset(m.hash_cache, 0, sizeof m.hash_cache);
     m.seq = (zseq*)malloc((BLOCK_MAX / 3 + 1) * sizeof(zseq));
@@ -1814,6 +1840,416 @@ int64_t orc_zstd_compress_ex(const uint8_t* src, size_t n, uint8_t* dst, size_t 
         pos += len; first = 0; m.blk++;
     }
     free(m.table); free(m.small); free(m.tags); free(m.seq); free(m.lit); free(llc); free(opt.node); free(opt.match); free(opt.hash3);
+    return result < 0 ? result : (int64_t)o;
+}
+
+/* ------------------------------------------------------------------------------------------------ streamed frames
+ * ZSTD_initCStream(level) + ZSTD_compressStream + ZSTD_endStream (oracle.h: orc_zstd_stream_compress_ex). */
+typedef struct {            /* what a search of an ext-dict parser probed, for the trace alone */
+    uint32_t ha[64], hb[64]; uint64_t w[64];
+    uint32_t n, share_dist, share_equal, pair_same, step_grew; size_t first;
+} zprobes;
+
+static void zs_search_begin(zprobes* q, size_t first) { q->n = 0; q->share_dist = 0; q->share_equal = 0; q->pair_same = 0; q->step_grew = 0; q->first = first; }
+/* one probe: two table slots (fast: the pair's two positions in one table; dfast: the long and the short table's, told apart by bit 31) */
+static void zs_probe(zprobes* q, uint32_t ha, uint32_t hb, uint64_t word)
+{
+    uint32_t j;
+    for (j = 1; j <= q->n && j < 64; j++) {
+        const uint32_t k = (q->n - j) & 63;
+        if (q->ha[k] == ha || q->hb[k] == hb || q->ha[k] == hb || q->hb[k] == ha) {
+            if (!q->share_dist || j < q->share_dist) q->share_dist = j;
+            if (j <= 15 && q->w[k] == word) q->share_equal = 1;
+        }
+    }
+    q->ha[q->n & 63] = ha; q->hb[q->n & 63] = hb; q->w[q->n & 63] = word; q->n++;
+}
+static void zs_search_end(const zmatch* m, const zprobes* q, uint32_t step, int arm, size_t from_anchor)
+{
+    if (m->str) {
+        const int32_t row[ORC_ZSTR_SEARCH_WORDS] = {m->blk, (int32_t)q->first, (int32_t)q->n, (int32_t)step, arm, (int32_t)from_anchor,
+                                                    (int32_t)q->share_dist, (int32_t)q->share_equal, (int32_t)q->pair_same, (int32_t)q->step_grew};
+        orc_tr_put(m->str, ORC_TR_SEARCH, row, ORC_ZSTR_SEARCH_WORDS);
+    }
+}
+static void zs_rep_test(const zmatch* m, const uint8_t* s, int site, size_t at, uint32_t rix, uint32_t rep, uint32_t pfx_idx, int accepted)
+{
+    if (m->str && rep > 0 && rix >= 2 && rix < at + 2 && rd32(s + rix - 2) == rd32(s + at)) {
+        const int32_t row[ORC_ZSTR_REP_WORDS] = {m->blk, site, (int32_t)at, (int32_t)rix - (int32_t)pfx_idx, accepted};
+        orc_tr_put(m->str, ORC_TR_EMIT, row, ORC_ZSTR_REP_WORDS);
+    }
+}
+/* a table entry at or below the parser's candidate bound that holds the probe's four bytes: read and refused */
+static void zs_cand_refused(const zmatch* m, const uint8_t* s, size_t at, uint32_t idx, uint32_t dict_idx)
+{
+    if (m->str && idx >= 2 && idx <= dict_idx && idx + 8 > dict_idx && rd32(s + idx - 2) == rd32(s + at)) {
+        const int32_t row[ORC_ZSTR_REP_WORDS] = {m->blk, 2, (int32_t)at, (int32_t)idx - (int32_t)dict_idx, 0};
+        orc_tr_put(m->str, ORC_TR_EMIT, row, ORC_ZSTR_REP_WORDS);
+    }
+}
+static void zs_seq(const zmatch* m, int arm, size_t ip, uint32_t cand_idx, uint32_t pfx_idx, size_t mlen, size_t back, int stop, size_t end, int own, uint32_t turn)
+{
+    if (m->str) {
+        const size_t mpos = cand_idx - 2 - back;                /* the match's first byte after the catch-up */
+        const int32_t row[ORC_ZSTR_SEQ_WORDS] = {m->blk, arm, (int32_t)ip, (int32_t)cand_idx, cand_idx >= pfx_idx, cand_idx < pfx_idx && mpos + mlen > pfx_idx - 2,
+                                                 (int32_t)back, stop, (int32_t)mlen, (int32_t)(end - ip - mlen), own, (int32_t)turn};
+        orc_tr_put(m->str, ORC_TR_ARM, row, ORC_ZSTR_SEQ_WORDS);
+    }
+}
+
+/* the backward catch-up of a table match (zstd_fast.c:879-892, zstd_double_fast.c:654-658): it stays in the segment the match
+ * starts in.  Returns the bytes walked back; *stop: ORC_ZSTOP_*. */
+static size_t zs_catch_up(const zmatch* m, const uint8_t* s, size_t* ip, size_t* match, size_t anchor, uint32_t cand_idx, uint32_t dict_idx, uint32_t pfx_idx, int* stop)
+{
+    const int in_pfx = cand_idx >= pfx_idx;
+    size_t low = (size_t)(in_pfx ? pfx_idx : dict_idx) - 2, back = 0;
+    if (m->mutate == (in_pfx ? ORC_ZMUT_CATCHUP_PFX : ORC_ZMUT_CATCHUP_EXT)) low = 0;
+    while (*ip > anchor && *match > low && s[*ip - 1] == s[*match - 1]) { (*ip)--; (*match)--; back++; }
+    *stop = *ip == anchor ? ORC_ZSTOP_ANCHOR : *match > low ? ORC_ZSTOP_MISMATCH : (*match > 0 && s[*ip - 1] == s[*match - 1]) ? ORC_ZSTOP_LOW_EQUAL : ORC_ZSTOP_LOW;
+    return back;
+}
+
+/* ZSTD_compressBlock_fast_extDict_generic (zstd_fast.c:684-935) over s[start, end); dict_idx = dictStartIndex < pfx_idx = prefixStartIndex */
+static size_t fast_block_ext(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t start, size_t end, uint32_t dict_idx, uint32_t pfx_idx, int32_t* brow)
+{
+    uint32_t* const tab = m->table;
+    const uint32_t hlog = m->p.hlog;
+    const uint32_t mls = (m->p.mml >= 5 && m->p.mml <= 7) ? m->p.mml : 4;
+    const size_t step0 = (size_t)m->p.tlen + !m->p.tlen + 1;
+    const int64_t ilimit = (int64_t)end - 8;
+    const uint64_t wmask = mls >= 8 ? ~0ull : (1ull << (8 * mls)) - 1;
+    size_t anchor = start, ip0 = start, ip1, ip2, ip3, step, next_step, match0, mlen, back;
+    uint32_t rep1 = rep[0], rep2 = rep[1], saved1 = 0, saved2 = 0, cur0 = 0, idx, off_base, h0, h1, cand;
+    int arm, stop, own;
+    zprobes q;
+    {   /* :739-743 */
+        const uint32_t max_rep = (uint32_t)ip0 + 2 - dict_idx;
+        const int gt = m->mutate == ORC_ZMUT_MAXREP_GT;
+        if (gt ? rep2 > max_rep : rep2 >= max_rep) { saved2 = rep2; rep2 = 0; }
+        if (gt ? rep1 > max_rep : rep1 >= max_rep) { saved1 = rep1; rep1 = 0; }
+        brow[ORC_ZSB_MAX_REP] = (int32_t)max_rep;
+        brow[ORC_ZSB_ZEROED] = (saved1 != 0) + 2 * (saved2 != 0);
+    }
+    for (;;) {                                     /* _start */
+        step = step0; next_step = ip0 + 128;
+        ip1 = ip0 + 1; ip2 = ip0 + step; ip3 = ip2 + 1;
+        if ((int64_t)ip3 >= ilimit) break;
+        zs_search_begin(&q, ip0);
+        h0 = zhash(s + ip0, hlog, mls); h1 = zhash(s + ip1, hlog, mls);
+        idx = tab[h0];
+        for (;;) {
+            {   /* :767-795, the repeat offset at ip2 */
+                const uint32_t rix = (uint32_t)ip2 + 2 - rep1;
+                const int ok = ((uint32_t)(pfx_idx - rix) >= (m->mutate == ORC_ZMUT_FAST_REP_3 ? 3u : 4u)) & (rep1 > 0);
+                const uint32_t rval = (ok && rix >= 2) ? rd32(s + rix - 2) : rd32(s + ip2) ^ 1;
+                if (m->str) {
+                    if (h0 == h1) q.pair_same = 1;
+                    zs_probe(&q, h0, h1, rd64(s + ip0) & wmask);
+                    zs_rep_test(m, s, 0, ip2, rix, rep1, pfx_idx, ok);
+                }
+                cur0 = (uint32_t)ip0 + 2;
+                tab[h0] = cur0;
+                if (rd32(s + ip2) == rval) {
+                    ip0 = ip2; match0 = rix - 2;
+                    mlen = s[ip0 - 1] == s[match0 - 1];
+                    ip0 -= mlen; match0 -= mlen;
+                    off_base = 1; back = mlen; mlen += 4;
+                    arm = ORC_ZSARM_REP; cand = rix; stop = ORC_ZSTOP_NONE; own = 0;
+                    goto match;
+                }
+            }
+            if ((m->mutate == ORC_ZMUT_FAST_STRICT ? idx > dict_idx : idx >= dict_idx) && idx < cur0 && rd32(s + idx - 2) == rd32(s + ip0)) { arm = ORC_ZSARM_HIT_IP0; goto offset; }   /* :797-806 */
+            if (m->mutate == ORC_ZMUT_FAST_STRICT ? idx <= dict_idx : idx < dict_idx) zs_cand_refused(m, s, ip0, idx, dict_idx);
+            idx = tab[h1]; h0 = h1; h1 = zhash(s + ip2, hlog, mls);
+            ip0 = ip1; ip1 = ip2; ip2 = ip3;
+            cur0 = (uint32_t)ip0 + 2;
+            tab[h0] = cur0;
+            if ((m->mutate == ORC_ZMUT_FAST_STRICT ? idx > dict_idx : idx >= dict_idx) && idx < cur0 && rd32(s + idx - 2) == rd32(s + ip0)) { arm = ORC_ZSARM_HIT_IP1; goto offset; }   /* :825-834 */
+            if (m->mutate == ORC_ZMUT_FAST_STRICT ? idx <= dict_idx : idx < dict_idx) zs_cand_refused(m, s, ip0, idx, dict_idx);
+            idx = tab[h1]; h0 = h1; h1 = zhash(s + ip2, hlog, mls);
+            ip0 = ip1; ip1 = ip2; ip2 = ip0 + step; ip3 = ip1 + step;
+            if (ip2 >= next_step) { step++; next_step += 128; if (!q.step_grew) q.step_grew = q.n; }
+            if ((int64_t)ip3 >= ilimit) { zs_search_end(m, &q, (uint32_t)step, 0, ip0 - anchor); goto cleanup; }
+        }
+    offset:                                        /* :875-892 */
+        match0 = idx - 2; cand = idx; own = match0 >= q.first;
+        rep2 = rep1; rep1 = cur0 - idx;
+        off_base = rep1 + 3;
+        back = zs_catch_up(m, s, &ip0, &match0, anchor, idx, dict_idx, pfx_idx, &stop);
+        mlen = 4 + back;
+    match:                                         /* :894-908; ZSTD_count_2segments over contiguous bytes is a plain count */
+        if (m->str) q.n--;                                                       /* (the event's own pair is not "before the event") */
+        zs_search_end(m, &q, (uint32_t)step, arm, ip0 + back - anchor);
+        mlen += count_eq(s, ip0 + mlen, match0 + mlen, end);
+        zs_seq(m, arm, ip0, cand, pfx_idx, mlen, back, stop, end, own, 0);
+        store_seq(m, s, anchor, ip0 - anchor, off_base, mlen);
+        ip0 += mlen; anchor = ip0;
+        if (ip1 < ip0) tab[h1] = (uint32_t)ip1 + 2;
+        if ((int64_t)ip0 <= ilimit) {                                            /* :911-932 */
+            uint32_t turn = 0;
+            tab[zhash(s + cur0, hlog, mls)] = cur0 + 2;
+            tab[zhash(s + ip0 - 2, hlog, mls)] = (uint32_t)ip0;
+            while ((int64_t)ip0 <= ilimit) {
+                const uint32_t rix2 = (uint32_t)ip0 + 2 - rep2;
+                const int ok = ((uint32_t)((pfx_idx - 1) - rix2) >= (m->mutate == ORC_ZMUT_AFTER_REP_4 ? 4u : 3u)) & (rep2 > 0);
+                size_t rlen;
+                zs_rep_test(m, s, 1, ip0, rix2, rep2, pfx_idx, ok);
+                if (!(ok && rix2 >= 2 && rd32(s + rix2 - 2) == rd32(s + ip0))) break;
+                rlen = count_eq(s, ip0 + 4, (size_t)rix2 - 2 + 4, end) + 4;
+                { const uint32_t t = rep2; rep2 = rep1; rep1 = t; }
+                zs_seq(m, ORC_ZSARM_REP_LOOP, ip0, rix2, pfx_idx, rlen, 0, ORC_ZSTOP_NONE, end, 0, ++turn);
+                store_seq(m, s, anchor, 0, 1, rlen);
+                tab[zhash(s + ip0, hlog, mls)] = (uint32_t)ip0 + 2;
+                ip0 += rlen; anchor = ip0;
+            }
+        }
+    }
+cleanup:                                           /* :859-873 */
+    {
+        const int moved = saved1 != 0 && rep1 != 0;                              /* rep1 was put aside and a new one found: the saved one is the second offset now */
+        brow[ORC_ZSB_RESTORED] = (!rep1 && saved1) + 2 * (!rep2 && saved2 && !moved) + 4 * (!rep2 && moved);
+        if (moved) saved2 = saved1;
+    }
+    if (m->mutate == ORC_ZMUT_NO_RESTORE) saved1 = saved2 = 0;
+    rep[0] = rep1 ? rep1 : saved1;
+    rep[1] = rep2 ? rep2 : saved2;
+    return end - anchor;
+}
+
+/* ZSTD_compressBlock_doubleFast_extDict_generic (zstd_double_fast.c:592-734) over s[start, end) */
+static size_t dfast_block_ext(zmatch* m, uint32_t rep[3], const uint8_t* s, size_t start, size_t end, uint32_t dict_idx, uint32_t pfx_idx)
+{
+    uint32_t* const tl = m->table; uint32_t* const ts = m->small;
+    const uint32_t hl_log = m->p.hlog, hs_log = m->p.clog;
+    const uint32_t mls = (m->p.mml >= 5 && m->p.mml <= 7) ? m->p.mml : 4;
+    const int64_t ilimit = (int64_t)end - 8;
+    const int loose = m->mutate == ORC_ZMUT_DFAST_LOOSE;
+    size_t anchor = start, ip = start;
+    uint32_t rep1 = rep[0], rep2 = rep[1];
+    zprobes q;
+    int searching = 0;
+#define HL(p_) ((uint32_t)((rd64(s + (p_)) * 0xCF1BBCDCB7A56463ull) >> (64 - hl_log)))
+#define VALID(i_, c_) ((loose ? (i_) >= dict_idx : (i_) > dict_idx) && (i_) < (c_))
+    while ((int64_t)ip < ilimit) {
+        const uint32_t hs = zhash(s + ip, hs_log, mls), hl = HL(ip);
+        const uint32_t midx = ts[hs], lidx = tl[hl];
+        const uint32_t curr = (uint32_t)ip + 2;
+        const uint32_t rix = curr + 1 - rep1;
+        const int rok = ((uint32_t)((pfx_idx - 1) - rix) >= 3) & (rep1 <= curr + 1 - dict_idx);
+        size_t mlen, match, back = 0;
+        uint32_t offset, cand;
+        int arm, stop = ORC_ZSTOP_NONE, own;
+        if (!searching) { zs_search_begin(&q, ip); searching = 1; }
+        if (m->str) { zs_probe(&q, hl, hs | 0x80000000u, rd64(s + ip)); zs_rep_test(m, s, 0, ip + 1, rix, rep1, pfx_idx, rok); }
+        ts[hs] = tl[hl] = curr;
+        if (rok && rix >= 2 && rd32(s + rix - 2) == rd32(s + ip + 1)) {          /* :644-650 */
+            mlen = count_eq(s, ip + 1 + 4, (size_t)rix - 2 + 4, end) + 4;
+            if (m->str) q.n--;
+            zs_search_end(m, &q, (uint32_t)((ip - anchor) >> 8) + 1, ORC_ZSARM_REP, ip + 1 - anchor);
+            ip++;
+            zs_seq(m, ORC_ZSARM_REP, ip, rix, pfx_idx, mlen, 0, ORC_ZSTOP_NONE, end, 0, 0);
+            store_seq(m, s, anchor, ip - anchor, 1, mlen);
+        } else {
+            const size_t found = ip;
+            if (VALID(lidx, curr) && rd64(s + lidx - 2) == rd64(s + ip)) {       /* :652-661 */
+                arm = ORC_ZSARM_LONG; cand = lidx; match = lidx - 2;
+                mlen = count_eq(s, ip + 8, match + 8, end) + 8;
+                offset = curr - lidx;
+            } else if (VALID(midx, curr) && rd32(s + midx - 2) == rd32(s + ip)) {   /* :663-686 */
+                const uint32_t h3 = HL(ip + 1), idx3 = tl[h3];
+                tl[h3] = curr + 1;
+                if (m->mutate != ORC_ZMUT_NO_UPGRADE && VALID(idx3, curr + 1) && rd64(s + idx3 - 2) == rd64(s + ip + 1)) {
+                    arm = ORC_ZSARM_SHORT_THEN_LONG; cand = idx3; match = idx3 - 2;
+                    mlen = count_eq(s, ip + 9, match + 8, end) + 8;
+                    ip++;
+                    offset = curr + 1 - idx3;
+                } else {
+                    arm = ORC_ZSARM_SHORT; cand = midx; match = midx - 2;
+                    mlen = count_eq(s, ip + 4, match + 4, end) + 4;
+                    offset = curr - midx;
+                }
+            } else {                                                             /* :688-690 */
+                const size_t nip = ip + ((ip - anchor) >> 8) + 1;
+                if (!VALID(midx, curr)) zs_cand_refused(m, s, ip, midx, dict_idx);
+                if (!VALID(lidx, curr) && lidx >= 2 && lidx <= dict_idx && rd64(s + lidx - 2) == rd64(s + ip)) zs_cand_refused(m, s, ip, lidx, dict_idx);
+                if (((nip - anchor) >> 8) != ((ip - anchor) >> 8) && !q.step_grew) q.step_grew = q.n;
+                ip = nip;
+                continue;
+            }
+            own = match >= q.first;
+            back = zs_catch_up(m, s, &ip, &match, anchor, cand, dict_idx, pfx_idx, &stop);
+            mlen += back;
+            if (m->str) q.n--;
+            zs_search_end(m, &q, (uint32_t)((found - anchor) >> 8) + 1, arm, found - anchor);
+            rep2 = rep1; rep1 = offset;
+            zs_seq(m, arm, ip, cand, pfx_idx, mlen, back, stop, end, own, 0);
+            store_seq(m, s, anchor, ip - anchor, offset + 3, mlen);
+        }
+        searching = 0;
+        ip += mlen; anchor = ip;
+        if ((int64_t)ip <= ilimit) {                                             /* :697-726 */
+            uint32_t turn = 0;
+            const uint32_t ins = curr + 2;                                       /* index; its position is curr */
+            tl[HL(curr)] = ins;
+            tl[HL(ip - 2)] = (uint32_t)ip;
+            ts[zhash(s + curr, hs_log, mls)] = ins;
+            ts[zhash(s + ip - 1, hs_log, mls)] = (uint32_t)ip + 1;
+            while ((int64_t)ip <= ilimit) {
+                const uint32_t cur2 = (uint32_t)ip + 2, rix2 = cur2 - rep2;
+                const int ok = ((uint32_t)((pfx_idx - 1) - rix2) >= (m->mutate == ORC_ZMUT_AFTER_REP_4 ? 4u : 3u)) & (rep2 <= cur2 - dict_idx);
+                size_t rlen;
+                zs_rep_test(m, s, 1, ip, rix2, rep2, pfx_idx, ok);
+                if (!(ok && rix2 >= 2 && rd32(s + rix2 - 2) == rd32(s + ip))) break;
+                rlen = count_eq(s, ip + 4, (size_t)rix2 - 2 + 4, end) + 4;
+                { const uint32_t t = rep2; rep2 = rep1; rep1 = t; }
+                zs_seq(m, ORC_ZSARM_REP_LOOP, ip, rix2, pfx_idx, rlen, 0, ORC_ZSTOP_NONE, end, 0, ++turn);
+                store_seq(m, s, anchor, 0, 1, rlen);
+                ts[zhash(s + ip, hs_log, mls)] = cur2;
+                tl[HL(ip)] = cur2;
+                ip += rlen; anchor = ip;
+            }
+        }
+    }
+    if (searching) zs_search_end(m, &q, (uint32_t)((ip - anchor) >> 8) + 1, 0, ip - anchor);
+#undef VALID
+#undef HL
+    rep[0] = rep1; rep[1] = rep2;                                                /* :728-730 */
+    return end - anchor;
+}
+
+int64_t orc_zstd_stream_compress_ex(const uint8_t* src, size_t n, int level, uint8_t* dst, size_t cap, orc_trace* trace, int mutate)
+{
+    zparams p;
+    zmatch m;
+    zentropy ent[2];
+    int cur = 0, first = 1;
+    size_t o = 0, pos = 0;
+    int64_t result = 0;
+    uint8_t *llc, *ofc, *mlc;
+    uint32_t wsize, ring_blocks, k = 0;
+    /* the window (zstd_compress_internal.h: ZSTD_window_t), ring addresses as integers: the ring is [0, window + 128 KiB) */
+    const int64_t far = -((int64_t)1 << 60);
+    int64_t base = far, dict_base = far, next_src = far + 2, at = 0, ring;
+    uint32_t low = 2, dct = 2;
+    if (level < 1 || level > 4) return ORC_ZSTD_UNSUPPORTED;
+    p = level_params(level, (size_t)1 << 30);                                    /* row 0 of the level: the source size is unknown */
+    wsize = 1u << p.wlog; ring = (int64_t)wsize + BLOCK_MAX; ring_blocks = wsize / BLOCK_MAX + 1;
+    if (cap < 9) return ERR_TOOSMALL;
+    dst[0] = 0x28; dst[1] = 0xB5; dst[2] = 0x2F; dst[3] = 0xFD; dst[4] = 0; dst[5] = (uint8_t)((p.wlog - 10) << 3);
+    o = 6;
+    memset(&m, 0, sizeof m);
+    m.p = p;
+    m.table = (uint32_t*)calloc((size_t)1 << p.hlog, 4);
+    m.small = (uint32_t*)calloc((size_t)1 << p.clog, 4);
+    m.str = trace; m.mutate = mutate;
+    m.seq = (zseq*)malloc((BLOCK_MAX / 3 + 1) * sizeof(zseq));
+    m.lit = (uint8_t*)malloc(BLOCK_MAX + 64);
+    llc = (uint8_t*)malloc(3 * (BLOCK_MAX / 3 + 1)); ofc = llc + BLOCK_MAX / 3 + 1; mlc = ofc + BLOCK_MAX / 3 + 1;
+    memset(ent, 0, sizeof ent);
+    ent[0].rep[0] = 1; ent[0].rep[1] = 4; ent[0].rep[2] = 8;
+    while (pos < n) {
+        const size_t len = n - pos < BLOCK_MAX ? n - pos : BLOCK_MAX;
+        const uint32_t last = len < BLOCK_MAX;                                   /* a full block is compressed before the end is known */
+        const zentropy* prev = &ent[cur];
+        zentropy* next = &ent[cur ^ 1];
+        const uint32_t start_idx = (uint32_t)pos + 2, end_idx = (uint32_t)(pos + len) + 2;
+        int64_t c = 0;
+        size_t bcap;
+        int32_t row[ORC_ZSTR_BLOCK_WORDS];
+        memset(row, 0, sizeof row);
+        {   /* ZSTD_window_update (:1177-1212) */
+            const int64_t ip = at;
+            if (ip != next_src) {                                                /* not contiguous: the prefix becomes the external dictionary */
+                const int64_t dist = next_src - base;
+                low = dct; dct = (uint32_t)dist; dict_base = base; base = ip - dist;
+                if (dct - low < 8) low = dct;
+            }
+            next_src = ip + (int64_t)len;
+            if (ip + (int64_t)len > dict_base + low && ip < dict_base + dct) {   /* the input overwrites the dictionary's low end */
+                const int64_t high = ip + (int64_t)len - dict_base;
+                low = high > (int64_t)dct ? dct : (uint32_t)high;
+            }
+            if ((int64_t)start_idx != ip - base) { result = ERR_GENERIC; break; }   /* (an index is a stream position + 2 throughout) */
+            if (start_idx > wsize) {                                             /* ZSTD_window_enforceMaxDist at the block's start (:1086-1122, zstd_compress.c:4015) */
+                if (low < start_idx - wsize) low = start_idx - wsize;
+                if (dct < low) dct = low;
+            }
+            at = ip + (int64_t)len;
+            if (at + BLOCK_MAX > ring) at = 0;                                   /* zstd_compress.c:5517-5519 */
+        }
+        row[ORC_ZSB_NUMBER] = (int32_t)k; row[ORC_ZSB_START] = (int32_t)pos; row[ORC_ZSB_LEN] = (int32_t)len; row[ORC_ZSB_MODE] = ORC_ZSMODE_SHORT;
+        row[ORC_ZSB_IN_CYCLE] = (int32_t)(k % ring_blocks); row[ORC_ZSB_CYCLE] = (int32_t)(k / ring_blocks); row[ORC_ZSB_LAST] = (int32_t)last;
+        row[ORC_ZSB_REP_IN] = row[ORC_ZSB_REP_OUT] = (int32_t)prev->rep[0]; row[ORC_ZSB_REP_IN + 1] = row[ORC_ZSB_REP_OUT + 1] = (int32_t)prev->rep[1];
+        if (cap - o < 3 + len + 64) { result = ERR_TOOSMALL; break; }
+        bcap = cap - o - 3;
+        m.blk = (int32_t)k;
+        if (len >= 7) {
+            uint8_t* const out = dst + o + 3;
+            size_t tail;
+            int64_t lsz, ssz;
+            int ext = low < dct;                                                 /* ZSTD_matchState_dictMode */
+            uint32_t dict_idx = 0, pfx_idx = 0;
+            m.nseq = 0; m.nlit = 0;
+            memcpy(next->rep, prev->rep, sizeof next->rep);
+            if (ext) {                                                           /* zstd_fast.c:697-704, :735-737 */
+                const uint32_t from = mutate == ORC_ZMUT_DICT_FROM_START ? start_idx : end_idx;
+                dict_idx = from - low > wsize ? from - wsize : low;              /* ZSTD_getLowestMatchIndex, no dictionary loaded */
+                pfx_idx = dct < dict_idx ? dict_idx : dct;
+                row[ORC_ZSB_MODE] = ORC_ZSMODE_EXT;
+                if (pfx_idx == dict_idx) { row[ORC_ZSB_MODE] = ORC_ZSMODE_HANDOVER; if (mutate != ORC_ZMUT_HANDOVER_EXT) ext = 0; }
+            } else row[ORC_ZSB_MODE] = ORC_ZSMODE_PREFIX;
+            if (ext) {
+                row[ORC_ZSB_DICT_IDX] = (int32_t)dict_idx; row[ORC_ZSB_PFX_IDX] = (int32_t)pfx_idx;
+                tail = p.strat == 2 ? dfast_block_ext(&m, next->rep, src, pos, pos + len, dict_idx, pfx_idx)
+                                    : fast_block_ext(&m, next->rep, src, pos, pos + len, dict_idx, pfx_idx, row);
+            } else {
+                const uint32_t prefix_idx = end_idx - dct > wsize ? end_idx - wsize : dct;       /* ZSTD_getLowestPrefixIndex(endIndex) */
+                const uint32_t cur_idx = start_idx + (start_idx == prefix_idx);
+                const uint32_t ref_max = cur_idx - (cur_idx - dct > wsize ? cur_idx - wsize : dct);
+                const uint32_t dev_max = cur_idx - (cur_idx - prefix_idx > wsize ? cur_idx - wsize : prefix_idx);
+                const int carry = (next->rep[0] > dev_max && next->rep[0] <= ref_max) || (next->rep[1] > dev_max && next->rep[1] <= ref_max);
+                row[ORC_ZSB_DICT_IDX] = (int32_t)dct; row[ORC_ZSB_PFX_IDX] = (int32_t)prefix_idx;
+                row[ORC_ZSB_DEV_MAX] = (int32_t)dev_max; row[ORC_ZSB_REF_MAX] = (int32_t)ref_max;
+                row[ORC_ZSB_ZEROED] = (next->rep[0] > ref_max) + 2 * (next->rep[1] > ref_max);
+                if (carry) row[ORC_ZSB_MODE]++;
+                m.stream_dl = dct;
+                tail = p.strat == 2 ? dfast_block(&m, next->rep, src, pos, pos + len) : fast_block(&m, next->rep, src, pos, pos + len);
+                m.stream_dl = 0;
+            }
+            memcpy(m.lit + m.nlit, src + pos + len - tail, tail); m.nlit += tail;
+            row[ORC_ZSB_NSEQ] = (int32_t)m.nseq;
+            row[ORC_ZSB_REP_OUT] = (int32_t)next->rep[0]; row[ORC_ZSB_REP_OUT + 1] = (int32_t)next->rep[1];
+            lsz = compress_literals(prev, next, out, bcap, m.lit, m.nlit, m.nseq == 0 || m.nlit / m.nseq >= 20, p.strat);
+            c = lsz;
+            if (lsz >= 0) {
+                ssz = encode_sequences(out + lsz, bcap - (size_t)lsz, m.seq, m.nseq, llc, ofc, mlc, p.strat, prev, next);
+                c = ssz <= 0 ? ssz : lsz + ssz;
+            }
+            if (c == ERR_TOOSMALL && len <= bcap) c = 0;
+            if (c < 0) { result = c; break; }
+            if (c > 0 && (size_t)c >= len - ((len >> 6) + 2)) c = 0;
+            if (!first && c < 25 && is_rle(src + pos, len)) { c = 1; out[0] = src[pos]; }
+            if (c > 1) cur ^= 1;                                                 /* ZSTD_blockState_confirmRepcodesAndEntropyTables */
+        }
+        row[ORC_ZSB_TYPE] = c == 0 ? 0 : c == 1 ? 1 : 2;
+        orc_tr_put(trace, ORC_TR_BLOCK, row, ORC_ZSTR_BLOCK_WORDS);
+        if (c == 0) {
+            const uint32_t h = last + ((uint32_t)len << 3);
+            dst[o] = (uint8_t)h; dst[o + 1] = (uint8_t)(h >> 8); dst[o + 2] = (uint8_t)(h >> 16);
+            memcpy(dst + o + 3, src + pos, len);
+            o += 3 + len;
+        } else {
+            const uint32_t h = c == 1 ? last + (1u << 1) + ((uint32_t)len << 3) : last + (2u << 1) + ((uint32_t)c << 3);
+            dst[o] = (uint8_t)h; dst[o + 1] = (uint8_t)(h >> 8); dst[o + 2] = (uint8_t)(h >> 16);
+            o += 3 + (size_t)c;
+        }
+        pos += len; first = 0; k++;
+    }
+    if (result >= 0 && n % BLOCK_MAX == 0) {                                     /* ZSTD_endStream with nothing buffered: ZSTD_writeEpilogue's empty raw last block */
+        if (cap - o < 3) result = ERR_TOOSMALL;
+        else { dst[o] = 1; dst[o + 1] = 0; dst[o + 2] = 0; o += 3; }
+    }
+    free(m.table); free(m.small); free(m.seq); free(m.lit); free(llc);
     return result < 0 ? result : (int64_t)o;
 }
 

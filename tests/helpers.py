@@ -278,6 +278,33 @@ def orc_zstd_compress_ex(src, level=1, cap=None):
     return r, dst[:max(r, 0)].copy(), [bufs[k][:t2.n[k]].reshape(-1, ZSTD_TRACE_WORDS[k]) for k in range(4)]
 
 
+ZSTD_STREAM_TRACE_WORDS = (10, 20, 12, 5)  # oracle.h ORC_ZSTR_*: SEARCH, BLOCK, SEQ, REP
+
+
+def orc_zstd_stream_compress(src, level, trace=False, mutate=0):
+    """orc_zstd_stream_compress_ex -> the image's bytes, or (bytes, [search, block, seq, rep] tables of int32 rows) with trace=True
+    (two runs, the first with no room to size the second)."""
+    src = np.ascontiguousarray(src, dtype=np.uint8)
+    L = oracle()
+    f = L.orc_zstd_stream_compress_ex
+    f.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]; f.restype = C.c_int64
+    cap = len(src) + (len(src) >> 7) + 4096
+    dst = np.empty(cap, dtype=np.uint8)
+    if not trace:
+        r = f(src.ctypes.data, len(src), level, dst.ctypes.data, cap, None, mutate)
+        assert r > 0, r
+        return dst[:r].tobytes()
+    t = OrcTrace()
+    f(src.ctypes.data, len(src), level, dst.ctypes.data, cap, C.byref(t), mutate)
+    bufs = [np.zeros(max(t.n[k], 1), np.int32) for k in range(4)]
+    t2 = OrcTrace()
+    for k in range(4):
+        t2.ev[k] = bufs[k].ctypes.data_as(C.POINTER(C.c_int32)); t2.cap[k] = len(bufs[k])
+    r = f(src.ctypes.data, len(src), level, dst.ctypes.data, cap, C.byref(t2), mutate)
+    assert r > 0 and [t2.n[k] for k in range(4)] == [t.n[k] for k in range(4)]
+    return dst[:r].tobytes(), [bufs[k][:t2.n[k]].reshape(-1, ZSTD_STREAM_TRACE_WORDS[k]) for k in range(4)]
+
+
 def golden_zstd_inputs():
     """The inputs of tests/golden/zstd_frames.json (frames written by the reference's ZSTD_compress at levels 1..12);
     tests/golden/make_golden.py generates the fixture from exactly these."""
