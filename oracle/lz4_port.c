@@ -56,10 +56,16 @@ static uint32_t common_len(const uint8_t* a, const uint8_t* b, const uint8_t* li
     return (uint32_t)(a - a0);
 }
 
-int orc_lz4_compress_fast(const uint8_t* src, uint8_t* dst, int n, int cap)
+/* The trace (oracle.h, ORC_LF_*): `filled` says which slots have been written (an empty slot reads as position 0), kept for a
+ * trace alone.  Nothing of it feeds back into the parse. */
+static void lf_event(orc_trace* t, int kind, uint32_t ip, uint32_t a, uint32_t b)
+{ const int32_t row[ORC_LF_EV_WORDS] = {kind, (int32_t)ip, (int32_t)a, (int32_t)b}; orc_tr_put(t, ORC_TR_ARM, row, ORC_LF_EV_WORDS); }
+
+int orc_lz4_compress_fast_ex(const uint8_t* src, uint8_t* dst, int n, int cap, orc_trace* tr)
 {
     uint32_t tab32[1 << HASHLOG];            /* viewed as 8192 u16 slots in TAB_U16 mode        */
     uint16_t* const tab16 = (uint16_t*)tab32;
+    uint8_t filled[1 << (HASHLOG + 1)];      /* trace only */
     const int limited = cap < orc_lz4_compress_bound(n);             /* lz4.c:1352            */
     const int tab = (n < SMALL_LIMIT) ? TAB_U16 : TAB_U32;            /* lz4.c:1353-1357       */
     uint8_t* op = dst;
@@ -71,8 +77,9 @@ int orc_lz4_compress_fast(const uint8_t* src, uint8_t* dst, int n, int cap)
         dst[0] = 0; return 1;
     }
     memset(tab32, 0, sizeof tab32);                                   /* LZ4_initStream :1348  */
+    if (tr) { memset(filled, 0, sizeof filled); lf_event(tr, ORC_LF_EV_TABLE, 0, (uint32_t)tab, 0); }
 #define TAB_GET(h)    ((tab == TAB_U32) ? tab32[h] : (uint32_t)tab16[h])
-#define TAB_PUT(h, v) do { if (tab == TAB_U32) tab32[h] = (v); else tab16[h] = (uint16_t)(v); } while (0)
+#define TAB_PUT(h, v) do { if (tab == TAB_U32) tab32[h] = (v); else tab16[h] = (uint16_t)(v); if (tr) filled[h] = 1; } while (0)
 
     if (n >= MINLEN) {
         const uint32_t mflimit_p1 = (uint32_t)n - MFLIMIT + 1;        /* first pos a match may NOT start at */
@@ -82,23 +89,38 @@ int orc_lz4_compress_fast(const uint8_t* src, uint8_t* dst, int n, int cap)
         for (;;) {
             uint32_t cand, fwd = ip, step = 1, tries = 1u << 6;      /* lz4.c:1014-1016        */
             uint8_t* token;
+            /* what the trace says of this search and its hit */
+            const uint32_t t_first = ip;
+            uint32_t t_probes = 0, t_empties = 0, t_ndist = 0, t_lastdist = 0, t_hit = 0, t_empty = 0, t_back = 0, t_stop = ORC_LF_STOP_NONE, t_retest = 0, t_shared = 0;
             /* probe forward until a 4-byte match inside the 64 KiB window turns up */
             for (;;) {
                 const uint32_t h = fwd_hash, cur = fwd;
                 cand = TAB_GET(h);
+                if (tr) { t_probes++; t_empty = !filled[h]; t_empties += t_empty; }
                 ip = fwd; fwd += step; step = tries++ >> 6;           /* lz4.c:1021-1023        */
-                if (fwd > mflimit_p1) goto last_literals;
+                if (fwd > mflimit_p1) {
+                    if (tr) { const int32_t row[ORC_LF_SEARCH_WORDS] = {(int32_t)t_first, (int32_t)t_probes, ORC_LF_END_LIMIT, (int32_t)t_empties}; orc_tr_put(tr, ORC_TR_SEARCH, row, ORC_LF_SEARCH_WORDS); }
+                    goto last_literals;
+                }
                 fwd_hash = hash_pos(src + fwd, tab);
                 TAB_PUT(h, cur);
-                if (tab == TAB_U32 && cand + MAX_DIST < cur) continue;   /* lz4.c:1064-1067     */
+                if (tab == TAB_U32 && cand + MAX_DIST < cur) {        /* lz4.c:1064-1067        */
+                    if (tr) { t_ndist++; t_lastdist = cur - cand; lf_event(tr, ORC_LF_EV_DIST, cur, cur - cand, rd32(src + cand) == rd32(src + cur)); }
+                    continue;
+                }
                 if (rd32(src + cand) == rd32(src + ip)) break;
             }
+            if (tr) { const int32_t row[ORC_LF_SEARCH_WORDS] = {(int32_t)t_first, (int32_t)t_probes, ORC_LF_END_HIT, (int32_t)t_empties}; orc_tr_put(tr, ORC_TR_SEARCH, row, ORC_LF_SEARCH_WORDS); }
+            t_hit = ip;
             /* extend backwards over equal bytes (lz4.c:1080) */
             while (ip > anchor && cand > 0 && src[ip - 1] == src[cand - 1]) { ip--; cand--; }
+            if (tr) { t_back = t_hit - ip; t_stop = ip == anchor ? ORC_LF_STOP_ANCHOR : cand == 0 ? ORC_LF_STOP_CAND0 : ORC_LF_STOP_BYTE; }
 
             {   const uint32_t lit = ip - anchor;
                 token = op++;
-                if (limited && (size_t)(op - dst) + lit + (2 + 1 + LASTLITERALS) + lit / 255 > (size_t)cap) return 0;   /* lz4.c:1085 */
+                if (limited && (size_t)(op - dst) + lit + (2 + 1 + LASTLITERALS) + lit / 255 > (size_t)cap) {   /* lz4.c:1085 */
+                    lf_event(tr, ORC_REFUSE_LITERALS, ip, 0, 0); return 0;
+                }
                 if (lit >= 15) {
                     uint32_t rest = lit - 15;
                     *token = 0xF0;
@@ -108,12 +130,21 @@ int orc_lz4_compress_fast(const uint8_t* src, uint8_t* dst, int n, int cap)
                 memcpy(op, src + anchor, lit); op += lit;
             }
         next_match:
-            {   const uint32_t off = ip - cand;
+            {   const uint32_t off = ip - cand, start = ip;
                 uint32_t mcode;
                 op[0] = (uint8_t)off; op[1] = (uint8_t)(off >> 8); op += 2;
                 mcode = common_len(src + ip + 4, src + cand + 4, matchlimit);
                 ip += mcode + 4;
-                if (limited && (size_t)(op - dst) + (1 + LASTLITERALS) + (mcode + 240) / 255 > (size_t)cap) return 0;   /* lz4.c:1158 */
+                if (limited && (size_t)(op - dst) + (1 + LASTLITERALS) + (mcode + 240) / 255 > (size_t)cap) {   /* lz4.c:1158 */
+                    lf_event(tr, ORC_REFUSE_MATCHLEN, start, 0, 0); return 0;
+                }
+                if (tr) {
+                    const int32_t row[ORC_LF_HIT_WORDS] = {(int32_t)t_hit, (int32_t)(t_hit - off), (int32_t)t_empty, (int32_t)t_ndist, (int32_t)t_lastdist,
+                        (int32_t)t_back, (int32_t)t_stop, (int32_t)(start - anchor), (int32_t)mcode, src + ip == matchlimit, (int32_t)t_retest, (int32_t)t_shared};
+                    const int32_t em[ORC_LF_EMIT_WORDS] = {(int32_t)(start - anchor), (int32_t)(mcode + 4), (int32_t)off};
+                    orc_tr_put(tr, ORC_TR_CAND, row, ORC_LF_HIT_WORDS);
+                    orc_tr_put(tr, ORC_TR_EMIT, em, ORC_LF_EMIT_WORDS);
+                }
                 if (mcode >= 15) {
                     *token += 15; mcode -= 15;
                     for (; mcode >= 255; mcode -= 255) *op++ = 255;
@@ -126,17 +157,26 @@ int orc_lz4_compress_fast(const uint8_t* src, uint8_t* dst, int n, int cap)
             {   const uint32_t h = hash_pos(src + ip, tab);           /* lz4.c:1218-1259        */
                 cand = TAB_GET(h);
                 TAB_PUT(h, ip);
+                if (tr) {
+                    t_shared = h == hash_pos(src + ip - 2, tab);
+                    if (tab == TAB_U32 && cand + MAX_DIST < ip) lf_event(tr, ORC_LF_EV_DIST, ip, ip - cand, rd32(src + cand) == rd32(src + ip));
+                }
                 if ((tab == TAB_U16 || cand + MAX_DIST >= ip) && rd32(src + cand) == rd32(src + ip)) {
                     token = op++; *token = 0;
+                    if (tr) { lf_event(tr, ORC_LF_EV_RETEST, ip, 1, t_shared); t_hit = ip; t_empty = 0; t_ndist = 0; t_lastdist = 0; t_back = 0; t_stop = ORC_LF_STOP_NONE; t_retest = 1; }
                     goto next_match;
                 }
+                if (tr) lf_event(tr, ORC_LF_EV_RETEST, ip, 0, t_shared);
             }
             fwd_hash = hash_pos(src + (++ip), tab);
         }
     }
 last_literals:
     {   const uint32_t run = (uint32_t)n - anchor;
-        if (limited && (size_t)(op - dst) + run + 1 + (run + 255 - 15) / 255 > (size_t)cap) return 0;   /* lz4.c:1269 */
+        if (limited && (size_t)(op - dst) + run + 1 + (run + 255 - 15) / 255 > (size_t)cap) {   /* lz4.c:1269 */
+            lf_event(tr, ORC_REFUSE_LAST, anchor, 0, 0); return 0;
+        }
+        if (tr) { const int32_t em[ORC_LF_EMIT_WORDS] = {(int32_t)run, 0, 0}; orc_tr_put(tr, ORC_TR_EMIT, em, ORC_LF_EMIT_WORDS); }
         if (run >= 15) {
             uint32_t rest = run - 15;
             *op++ = 0xF0;
@@ -149,6 +189,9 @@ last_literals:
 #undef TAB_GET
 #undef TAB_PUT
 }
+
+int orc_lz4_compress_fast(const uint8_t* src, uint8_t* dst, int n, int cap)
+{ return orc_lz4_compress_fast_ex(src, dst, n, cap, NULL); }
 
 /* ------------------------------------------------------------------------------------------ */
 /* Decoder                                                                                    */

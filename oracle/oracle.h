@@ -33,6 +33,23 @@ int orc_lz4_compress_bound(int n);
  * native/lz4/lz4.c:1435 -> :1416 -> :1346-1367 -> :910-1302.
  * Returns bytes written, or 0 when the output does not fit `cap` (limitedOutput). */
 int orc_lz4_compress_fast(const uint8_t* src, uint8_t* dst, int n, int cap);
+/* The same call with an orc_trace (NULL: none, and nothing is computed for it; the rules of orc_trace below hold).  The trace
+ * changes no byte.  Tables (int32 rows, positions are offsets into the input):
+ *   ORC_TR_SEARCH  ORC_LF_SEARCH_WORDS, one row per search: its first position, probes made (the one that hit or ran past the
+ *                  limit included), ORC_LF_END_HIT / ORC_LF_END_LIMIT (`fwd > mflimitPlusOne`), probes that read an empty slot (as position 0)
+ *   ORC_TR_CAND    ORC_LF_HIT_WORDS, one row per hit that became a sequence: the position that hit, its candidate, 1 when the candidate
+ *                  was an empty slot read as position 0, candidates of this search refused by distance and the last such distance,
+ *                  bytes walked back and ORC_LF_STOP_* (what ended the walk), literals, mcode (match length - 4), 1 when the match
+ *                  ended at matchlimit, 1 when the hit was the re-test behind a match (`_next_match` with no literals), 1 when that
+ *                  re-test read the slot the ip-2 refill had just written
+ *   ORC_TR_ARM     event rows of ORC_LF_EV_WORDS, unused words 0: ORC_REFUSE_LITERALS / _MATCHLEN / _LAST (the site of a refusal), position;
+ *                  ORC_LF_EV_TABLE, 0, table kind (0: 16-bit, 1: 32-bit); ORC_LF_EV_DIST, position, distance, 1 when the refused
+ *                  candidate holds the position's four bytes; ORC_LF_EV_RETEST, position, hit, 1 when the ip-2 refill wrote its slot
+ *   ORC_TR_EMIT    ORC_LF_EMIT_WORDS: literals, match length (0: the last literals), offset */
+enum { ORC_LF_SEARCH_WORDS = 4, ORC_LF_HIT_WORDS = 12, ORC_LF_EV_WORDS = 4, ORC_LF_EMIT_WORDS = 3 };
+enum { ORC_LF_END_HIT = 0, ORC_LF_END_LIMIT = 1 };
+enum { ORC_LF_STOP_ANCHOR = 0, ORC_LF_STOP_CAND0 = 1, ORC_LF_STOP_BYTE = 2, ORC_LF_STOP_NONE = 3 };
+enum { ORC_LF_EV_TABLE = 64, ORC_LF_EV_DIST = 65, ORC_LF_EV_RETEST = 66 };
 
 /* LZ4_compress_HC at any level (4mc uses 4 and 8; levels below 1 run as 9, levels above 12 as 12, native/lz4/lz4hc.c:840-841) -
  * :958-973 -> :553-788 (levels 1..9) / :1330-1626 (levels 10..12).  Returns bytes written, 0 when it does not fit `cap`. */
@@ -89,6 +106,7 @@ enum {  /* the statements of LZ4HC_compress_hashChain's arbitration (lz4hc.c:592
 enum { ORC_SHARE_NTU_PREV = 1, ORC_SHARE_NTU_IP = 2, ORC_SHARE_PREV_IP = 4,       /* two slots of one probe in one bucket ... */
        ORC_DIFF_NTU_PREV = 8, ORC_DIFF_NTU_IP = 16, ORC_DIFF_PREV_IP = 32 };      /* ... holding different words */
 int orc_lz4hc_compress_ex(const uint8_t* src, uint8_t* dst, int n, int cap, int level, orc_trace* trace);
+int orc_lz4_compress_fast_ex(const uint8_t* src, uint8_t* dst, int n, int cap, orc_trace* trace);   /* (described beside orc_lz4_compress_fast) */
 /* The trace of HC levels 9..12 (any level below 1 or above 8 after the mapping) has rows of its own; the rules above hold.
  *   ORC_TR_SEARCH  one row per search, ORC_HX_SEARCH_WORDS: sequences emitted before it, ip, low, longest on entry, candidates
  *                  walked, ORC_END_* (ORC_END_BREAK: the walk left through a `break`), the winner's number in the walk (-1: none),

@@ -96,6 +96,10 @@ json.dump(zf, open(os.path.join(HERE, "zstd_frames.json"), "w"))
 import zstd_shapes  # noqa: E402
 json.dump(zstd_shapes.fixture_select(zstd_shapes.frames()), open(zstd_shapes.FIXTURE, "w"), indent=0)
 
+# the exact LZ4 fast encoder's catalogue (tests/lz4_enc_shapes.py): SHA-256 of LZ4_compress_default's result and bytes per (input, capacity) pair
+import lz4_enc_shapes  # noqa: E402
+json.dump(lz4_enc_shapes.reference_digests(ref), open(lz4_enc_shapes.FIXTURE, "w"), indent=0, sort_keys=True)
+
 # the reference's shipped JNI library through the mock JNIEnv driver: stdout, size + SHA-256 of every payload, stream sizes
 from test_jni_reference_artifact import REF_SO, RUNS, run_driver  # noqa: E402
 assert os.path.exists(REF_SO), REF_SO
